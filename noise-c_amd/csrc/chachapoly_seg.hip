@@ -210,10 +210,21 @@ struct SegIOL {
        interior for every owner: no clamp, no limit test per instruction
        (≈100 of a step's ≈2300 VALU, the owner-geometry arithmetic) */
     uint32_t min_hi, min_sl;
+    /* wave-uniform: each of a step's eight DMA instructions has an owner
+       with blocks.  An instruction whose eight owners all have none (idle
+       lanes of the plan's last job) is skipped by the whole wave and never
+       counts in vmcnt */
+    bool all8;
+    NA_DEV bool dma8() const { return all8; }
     NA_DEV void init(const SegLane &q, uint32_t lane)
     {
         const SegOwner g = seg_geom(q);
         tab[lane] = g;
+        uint64_t any = __ballot(g.hi != 0); /* byte i: instruction i's owners */
+        any |= any >> 4;
+        any |= any >> 2;
+        any |= any >> 1;
+        all8 = (any & 0x0101010101010101ull) == 0x0101010101010101ull;
         uint32_t h = g.hi ? g.hi : 0xffffffffu, sl = g.hi ? (g.sl & 0x7fffffffu) : 0xffffffffu;
 #pragma unroll
         for (int off = 1; off < 64; off <<= 1) {
@@ -277,6 +288,9 @@ struct SegIOU {
     uint32_t hi, sl;   /* its geometry (every record has the same length) */
     uint32_t livem;    /* bit i: owner record rec0 + 4i + lane/16 exists */
     bool full;         /* wave-uniform: all 32 records of the wave exist */
+    /* a step's DMA is eight instructions: in a partial wave the ones whose
+       four records are all past the batch are skipped by the whole wave */
+    NA_DEV bool dma8() const { return full; }
     NA_DEV void init(const UniformArgs &a, uint32_t rec0, const SegLane &q, uint32_t lane)
     {
         in = a.in + (size_t)rec0 * a.in_stride;
@@ -530,7 +544,10 @@ NA_DEV void seg_auth(const SegLane &q, const IO &io, uint32_t lane, uint32_t S, 
     for (uint32_t m = 0; m < S; ++m) {
         uint4 *cur = tiles + SOLO_TILE * (m & 1);
         uint32_t wu[2][16];
-        if (m + 1 < S) solo_wait_step_old();
+        /* the step-old wait leaves eight instructions, the next step's DMA,
+           in flight: a wave whose steps issue fewer waits for them all, or it
+           would read this step's tile before its DMA has landed */
+        if (m + 1 < S && io.dma8()) solo_wait_step_old();
         else solo_wait();
         solo_get(cur, lane, 0, wu[0]);
         solo_get(cur, lane, 1, wu[1]);

@@ -139,6 +139,52 @@ def test_bench_module_constants_exist():
     assert not missing, missing
 
 
+def test_dump_checksums_and_sample(tmp_path):
+    """--dump-outputs helpers on CPU tensors: the per-record checksums equal
+    a direct sum over each record's bytes (ragged records with unread gaps,
+    several chunks), the record sample is fixed and holds both ends, and the
+    files are float arrays within the size limit."""
+    import numpy as np
+    import torch
+
+    rng = np.random.default_rng(7)
+    lens = rng.integers(1, 300, size=97).astype(np.int64)
+    gaps = rng.integers(0, 64, size=97).astype(np.int64)
+    starts = np.cumsum(lens + gaps) - lens
+    buf = rng.integers(0, 256, size=int(starts[-1] + lens[-1]) + 5, dtype=np.uint8)
+    want = np.array([[buf[s:s + n].sum(dtype=np.int64),
+                      (buf[s:s + n].astype(np.int64) * np.arange(1, n + 1)).sum()]
+                     for s, n in zip(starts, lens)], dtype=np.float64)
+    for chunk in (1 << 24, 1000, 1):
+        got = bench.record_checksums(torch, torch.from_numpy(buf), starts, lens, chunk_bytes=chunk)
+        assert got.dtype == np.float64 and np.array_equal(got, want), chunk
+
+    a, b = bench.dump_sample(65536, 1024), bench.dump_sample(65536, 1024)
+    assert np.array_equal(a, b) and a[0] == 0 and a[-1] == 65535
+    assert 1024 <= len(a) <= 1026 and np.all(np.diff(a) > 0)
+    assert np.array_equal(bench.dump_sample(10, 1024), np.arange(10))
+
+    bench.write_dump(str(tmp_path / "d"), {"x": want, "y": np.zeros(3, dtype=np.float32)})
+    assert np.array_equal(np.load(tmp_path / "d" / "x.npy"), want)
+    assert sorted(os.listdir(tmp_path / "d")) == ["x.npy", "y.npy"]
+    import pytest
+    with pytest.raises(AssertionError):
+        bench.write_dump(str(tmp_path / "e"), {"big": np.zeros(bench.DUMP_LIMIT // 8 + 1)})
+    with pytest.raises(AssertionError):
+        bench.write_dump(str(tmp_path / "f"), {"bytes": np.zeros(3, dtype=np.uint8)})
+
+
+def test_parser_knows_full_and_dump_outputs():
+    """The parser takes --full and --dump-outputs DIR beside the driver's
+    arguments and refuses a run without timed steps."""
+    r = _bench(["--gpus", "1", "--dry-run", "--full", "--dump-outputs", "unused", "--steps", "4",
+                "--warmup", "1"])
+    assert r.returncode == 0, r.stderr[-2000:]
+    d = json.loads(r.stdout.strip().splitlines()[-1])
+    assert d["steps"] == 4 and d["warmup"] == 1 and d["ms_per_step"] >= 0 and d["unit"] == "GiB/s"
+    assert _bench(["--dry-run", "--steps", "0"]).returncode == 2
+
+
 def test_group_runs_keep_stdout_for_the_line():
     """A run with a process group points fd 1 at stderr (RCCL prints its
     banner on stdout when a communicator is made); the JSON line still goes

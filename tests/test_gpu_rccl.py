@@ -30,8 +30,9 @@ def _run(config, extra=(), rehearse_ranks=0):
     e = dict(os.environ)
     for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT"):
         e.pop(k, None)
-    common = ["--config", config, "--steps", "3", "--warmup", "1", "--settle-ms", "0", "--no-cpu-baseline",
-              "--xfer-reps", "2", *extra]
+    # --full: the checks and the scatter/seal/gather leg run only with it
+    common = ["--config", config, "--steps", "3", "--warmup", "1", "--settle-ms", "0", "--full",
+              "--no-cpu-baseline", "--xfer-reps", "2", *extra]
     if rehearse_ranks:  # bench.py starts its own ranks, all on this GPU, gloo
         e["NOISE_BENCH_REHEARSE"] = "1"
         cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", str(rehearse_ranks), "--no-n1"]

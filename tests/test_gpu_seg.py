@@ -193,6 +193,30 @@ def test_uniform_seg2_vs_oracle(aead, gpu, oracle, vf, rps):
                 assert np.array_equal(g[i * outs: i * outs + L], pt[i * ins: i * ins + L]), (L, i)
 
 
+@pytest.mark.parametrize("count", [33, 37, 70, 95])
+def test_uniform_seg2_verify_first_partial_wave(aead, gpu, oracle, count):
+    """A verify-first open whose last wave holds 1, 5, 6 or 31 of its 32
+    records: that wave's step DMA is fewer than eight instructions (the ones
+    whose records are all past the batch are skipped), so the AUTH pass may
+    not leave "one step's eight" in flight when it reads a tile.  Records of
+    several steps (6, 20 and 65 two-block steps per segment), none tampered:
+    every record is accepted and opens to its plaintext."""
+    rng = np.random.default_rng(977 + count)
+    rps = 16
+    for L in (1400, 5000, 16384):
+        S = (count + rps - 1) // rps
+        keys = rng.integers(0, 256, (S, 32), dtype=np.uint8)
+        nb = rng.integers(0, 2**63, S, dtype=np.uint64)
+        ins = outs = ((L + 63) // 64) * 64 + 64
+        pt = rng.integers(0, 256, count * ins + 64, dtype=np.uint8)
+        exp = oracle_seal_records(oracle, CHACHA, keys, nb, rps, pt, ins, L, count, outs)
+        back, st = gpu_uniform(aead, True, CHACHA, keys, nb, rps, exp, outs, L, count, ins, lanes=2,
+                               out_init=0x5A, flags=aead.FLAG_VERIFY_FIRST)
+        assert not st.any(), (L, np.nonzero(st)[0].tolist())
+        for i in range(count):
+            assert np.array_equal(back[i * ins: i * ins + L], pt[i * ins: i * ins + L]), (L, i)
+
+
 def test_default_lanes_segmented(aead):
     """The library's choice: four lanes for a standalone 64 Ki-record
     ChaChaPoly job (two segments measured slower there), one lane from

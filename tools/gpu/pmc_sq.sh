@@ -8,7 +8,7 @@ cd /tmp && export TMPDIR=/tmp
 run() {
   local name=$1; shift
   timeout -k 10 240 rocprofv3 --kernel-trace --pmc "$@" -d $OUT/$name -o run --output-format csv -- \
-      python3 $R/bench.py --config $CFG --no-cpu-baseline --steps 10 --warmup 2 "$EXTRA_ARGS" > $OUT/$name.log 2>&1
+      python3 $R/bench.py --config $CFG --full --no-cpu-baseline --steps 10 --warmup 2 "$EXTRA_ARGS" > $OUT/$name.log 2>&1
   echo "pmc $name rc=$?"
 }
 EXTRA_ARGS="${*:---sets=4}"

@@ -68,12 +68,12 @@ step() {  # kind name args...
     echo "smoke rc=$rc: $(tail -1 "$O/smoke.log")" ;;
   bench)
     local name=$1; shift
-    timeout -k 10 400 python bench.py "$@" > "$O/$name.json" 2> "$O/$name.err" || rc=$?
+    timeout -k 10 400 python bench.py --full "$@" > "$O/$name.json" 2> "$O/$name.err" || rc=$?
     if [ $rc -eq 0 ]; then summ "$name" "$O/$name.json"; else echo "bench $name rc=$rc"; tail -5 "$O/$name.err"; fi ;;
   prof)
     local name=$1; shift
     ( cd /tmp && timeout -k 10 400 rocprofv3 --kernel-trace --stats -d "$O/$name" -o run --output-format csv -- \
-        python3 "$R/bench.py" "$@" > "$O/$name.json" 2> "$O/$name.err" ) || rc=$?
+        python3 "$R/bench.py" --full "$@" > "$O/$name.json" 2> "$O/$name.err" ) || rc=$?
     if [ $rc -eq 0 ]; then
       summ "$name" "$O/$name.json"
       # the timed window: the last --steps dispatches of the line's kernel
@@ -104,7 +104,7 @@ PY
     for i in $(seq "$rounds"); do
       for v in $libs; do
         if [ "$v" = cur ]; then unset NOISE_AEAD_LIB; else export NOISE_AEAD_LIB=$R/noise-c_amd/ab/libnoise_aead_hip_$v.so; fi
-        timeout -k 10 400 python bench.py "$@" > "$O/$name.$v.$i.json" 2> "$O/$name.$v.$i.err" || rc=$?
+        timeout -k 10 400 python bench.py --full "$@" > "$O/$name.$v.$i.json" 2> "$O/$name.$v.$i.err" || rc=$?
         unset NOISE_AEAD_LIB
         if [ $rc -ne 0 ]; then echo "ab $name $v rc=$rc"; tail -5 "$O/$name.$v.$i.err"; fatal $rc && return $rc; rc=0; continue; fi
         python3 -c "import json,sys;d=json.loads(open('$O/$name.$v.$i.json').read().strip().splitlines()[-1]);d['ab']={'variant':'$v','round':$i};print(json.dumps(d))" >> "$O/$name.jsonl"
@@ -125,7 +125,7 @@ PY
         for w in ${sets[$k]}; do
           if [ ${#args[@]} -eq 0 ] && [[ "$w" == [A-Z]*=* ]]; then envs+=("$w"); else args+=("$w"); fi
         done
-        timeout -k 10 400 env "${envs[@]}" python bench.py "${args[@]}" > "$O/$name.$k.$i.json" 2> "$O/$name.$k.$i.err" || rc=$?
+        timeout -k 10 400 env "${envs[@]}" python bench.py --full "${args[@]}" > "$O/$name.$k.$i.json" 2> "$O/$name.$k.$i.err" || rc=$?
         if [ $rc -ne 0 ]; then echo "abargs $name $k rc=$rc"; tail -5 "$O/$name.$k.$i.err"; fatal $rc && return $rc; rc=0; continue; fi
         python3 -c "import json;d=json.loads(open('$O/$name.$k.$i.json').read().strip().splitlines()[-1]);d['ab']={'args':'''${sets[$k]}''','round':$i};print(json.dumps(d))" >> "$O/$name.jsonl"
         summ "$name [${sets[$k]} ] r$i" "$O/$name.$k.$i.json"
