@@ -42,6 +42,25 @@
  * OPEN1: the opt-in NOISE_AEAD_FLAG_ONE_PASS of the FAST layouts) decrypt as
  * they authenticate and undo the plaintext of a rejected record before the
  * kernel ends (restored in place, zeroed out of place).
+ *
+ * Kernel map: per family a record struct with its setup, a Poly1305 step-0
+ * setup, a pass body per PassMode, an AUTH pass and a repair, composed by
+ * short seal / open functions.
+ *   windowed interleaved (K = 4..64; *_uniform, *_ragged): IlRec + il_rec
+ *     (RecKey + rec_key), il_poly_setup, il_pass<MODE>, il_auth, il_repair;
+ *     seal_il, open_il_1p, open_il;
+ *   contiguous (K = 1, 2): RecKey, CtPlan + ct_plan, ct_poly_key; seal_ct
+ *     and open_ct keep their own loops (a run of blocks per lane);
+ *   staged (K = 4, 8, uniform FAST; *_staged): StagedRec + staged_rec,
+ *     staged_poly_setup, staged_pass<SEAL | OPEN1>, staged_verdict,
+ *     staged_repair; seal_il_staged, open_il_staged; open_il_staged_vf
+ *     (AUTH + DEC) keeps one body of its own, see there;
+ *   one lane (uniform FAST; *_solo): SoloRec + solo_rec, solo_poly_key,
+ *     solo_pass<SEAL | OPEN1>, solo_auth, solo_dec_rev (DEC, last step
+ *     first), solo_repair; seal_solo_staged, open_solo_staged;
+ *   segmented (chachapoly_seg.hip): SegLane, seg_pass<MODE>, seg_auth,
+ *     seg_repair; seg_job.
+ * owner_mask<N> gates a staged tile's N coalesced stores by the verdicts.
  */
 #include "aead_device.h"
 #include "aead_kernels.h"
@@ -49,6 +68,26 @@
 namespace na {
 
 typedef __attribute__((address_space(3))) void lds_void;
+
+/* What a pass over a record's units does (il_pass, staged_pass, solo_pass,
+   chachapoly_seg.hip seg_pass).  SEAL: plaintext -> CT, Poly1305 over the
+   CT; OPEN1 (NOISE_AEAD_FLAG_ONE_PASS): Poly1305 over the CT as read,
+   plaintext out before the verdict; DEC: the verify-first open's second
+   pass, key stream and XOR only, stores gated by the verdicts. */
+enum PassMode { PASS_SEAL, PASS_OPEN1, PASS_DEC };
+
+/* bit i (i < N): owner (64/N) i + lane/N, whose chunk this lane moves in
+   coalesced instruction i of a staged tile (N = 4: 4 KB tiles, 8: 8 KB), has
+   the flag */
+template <int N>
+NA_DEV uint32_t owner_mask(bool flag, uint32_t lane)
+{
+    uint32_t m = 0;
+#pragma unroll
+    for (int i = 0; i < N; ++i)
+        m |= (__shfl((int)flag, (int)((64u / N) * i + lane / N), 64) != 0 ? 1u : 0u) << i;
+    return m;
+}
 
 /* One record as seen by its group of lanes. */
 struct RecView {
@@ -123,36 +162,48 @@ NA_DEV void pick_chunk(const uint32_t w[16], uint32_t c, uint32_t o[4])
         o[i] = c == 0 ? w[i] : (c == 1 ? w[4 + i] : (c == 2 ? w[8 + i] : w[12 + i]));
 }
 
+/* FAST exact-size store of a record's last unit: nb (1..64) bytes at p
+   (16-B aligned): aligned chunks as dwordx4, a partial chunk of 8 bytes as
+   one 8-B store. */
+NA_DEV void last_unit_out(uint8_t *p, uint32_t nb, const uint32_t w[16])
+{
+#pragma unroll
+    for (uint32_t c = 0; c < 4; ++c)
+        if (16 * c + 16 <= nb)
+            *(uint4 *)(p + 16 * c) = make_uint4(w[4 * c], w[4 * c + 1], w[4 * c + 2], w[4 * c + 3]);
+    const uint32_t rem = nb & 15;
+    if (rem) {
+        uint32_t part[4];
+        pick_chunk(w, nb >> 4, part);
+        uint8_t *q = p + (nb & ~15u);
+        if (rem == 8) *(uint2 *)q = make_uint2(part[0], part[1]);
+        else store16(q, rem, part);
+    }
+}
+
+/* FAST tag store at p = record + len (p is 16-B aligned iff len % 16 == 0;
+   8-B stores when len % 8 == 0). */
+NA_DEV void tag_out(uint8_t *p, uint32_t len, const uint32_t t[4])
+{
+    if ((len & 15) == 0) {
+        *(uint4 *)p = make_uint4(t[0], t[1], t[2], t[3]);
+    } else if ((len & 7) == 0) {
+        *(uint2 *)p = make_uint2(t[0], t[1]);
+        *(uint2 *)(p + 8) = make_uint2(t[2], t[3]);
+    } else {
+        store16(p, 16, t);
+    }
+}
+
 /* Exact-size store of the last unit's bytes [64(J-1), len), then (seal) the
-   tag at len.  FAST: aligned chunks as dwordx4, the partial chunk merged with
-   the tag into 8-B stores when len % 8 == 0. */
+   tag at len. */
 template <bool FAST, bool TAG>
 NA_DEV void tail_out(uint8_t *rec, uint32_t J, uint32_t len, const uint32_t w[16],
                      const uint32_t tag[4])
 {
     if constexpr (FAST) {
-        uint32_t rem = 0, part[4] = {0, 0, 0, 0};
-        if (J >= 1) {
-            const uint32_t base = 64 * (J - 1), nb = len - base;
-#pragma unroll
-            for (uint32_t c = 0; c < 4; ++c)
-                if (16 * c + 16 <= nb)
-                    *(uint4 *)(rec + base + 16 * c) =
-                        make_uint4(w[4 * c], w[4 * c + 1], w[4 * c + 2], w[4 * c + 3]);
-            rem = nb & 15;
-            if (rem) pick_chunk(w, nb >> 4, part);
-        }
-        const uint32_t pstart = len - rem;
-        if (rem == 8) {
-            *(uint2 *)(rec + pstart) = make_uint2(part[0], part[1]);
-            if (TAG) {
-                *(uint2 *)(rec + len) = make_uint2(tag[0], tag[1]);
-                *(uint2 *)(rec + len + 8) = make_uint2(tag[2], tag[3]);
-            }
-        } else {
-            if (rem) store16(rec + pstart, rem, part);
-            if (TAG) store16(rec + len, 16, tag);
-        }
+        if (J >= 1) last_unit_out(rec + 64 * (J - 1), len - 64 * (J - 1), w);
+        if (TAG) tag_out(rec + len, len, tag);
     } else {
         if (J >= 1) store_unit(rec + 64 * (J - 1), len - 64 * (J - 1), w);
         if (TAG) store16(rec + len, 16, tag);
@@ -402,68 +453,203 @@ NA_DEV void slot_block(const uint32_t key[8], const ChaPre &pre, int v, uint32_t
     }
 }
 
-template <int K, bool FAST>
-NA_DEV void seal_il(const RecView &rv, int k)
-{
-    uint32_t key[8];
-    load_key(rv.key, key);
-    const uint32_t n_lo = (uint32_t)rv.nonce, n_hi = (uint32_t)(rv.nonce >> 32);
+/* A record's key, nonce and ChaCha block prefix (the windowed kernels). */
+struct RecKey {
+    uint32_t key[8], n_lo, n_hi;
     ChaPre pre;
-    chacha_pre(key, n_lo, n_hi, pre);
-    const uint32_t len = rv.len;
-    const GroupCtx<K> g = group_ctx<K>(len);
-    const int gbase = (int)(threadIdx.x & 63) & ~(K - 1);
-    const bool tree = K >= 16 && g.steps == 1; /* poly_tree_close */
+};
 
-    Fe acc = fe_zero(), r;
+NA_DEV RecKey rec_key(const RecView &rv)
+{
+    RecKey c;
+    load_key(rv.key, c.key);
+    c.n_lo = (uint32_t)rv.nonce;
+    c.n_hi = (uint32_t)(rv.nonce >> 32);
+    chacha_pre(c.key, c.n_lo, c.n_hi, c.pre);
+    return c;
+}
+
+/* Per-lane view of a record in the windowed interleaved kernels. */
+template <int K>
+struct IlRec {
+    RecKey c;
+    GroupCtx<K> g;
+    uint32_t len, tail; /* tail: bytes of unit J-1 */
+    int gbase;
+    bool tree;          /* poly_tree_close */
+};
+
+template <int K>
+NA_DEV IlRec<K> il_rec(const RecView &rv)
+{
+    IlRec<K> q;
+    q.c = rec_key(rv);
+    q.len = rv.len;
+    q.g = group_ctx<K>(q.len);
+    q.gbase = (int)(threadIdx.x & 63) & ~(K - 1);
+    q.tree = K >= 16 && q.g.steps == 1;
+    q.tail = q.g.J ? q.len - 64 * (q.g.J - 1) : 0;
+    return q;
+}
+
+/* A lane's Poly1305 state in the interleaved kernels (r, mfinal: the
+   windowed ones; the staged ones park the final scale in a FinSlot). */
+struct IlPoly {
+    Fe acc = {0, 0, 0, 0, 0}, r;
     Mul mr, mjump, mfinal;
-    uint32_t s[4], wn[16], wc[16], x[16];
-    bool seen = false;
+    uint32_t s[4];
+    bool seen = false; /* the lane has absorbed a unit: the next follows by mjump */
+};
+
+/* Step 0: r and s from the key block x of lane o, the powers, the AD. */
+template <int K>
+NA_DEV void il_poly_setup(const RecView &rv, const IlRec<K> &q, int k, const uint32_t x[16], IlPoly &p)
+{
+    poly_key_bcast(x, q.gbase + (int)q.g.o, p.r, p.s);
+    p.mr = mk_mul(p.r);
+    if (!q.tree) poly_powers<K>(p.r, k, q.g.q, p.mjump, p.mfinal);
+    /* unit 0 (block 1) sits in lane (o+1) % K; with no units, lane K-1 */
+    const int k0 = q.g.J ? (int)((q.g.o + 1) % K) : K - 1;
+    if (k == k0 && rv.ad_len) poly_ad(p.acc, p.mr, rv.ad, rv.ad_len);
+}
+
+/* nb Poly blocks of unit c.  A lane's first unit follows the AD directly
+   (gap 1) or starts from acc = 0, where any multiplier works: use r */
+NA_DEV void il_poly_unit(IlPoly &p, const uint32_t c[16], uint32_t nb)
+{
+    poly_unit(p.acc, p.seen ? p.mjump : p.mr, p.mr, c, nb);
+    p.seen = true;
+}
+
+template <int K>
+NA_DEV void il_close(const RecView &rv, const IlRec<K> &q, int k, const IlPoly &p, uint32_t tag[4])
+{
+    if (q.tree) poly_tree_close<K>(p.acc, k, p.r, p.mr, q.g.J, q.g.q, rv.ad_len, q.len, p.s, tag);
+    else poly_close<K>(p.acc, k, p.mr, p.mfinal, rv.ad_len, q.len, p.s, tag);
+}
+
+/* The prefetch queue of a pass: wn holds the unit of the lane's next slot.
+   il_first loads step 0's; il_next moves it to wc, loads the following
+   step's and returns step m's slot v (block v, unit v-1). */
+template <int K, bool FAST>
+NA_DEV void il_first(const RecView &rv, const IlRec<K> &q, int k, uint32_t wn[16])
+{
 #pragma unroll
     for (int i = 0; i < 16; ++i) wn[i] = 0;
-    {
-        const int v = k - (int)g.o;
-        unit_prefetch<FAST>(rv.src, v >= 1, (uint32_t)v - 1, len, wn);
-    }
-    for (uint32_t m = 0; m < g.steps; ++m) {
-        const int v = (int)(m * K + (uint32_t)k) - (int)g.o;
+    const int v = k - (int)q.g.o;
+    unit_prefetch<FAST>(rv.src, v >= 1, (uint32_t)v - 1, q.len, wn);
+}
+
+template <int K, bool FAST>
+NA_DEV int il_next(const RecView &rv, const IlRec<K> &q, int k, uint32_t m, uint32_t wn[16], uint32_t wc[16])
+{
+    const int v = (int)(m * K + (uint32_t)k) - (int)q.g.o;
 #pragma unroll
-        for (int i = 0; i < 16; ++i) wc[i] = wn[i];
-        const int vn = v + K; /* the unit of the next step, loaded now */
-        unit_prefetch<FAST>(rv.src, m + 1 < g.steps && vn >= 1, (uint32_t)vn - 1, len, wn);
-        slot_block(key, pre, v, n_lo, n_hi, x);
-        if (m == 0) {
-            poly_key_bcast(x, gbase + (int)g.o, r, s);
-            mr = mk_mul(r);
-            if (!tree) poly_powers<K>(r, k, g.q, mjump, mfinal);
-            /* unit 0 (block 1) sits in lane (o+1) % K; with no units, lane K-1 */
-            const int k0 = g.J ? (int)((g.o + 1) % K) : K - 1;
-            if (k == k0 && rv.ad_len) poly_ad(acc, mr, rv.ad, rv.ad_len);
+    for (int i = 0; i < 16; ++i) wc[i] = wn[i];
+    const int vn = v + K; /* the unit of the next step, loaded now */
+    unit_prefetch<FAST>(rv.src, m + 1 < q.g.steps && vn >= 1, (uint32_t)vn - 1, q.len, wn);
+    return v;
+}
+
+/* One pass over the lane's slots with the key stream.  SEAL leaves the last
+   unit in wl, masked, for the caller's tail_out with the tag; OPEN1 and DEC
+   store it themselves.  DEC: step 0's key stream x0 is kept from before the
+   AUTH pass.  SEAL / OPEN1 run the step-0 Poly1305 setup on their first block. */
+template <int K, bool FAST, int MODE>
+NA_DEV void il_pass(const RecView &rv, const IlRec<K> &q, int k, IlPoly &p, const uint32_t x0[16],
+                    uint32_t wl[16])
+{
+    const GroupCtx<K> &g = q.g;
+    uint32_t wn[16], wc[16], x[16];
+    il_first<K, FAST>(rv, q, k, wn);
+    for (uint32_t m = 0; m < g.steps; ++m) {
+        const int v = il_next<K, FAST>(rv, q, k, m, wn, wc);
+        if constexpr (MODE == PASS_DEC) {
+            if (m == 0) {
+#pragma unroll
+                for (int i = 0; i < 16; ++i) x[i] = x0[i];
+            } else {
+                chacha20_block_pre(q.c.key, q.c.pre, (uint32_t)v, q.c.n_lo, q.c.n_hi, x);
+            }
+        } else {
+            slot_block(q.c.key, q.c.pre, v, q.c.n_lo, q.c.n_hi, x);
+            if (m == 0) il_poly_setup<K>(rv, q, k, x, p);
         }
         if (v >= 1 && (uint32_t)v < g.J) { /* a full unit */
+            if constexpr (MODE == PASS_OPEN1) il_poly_unit(p, wc, 4);
             uint32_t w[16];
 #pragma unroll
             for (int i = 0; i < 16; ++i) w[i] = wc[i] ^ x[i];
             unit_out_full<FAST>(rv.dst + 64 * (v - 1), w);
-            /* a lane's first unit follows the AD directly (gap 1) or starts
-               from acc = 0, where any multiplier works: use r */
-            poly_unit(acc, seen ? mjump : mr, mr, w, 4);
-            seen = true;
+            if constexpr (MODE == PASS_SEAL) il_poly_unit(p, w, 4);
         }
     }
     /* the last unit (block J) is lane K-1's last step */
-    uint32_t w[16];
+    if constexpr (MODE == PASS_SEAL) {
 #pragma unroll
-    for (int i = 0; i < 16; ++i) w[i] = wc[i] ^ x[i];
-    if (k == K - 1 && g.J >= 1) {
-        const uint32_t nb = len - 64 * (g.J - 1);
-        mask_unit(w, nb);
-        poly_unit(acc, seen ? mjump : mr, mr, w, (nb + 15) / 16);
+        for (int i = 0; i < 16; ++i) wl[i] = wc[i] ^ x[i];
+        if (k == K - 1 && g.J >= 1) {
+            mask_unit(wl, q.tail);
+            il_poly_unit(p, wl, (q.tail + 15) / 16);
+        }
+    } else if (k == K - 1 && g.J >= 1) {
+        uint32_t w[16];
+#pragma unroll
+        for (int i = 0; i < 16; ++i) w[i] = wc[i] ^ x[i];
+        if constexpr (MODE == PASS_OPEN1) {
+            mask_unit(wc, q.tail);
+            il_poly_unit(p, wc, (q.tail + 15) / 16);
+        }
+        tail_out<FAST, false>(rv.dst, g.J, q.len, w, nullptr);
     }
-    uint32_t tag[4];
-    if (tree) poly_tree_close<K>(acc, k, r, mr, g.J, g.q, rv.ad_len, len, s, tag);
-    else poly_close<K>(acc, k, mr, mfinal, rv.ad_len, len, s, tag);
-    if (k == K - 1) tail_out<FAST, true>(rv.dst, g.J, len, w, tag);
+}
+
+/* The verify-first open's AUTH pass: Poly1305 over the ciphertext only. */
+template <int K, bool FAST>
+NA_DEV void il_auth(const RecView &rv, const IlRec<K> &q, int k, IlPoly &p)
+{
+    uint32_t wn[16], wc[16];
+    il_first<K, FAST>(rv, q, k, wn);
+    for (uint32_t m = 0; m < q.g.steps; ++m) {
+        const int v = il_next<K, FAST>(rv, q, k, m, wn, wc);
+        if (v >= 1) {
+            uint32_t nb = 4;
+            if ((uint32_t)v == q.g.J) {
+                mask_unit(wc, q.tail);
+                nb = (q.tail + 15) / 16;
+            }
+            il_poly_unit(p, wc, nb);
+        }
+    }
+}
+
+/* A rejected one-pass open's repair in place: plaintext XOR key stream = the
+   ciphertext as given. */
+template <int K>
+NA_DEV void il_repair(const RecView &rv, const IlRec<K> &q, int k)
+{
+    for (uint32_t m = 0; m < q.g.steps; ++m) {
+        const int v = (int)(m * K + (uint32_t)k) - (int)q.g.o;
+        if (v < 1) continue;
+        uint32_t x[16], w[16];
+        slot_block(q.c.key, q.c.pre, v, q.c.n_lo, q.c.n_hi, x);
+        unit_in<true>(rv.dst, (uint32_t)v - 1, q.len, w);
+#pragma unroll
+        for (int i = 0; i < 16; ++i) w[i] ^= x[i];
+        if ((uint32_t)v < q.g.J) unit_out_full<true>(rv.dst + 64 * (v - 1), w);
+        else tail_out<true, false>(rv.dst, q.g.J, q.len, w, nullptr);
+    }
+}
+
+template <int K, bool FAST>
+NA_DEV void seal_il(const RecView &rv, int k)
+{
+    const IlRec<K> q = il_rec<K>(rv);
+    IlPoly p;
+    uint32_t w[16], tag[4];
+    il_pass<K, FAST, PASS_SEAL>(rv, q, k, p, nullptr, w);
+    il_close<K>(rv, q, k, p, tag);
+    if (k == K - 1) tail_out<FAST, true>(rv.dst, q.g.J, q.len, w, tag);
 }
 
 /* Open in one pass (FAST layouts): seal_il's loop with Poly1305 over the
@@ -476,170 +662,34 @@ NA_DEV void seal_il(const RecView &rv, int k)
 template <int K>
 NA_DEV bool open_il_1p(const RecView &rv, int k)
 {
-    uint32_t key[8];
-    load_key(rv.key, key);
-    const uint32_t n_lo = (uint32_t)rv.nonce, n_hi = (uint32_t)(rv.nonce >> 32);
-    ChaPre pre;
-    chacha_pre(key, n_lo, n_hi, pre);
-    const uint32_t len = rv.len;
-    const GroupCtx<K> g = group_ctx<K>(len);
-    const int gbase = (int)(threadIdx.x & 63) & ~(K - 1);
-    const bool tree = K >= 16 && g.steps == 1; /* poly_tree_close */
-    const uint32_t tail = g.J ? len - 64 * (g.J - 1) : 0; /* bytes of unit J-1 */
-
-    Fe acc = fe_zero(), r;
-    Mul mr, mjump, mfinal;
-    uint32_t s[4], wn[16], wc[16], x[16];
-    bool seen = false;
-#pragma unroll
-    for (int i = 0; i < 16; ++i) wn[i] = 0;
-    {
-        const int v = k - (int)g.o;
-        unit_prefetch<true>(rv.src, v >= 1, (uint32_t)v - 1, len, wn);
-    }
-    for (uint32_t m = 0; m < g.steps; ++m) {
-        const int v = (int)(m * K + (uint32_t)k) - (int)g.o;
-#pragma unroll
-        for (int i = 0; i < 16; ++i) wc[i] = wn[i];
-        const int vn = v + K;
-        unit_prefetch<true>(rv.src, m + 1 < g.steps && vn >= 1, (uint32_t)vn - 1, len, wn);
-        slot_block(key, pre, v, n_lo, n_hi, x);
-        if (m == 0) {
-            poly_key_bcast(x, gbase + (int)g.o, r, s);
-            mr = mk_mul(r);
-            if (!tree) poly_powers<K>(r, k, g.q, mjump, mfinal);
-            const int k0 = g.J ? (int)((g.o + 1) % K) : K - 1;
-            if (k == k0 && rv.ad_len) poly_ad(acc, mr, rv.ad, rv.ad_len);
-        }
-        if (v >= 1 && (uint32_t)v < g.J) { /* a full unit */
-            poly_unit(acc, seen ? mjump : mr, mr, wc, 4);
-            seen = true;
-            uint32_t w[16];
-#pragma unroll
-            for (int i = 0; i < 16; ++i) w[i] = wc[i] ^ x[i];
-            unit_out_full<true>(rv.dst + 64 * (v - 1), w);
-        }
-    }
-    /* the last unit (block J) is lane K-1's last step */
-    if (k == K - 1 && g.J >= 1) {
-        uint32_t c[16], w[16];
-#pragma unroll
-        for (int i = 0; i < 16; ++i) {
-            c[i] = wc[i];
-            w[i] = wc[i] ^ x[i];
-        }
-        mask_unit(c, tail);
-        poly_unit(acc, seen ? mjump : mr, mr, c, (tail + 15) / 16);
-        tail_out<true, false>(rv.dst, g.J, len, w, nullptr);
-    }
+    const IlRec<K> q = il_rec<K>(rv);
+    IlPoly p;
+    il_pass<K, true, PASS_OPEN1>(rv, q, k, p, nullptr, nullptr);
     uint32_t tag[4], got[4];
-    if (tree) poly_tree_close<K>(acc, k, r, mr, g.J, g.q, rv.ad_len, len, s, tag);
-    else poly_close<K>(acc, k, mr, mfinal, rv.ad_len, len, s, tag);
-    tag_in<true>(rv.src, len, got); /* the tag bytes are never written */
+    il_close<K>(rv, q, k, p, tag);
+    tag_in<true>(rv.src, q.len, got); /* the tag bytes are never written */
     const bool ok = tag_equal(tag, got);
-    if (ok || rv.dst != rv.src) return ok;
-    /* repair in place: plaintext XOR key stream = the ciphertext as given */
-    for (uint32_t m = 0; m < g.steps; ++m) {
-        const int v = (int)(m * K + (uint32_t)k) - (int)g.o;
-        if (v < 1) continue;
-        slot_block(key, pre, v, n_lo, n_hi, x);
-        uint32_t w[16];
-        unit_in<true>(rv.dst, (uint32_t)v - 1, len, w);
-#pragma unroll
-        for (int i = 0; i < 16; ++i) w[i] ^= x[i];
-        if ((uint32_t)v < g.J) unit_out_full<true>(rv.dst + 64 * (v - 1), w);
-        else tail_out<true, false>(rv.dst, g.J, len, w, nullptr);
-    }
-    return false;
+    if (!ok && rv.dst == rv.src) il_repair<K>(rv, q, k);
+    return ok;
 }
 
+/* Verify-first open: AUTH, the verdict (identical on the group), then DEC
+   (the ciphertext re-read is served by L2). */
 template <int K, bool FAST>
 NA_DEV bool open_il(const RecView &rv, int k)
 {
-    uint32_t key[8];
-    load_key(rv.key, key);
-    const uint32_t n_lo = (uint32_t)rv.nonce, n_hi = (uint32_t)(rv.nonce >> 32);
-    ChaPre pre;
-    chacha_pre(key, n_lo, n_hi, pre);
-    const uint32_t len = rv.len;
-    const GroupCtx<K> g = group_ctx<K>(len);
-    const int gbase = (int)(threadIdx.x & 63) & ~(K - 1);
-    const bool tree = K >= 16 && g.steps == 1; /* poly_tree_close */
-
+    const IlRec<K> q = il_rec<K>(rv);
     /* step-0 key stream: block 0 on lane o, data on the others (kept) */
-    const int v0 = k - (int)g.o;
     uint32_t x0[16];
-    chacha20_block_pre(key, pre, (uint32_t)v0, n_lo, n_hi, x0);
-    Fe r;
-    uint32_t s[4];
-    poly_key_bcast(x0, gbase + (int)g.o, r, s);
-    const Mul mr = mk_mul(r);
-    Mul mjump, mfinal;
-    if (!tree) poly_powers<K>(r, k, g.q, mjump, mfinal);
-    Fe acc = fe_zero();
-    const int k0 = g.J ? (int)((g.o + 1) % K) : K - 1;
-    if (k == k0 && rv.ad_len) poly_ad(acc, mr, rv.ad, rv.ad_len);
-
-    /* phase 1: authenticate the ciphertext */
-    uint32_t wn[16], wc[16];
-    bool seen = false;
-#pragma unroll
-    for (int i = 0; i < 16; ++i) wn[i] = 0;
-    unit_prefetch<FAST>(rv.src, v0 >= 1, (uint32_t)v0 - 1, len, wn);
-    for (uint32_t m = 0; m < g.steps; ++m) {
-        const int v = (int)(m * K + (uint32_t)k) - (int)g.o;
-#pragma unroll
-        for (int i = 0; i < 16; ++i) wc[i] = wn[i];
-        const int vn = v + K;
-        unit_prefetch<FAST>(rv.src, m + 1 < g.steps && vn >= 1, (uint32_t)vn - 1, len, wn);
-        if (v >= 1) {
-            const uint32_t j = (uint32_t)v - 1;
-            uint32_t nb = 4;
-            if (j + 1 == g.J) {
-                const uint32_t bytes = len - 64 * j;
-                mask_unit(wc, bytes);
-                nb = (bytes + 15) / 16;
-            }
-            poly_unit(acc, seen ? mjump : mr, mr, wc, nb);
-            seen = true;
-        }
-    }
+    chacha20_block_pre(q.c.key, q.c.pre, (uint32_t)(k - (int)q.g.o), q.c.n_lo, q.c.n_hi, x0);
+    IlPoly p;
+    il_poly_setup<K>(rv, q, k, x0, p);
+    il_auth<K, FAST>(rv, q, k, p);
     uint32_t tag[4], got[4];
-    if (tree) poly_tree_close<K>(acc, k, r, mr, g.J, g.q, rv.ad_len, len, s, tag);
-    else poly_close<K>(acc, k, mr, mfinal, rv.ad_len, len, s, tag);
-    tag_in<FAST>(rv.src, len, got);
-    if (!tag_equal(tag, got)) return false; /* identical verdict on the group */
-
-    /* phase 2: decrypt (the ciphertext re-read is served by L2) */
-#pragma unroll
-    for (int i = 0; i < 16; ++i) wn[i] = 0;
-    unit_prefetch<FAST>(rv.src, v0 >= 1, (uint32_t)v0 - 1, len, wn);
-    uint32_t x[16];
-    for (uint32_t m = 0; m < g.steps; ++m) {
-        const int v = (int)(m * K + (uint32_t)k) - (int)g.o;
-#pragma unroll
-        for (int i = 0; i < 16; ++i) wc[i] = wn[i];
-        const int vn = v + K;
-        unit_prefetch<FAST>(rv.src, m + 1 < g.steps && vn >= 1, (uint32_t)vn - 1, len, wn);
-        if (m == 0) {
-#pragma unroll
-            for (int i = 0; i < 16; ++i) x[i] = x0[i];
-        } else {
-            chacha20_block_pre(key, pre, (uint32_t)v, n_lo, n_hi, x);
-        }
-        if (v >= 1 && (uint32_t)v < g.J) {
-            uint32_t w[16];
-#pragma unroll
-            for (int i = 0; i < 16; ++i) w[i] = wc[i] ^ x[i];
-            unit_out_full<FAST>(rv.dst + 64 * (v - 1), w);
-        }
-    }
-    if (k == K - 1 && g.J >= 1) {
-        uint32_t w[16];
-#pragma unroll
-        for (int i = 0; i < 16; ++i) w[i] = wc[i] ^ x[i];
-        tail_out<FAST, false>(rv.dst, g.J, len, w, nullptr);
-    }
+    il_close<K>(rv, q, k, p, tag);
+    tag_in<FAST>(rv.src, q.len, got);
+    if (!tag_equal(tag, got)) return false;
+    il_pass<K, FAST, PASS_DEC>(rv, q, k, p, x0, nullptr);
     return true;
 }
 
@@ -813,37 +863,6 @@ NA_DEV void wave_store(const UniformArgs &a, const WaveIO<K> &io, int j0, int la
     }
 }
 
-/* FAST exact-size store of a record's last unit: nb (1..64) bytes at p
-   (16-B aligned). */
-NA_DEV void last_unit_out(uint8_t *p, uint32_t nb, const uint32_t w[16])
-{
-#pragma unroll
-    for (uint32_t c = 0; c < 4; ++c)
-        if (16 * c + 16 <= nb)
-            *(uint4 *)(p + 16 * c) = make_uint4(w[4 * c], w[4 * c + 1], w[4 * c + 2], w[4 * c + 3]);
-    const uint32_t rem = nb & 15;
-    if (rem) {
-        uint32_t part[4];
-        pick_chunk(w, nb >> 4, part);
-        uint8_t *q = p + (nb & ~15u);
-        if (rem == 8) *(uint2 *)q = make_uint2(part[0], part[1]);
-        else store16(q, rem, part);
-    }
-}
-
-/* FAST tag store at p = record + len (p is 16-B aligned iff len % 16 == 0). */
-NA_DEV void tag_out(uint8_t *p, uint32_t len, const uint32_t t[4])
-{
-    if ((len & 15) == 0) {
-        *(uint4 *)p = make_uint4(t[0], t[1], t[2], t[3]);
-    } else if ((len & 7) == 0) {
-        *(uint2 *)p = make_uint2(t[0], t[1]);
-        *(uint2 *)(p + 8) = make_uint2(t[2], t[3]);
-    } else {
-        store16(p, 16, t);
-    }
-}
-
 /* Per-lane scratch the staged seal kernel parks outside its loop: lane k's
    final Poly1305 scale (an Fe), written at step 0 and read after the loop so
    it is not held in 5 VGPRs across the ChaCha blocks. */
@@ -889,80 +908,176 @@ NA_DEV void u_key_nonce(const UniformArgs &a, uint32_t rec0, uint32_t rc, uint32
     n_hi = (uint32_t)(n >> 32);
 }
 
-/* wave_job: the wave's 64/K consecutive records start at wave_job * (64/K) */
-template <int K, bool UKEY>
-NA_DEV void seal_il_staged(const UniformArgs &a, uint4 *tiles, FinSlot *fin, uint32_t wave_job)
-{
-    const uint32_t lane = threadIdx.x & 63;
-    const uint32_t rec0 = wave_job * (64 / K);
-    const uint32_t rec_raw = rec0 + lane / K;
-    const bool live = rec_raw < a.n_records;
-    const uint32_t rc = live ? rec_raw : a.n_records - 1;
-    const int k = (int)(lane % K);
-    uint32_t key[8], n_lo, n_hi;
-    u_key_nonce<UKEY>(a, rec0, rc, key, n_lo, n_hi);
-    ChaPre pre;
-    chacha_pre(key, n_lo, n_hi, pre);
-    const uint32_t len = a.len;
-    const GroupCtx<K> g = group_ctx<K>(len); /* wave-uniform (uniform batch) */
-    const int gbase = (int)lane & ~(K - 1);
-    const WaveIO<K> io = wave_io<K>(rec0, lane);
-    const int last_full = (int)g.J - 2; /* unit J-1 is stored by its owner */
+/* Per-lane view of a wave's 64/K records in the staged kernels.  wave_job:
+   the wave's 64/K consecutive records start at wave_job * (64/K); lanes past
+   the batch end are clamped onto the last record (rc) and store nothing. */
+template <int K>
+struct StagedRec {
+    uint32_t lane, rec0, rec_raw, rc, len, tail; /* tail: bytes of unit J-1 */
+    int k, gbase, last_full;                     /* unit J-1 is stored by its owner */
+    bool live;
+    RecKey c;
+    GroupCtx<K> g; /* wave-uniform (uniform batch) */
+    WaveIO<K> io;
+};
 
-    Fe acc = fe_zero();
-    Mul mr, mjump;
-    uint32_t s[4];
-    bool seen = false;
-    wave_dma_asm<K>(a, io, -(int)g.o - 1, tiles);
+template <int K, bool UKEY>
+NA_DEV StagedRec<K> staged_rec(const UniformArgs &a, uint32_t wave_job)
+{
+    StagedRec<K> q;
+    q.lane = threadIdx.x & 63;
+    q.rec0 = wave_job * (64 / K);
+    q.rec_raw = q.rec0 + q.lane / K;
+    q.live = q.rec_raw < a.n_records;
+    q.rc = q.live ? q.rec_raw : a.n_records - 1;
+    q.k = (int)(q.lane % K);
+    q.len = a.len;
+    q.g = group_ctx<K>(q.len);
+    q.gbase = (int)q.lane & ~(K - 1);
+    q.io = wave_io<K>(q.rec0, q.lane);
+    /* the key after the lane geometry: hipcc's register allocation of the
+       128-VGPR kernels follows this order (key first: seal_staged<4,false>
+       126 VGPRs / 36 B scratch -> 127 / 44) */
+    u_key_nonce<UKEY>(a, q.rec0, q.rc, q.c.key, q.c.n_lo, q.c.n_hi);
+    chacha_pre(q.c.key, q.c.n_lo, q.c.n_hi, q.c.pre);
+    q.last_full = (int)q.g.J - 2;
+    q.tail = q.g.J ? q.len - 64 * (q.g.J - 1) : 0;
+    return q;
+}
+
+/* Step 0: r and s from the key block (x of lane o), the powers — the final
+   scale parked in fin — and the AD on the lane with unit 0. */
+template <int K>
+NA_DEV void staged_poly_setup(const UniformArgs &a, const StagedRec<K> &q, const uint32_t x[16],
+                              FinSlot *fin, IlPoly &p)
+{
+    Fe r;
+    poly_key_bcast(x, q.gbase + (int)q.g.o, r, p.s);
+    p.mr = mk_mul(r);
+    Mul mfinal;
+    poly_powers<K>(r, q.k, q.g.q, p.mjump, mfinal);
+    fin_put(fin, q.lane, mfinal);
+    const int k0 = q.g.J ? (int)((q.g.o + 1) % K) : K - 1;
+    if (q.k == k0 && a.ad_len) poly_ad(p.acc, p.mr, u_ad(a, q.rc), a.ad_len);
+}
+
+/* Poly1305 over the unit of slot v (w: the CT; the last unit is masked).
+   OUT (the seal): the last unit leaves exactly here, before the mask. */
+template <int K, bool OUT>
+NA_DEV void staged_poly_unit(const UniformArgs &a, const StagedRec<K> &q, int v, uint32_t w[16], IlPoly &p)
+{
+    if (v >= 1 && (uint32_t)v <= q.g.J) {
+        /* one Poly path for full units and the last (lane K-1's last step),
+           so a wave never runs both */
+        uint32_t nb = 4;
+        if ((uint32_t)v == q.g.J) { /* bytes past len are never stored */
+            if (OUT && q.live) last_unit_out(u_dst(a, q.rc) + 64 * (q.g.J - 1), q.tail, w);
+            mask_unit(w, q.tail);
+            nb = (q.tail + 15) / 16;
+        }
+        il_poly_unit(p, w, nb);
+    }
+}
+
+/* The one pass over a wave's records, double-buffered: the next step's bytes
+   go into the other tile by DMA while this one computes, and each step's
+   full units leave coalesced from its own tile.  The step-0 Poly1305 setup
+   runs on the first block.  (open_il_staged_vf keeps its own loops.) */
+template <int K, int MODE>
+NA_DEV void staged_pass(const UniformArgs &a, const StagedRec<K> &q, uint4 *tiles, FinSlot *fin, IlPoly &p)
+{
+    const GroupCtx<K> &g = q.g;
+    wave_dma_asm<K>(a, q.io, -(int)g.o - 1, tiles);
     for (uint32_t m = 0; m < g.steps; ++m) {
         if (a.balance) prio_by_progress(m, g.steps);
         const int j0 = (int)(m * K) - (int)g.o - 1;
-        const int v = j0 + 1 + k;
+        const int v = j0 + 1 + q.k;
         uint4 *cur = tiles + 256 * (m & 1), *nxt = tiles + 256 * ((m + 1) & 1);
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); /* last step's reads and writes of nxt are done */
         __builtin_amdgcn_wave_barrier();
         /* next step's bytes go into the other tile while this one computes */
-        if (m + 1 < g.steps) wave_dma_asm<K>(a, io, j0 + K, nxt);
+        if (m + 1 < g.steps) wave_dma_asm<K>(a, q.io, j0 + K, nxt);
         uint32_t x[16];
-        slot_block<true>(key, pre, v, n_lo, n_hi, x, a.balance && 2 * m < g.steps);
-        if (m == 0) {
-            Fe r;
-            poly_key_bcast(x, gbase + (int)g.o, r, s);
-            mr = mk_mul(r);
-            Mul mfinal;
-            poly_powers<K>(r, k, g.q, mjump, mfinal);
-            fin_put(fin, lane, mfinal);
-            const int k0 = g.J ? (int)((g.o + 1) % K) : K - 1;
-            if (k == k0 && a.ad_len) poly_ad(acc, mr, u_ad(a, rc), a.ad_len);
-        }
+        slot_block<true>(q.c.key, q.c.pre, v, q.c.n_lo, q.c.n_hi, x, a.balance && 2 * m < g.steps);
+        if (m == 0) staged_poly_setup<K>(a, q, x, fin, p);
         __builtin_amdgcn_wave_barrier();
         /* this step's DMA (a step old) landed; the next step's may still fly */
         if (m + 1 < g.steps) asm volatile("s_waitcnt vmcnt(4)" ::: "memory");
         else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         uint32_t w[16];
-        tile_get_unit(cur, lane, w);
+        tile_get_unit(cur, q.lane, w);
+        if constexpr (MODE == PASS_SEAL) {
 #pragma unroll
-        for (int i = 0; i < 16; ++i) w[i] ^= x[i];
-        if (v >= 1 && (uint32_t)v <= g.J) {
-            /* one Poly path for full units and the last (lane K-1's last
-               step), so a wave never runs both */
-            uint32_t nb = 4;
-            if ((uint32_t)v == g.J) {
-                const uint32_t bytes = len - 64 * (g.J - 1);
-                if (live) last_unit_out(u_dst(a, rc) + 64 * (g.J - 1), bytes, w);
-                mask_unit(w, bytes);
-                nb = (bytes + 15) / 16;
-            }
-            poly_unit(acc, seen ? mjump : mr, mr, w, nb);
-            seen = true;
+            for (int i = 0; i < 16; ++i) w[i] ^= x[i];
+            staged_poly_unit<K, true>(a, q, v, w, p);
+        } else {
+            staged_poly_unit<K, false>(a, q, v, w, p);
+#pragma unroll
+            for (int i = 0; i < 16; ++i) w[i] ^= x[i];
+            if (v >= 1 && (uint32_t)v == g.J && q.live) last_unit_out(u_dst(a, q.rc) + 64 * (g.J - 1), q.tail, w);
         }
-        tile_put_unit(cur, lane, w);
+        tile_put_unit(cur, q.lane, w);
         __builtin_amdgcn_wave_barrier();
-        wave_store<K>(a, io, j0, last_full, cur, lane, 0xfu);
+        wave_store<K>(a, q.io, j0, q.last_full, cur, q.lane, 0xfu);
     }
+}
+
+/* The tag against the record's: the verdict, identical on the group's lanes,
+   and the status byte. */
+template <int K>
+NA_DEV bool staged_verdict(const UniformArgs &a, const StagedRec<K> &q, const FinSlot *fin, const IlPoly &p)
+{
+    uint32_t tag[4], got[4];
+    poly_close<K>(p.acc, q.k, p.mr, fin_get(fin, q.lane), a.ad_len, q.len, p.s, tag);
+    tag_in<true>(u_src(a, q.rc), q.len, got); /* the tag bytes are never written */
+    const bool ok = tag_equal(tag, got);
+    if (q.k == K - 1 && q.live && a.status) a.status[q.rec_raw] = ok ? 0 : 1;
+    return ok;
+}
+
+/* A one-pass open's repair of the wave's rejected records (taken only on MAC
+   failure), over the same coalesced stores gated by badm: in place the
+   plaintext is XORed with the key stream again, out of place zeroed. */
+template <int K>
+NA_DEV void staged_repair(const UniformArgs &a, const StagedRec<K> &q, uint4 *tiles, bool bad, uint32_t badm)
+{
+    const bool inplace = a.in == a.out && a.in_stride == a.out_stride;
+    __threadfence(); /* this wave's plaintext stores, visible to its reads below */
+    for (uint32_t m = 0; m < q.g.steps; ++m) {
+        const int j0 = (int)(m * K) - (int)q.g.o - 1;
+        const int v = j0 + 1 + q.k;
+        uint32_t w[16];
+        __builtin_amdgcn_wave_barrier();
+        if (inplace) {
+            wave_dma<K>(a, q.io, j0, tiles);
+            uint32_t x[16];
+            chacha20_block_pre(q.c.key, q.c.pre, (uint32_t)v, q.c.n_lo, q.c.n_hi, x);
+            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+            __builtin_amdgcn_wave_barrier();
+            tile_get_unit(tiles, q.lane, w);
+#pragma unroll
+            for (int i = 0; i < 16; ++i) w[i] ^= x[i];
+        } else {
+#pragma unroll
+            for (int i = 0; i < 16; ++i) w[i] = 0;
+        }
+        if (v >= 1 && (uint32_t)v == q.g.J && bad) last_unit_out(u_dst(a, q.rc) + 64 * (q.g.J - 1), q.tail, w);
+        __builtin_amdgcn_wave_barrier();
+        tile_put_unit(tiles, q.lane, w);
+        __builtin_amdgcn_wave_barrier();
+        wave_store<K>(a, q.io, j0, q.last_full, tiles, q.lane, badm);
+    }
+}
+
+template <int K, bool UKEY>
+NA_DEV void seal_il_staged(const UniformArgs &a, uint4 *tiles, FinSlot *fin, uint32_t wave_job)
+{
+    const StagedRec<K> q = staged_rec<K, UKEY>(a, wave_job);
+    IlPoly p;
+    staged_pass<K, PASS_SEAL>(a, q, tiles, fin, p);
     uint32_t tag[4];
-    poly_close<K>(acc, k, mr, fin_get(fin, lane), a.ad_len, len, s, tag);
-    if (k == K - 1 && live) tag_out(u_dst(a, rc) + len, len, tag);
+    poly_close<K>(p.acc, q.k, p.mr, fin_get(fin, q.lane), a.ad_len, q.len, p.s, tag);
+    if (q.k == K - 1 && q.live) tag_out(u_dst(a, q.rc) + q.len, q.len, tag);
 }
 
 /* Open, single pass (the structure of seal_il_staged): each step's
@@ -977,109 +1092,12 @@ NA_DEV void seal_il_staged(const UniformArgs &a, uint4 *tiles, FinSlot *fin, uin
 template <int K, bool UKEY>
 NA_DEV void open_il_staged(const UniformArgs &a, uint4 *tiles, FinSlot *fin, uint32_t wave_job)
 {
-    const uint32_t lane = threadIdx.x & 63;
-    const uint32_t rec0 = wave_job * (64 / K);
-    const uint32_t rec_raw = rec0 + lane / K;
-    const bool live = rec_raw < a.n_records;
-    const uint32_t rc = live ? rec_raw : a.n_records - 1;
-    const int k = (int)(lane % K);
-    uint32_t key[8], n_lo, n_hi;
-    u_key_nonce<UKEY>(a, rec0, rc, key, n_lo, n_hi);
-    ChaPre pre;
-    chacha_pre(key, n_lo, n_hi, pre);
-    const uint32_t len = a.len;
-    const GroupCtx<K> g = group_ctx<K>(len);
-    const int gbase = (int)lane & ~(K - 1);
-    const WaveIO<K> io = wave_io<K>(rec0, lane);
-    const int last_full = (int)g.J - 2;
-    const uint32_t tail = g.J ? len - 64 * (g.J - 1) : 0; /* bytes of unit J-1 */
-
-    Fe acc = fe_zero();
-    Mul mr, mjump;
-    uint32_t s[4];
-    bool seen = false;
-    wave_dma_asm<K>(a, io, -(int)g.o - 1, tiles);
-    for (uint32_t m = 0; m < g.steps; ++m) {
-        if (a.balance) prio_by_progress(m, g.steps);
-        const int j0 = (int)(m * K) - (int)g.o - 1;
-        const int v = j0 + 1 + k;
-        uint4 *cur = tiles + 256 * (m & 1), *nxt = tiles + 256 * ((m + 1) & 1);
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); /* last step's reads and writes of nxt are done */
-        __builtin_amdgcn_wave_barrier();
-        if (m + 1 < g.steps) wave_dma_asm<K>(a, io, j0 + K, nxt);
-        uint32_t x[16];
-        slot_block<true>(key, pre, v, n_lo, n_hi, x, a.balance && 2 * m < g.steps);
-        if (m == 0) {
-            Fe r;
-            poly_key_bcast(x, gbase + (int)g.o, r, s);
-            mr = mk_mul(r);
-            Mul mfinal;
-            poly_powers<K>(r, k, g.q, mjump, mfinal);
-            fin_put(fin, lane, mfinal);
-            const int k0 = g.J ? (int)((g.o + 1) % K) : K - 1;
-            if (k == k0 && a.ad_len) poly_ad(acc, mr, u_ad(a, rc), a.ad_len);
-        }
-        __builtin_amdgcn_wave_barrier();
-        /* this step's DMA (a step old) landed; the next step's may still fly */
-        if (m + 1 < g.steps) asm volatile("s_waitcnt vmcnt(4)" ::: "memory");
-        else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        uint32_t w[16];
-        tile_get_unit(cur, lane, w);
-        if (v >= 1 && (uint32_t)v <= g.J) {
-            uint32_t nb = 4;
-            if ((uint32_t)v == g.J) { /* bytes past len are never stored */
-                mask_unit(w, tail);
-                nb = (tail + 15) / 16;
-            }
-            poly_unit(acc, seen ? mjump : mr, mr, w, nb);
-            seen = true;
-        }
-#pragma unroll
-        for (int i = 0; i < 16; ++i) w[i] ^= x[i];
-        if (v >= 1 && (uint32_t)v == g.J && live) last_unit_out(u_dst(a, rc) + 64 * (g.J - 1), tail, w);
-        tile_put_unit(cur, lane, w);
-        __builtin_amdgcn_wave_barrier();
-        wave_store<K>(a, io, j0, last_full, cur, lane, 0xfu);
-    }
-    uint32_t tag[4], got[4];
-    poly_close<K>(acc, k, mr, fin_get(fin, lane), a.ad_len, len, s, tag);
-    tag_in<true>(u_src(a, rc), len, got); /* the tag bytes are never written */
-    const bool ok = tag_equal(tag, got);
-    if (k == K - 1 && live && a.status) a.status[rec_raw] = ok ? 0 : 1;
-    const bool bad = live && !ok;
+    const StagedRec<K> q = staged_rec<K, UKEY>(a, wave_job);
+    IlPoly p;
+    staged_pass<K, PASS_OPEN1>(a, q, tiles, fin, p);
+    const bool bad = q.live && !staged_verdict<K>(a, q, fin, p);
     if (__ballot(bad) == 0) return; /* wave-uniform: the common case */
-
-    /* repair pass: bit i of badm = the owner coalesced instruction i serves */
-    uint32_t badm = 0;
-#pragma unroll
-    for (int i = 0; i < 4; ++i)
-        badm |= (__shfl((int)bad, (int)(16u * i + (lane >> 2)), 64) != 0 ? 1u : 0u) << i;
-    const bool inplace = a.in == a.out && a.in_stride == a.out_stride;
-    __threadfence(); /* this wave's plaintext stores, visible to its reads below */
-    for (uint32_t m = 0; m < g.steps; ++m) {
-        const int j0 = (int)(m * K) - (int)g.o - 1;
-        const int v = j0 + 1 + k;
-        uint32_t w[16];
-        __builtin_amdgcn_wave_barrier();
-        if (inplace) {
-            wave_dma<K>(a, io, j0, tiles);
-            uint32_t x[16];
-            chacha20_block_pre(key, pre, (uint32_t)v, n_lo, n_hi, x);
-            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-            __builtin_amdgcn_wave_barrier();
-            tile_get_unit(tiles, lane, w);
-#pragma unroll
-            for (int i = 0; i < 16; ++i) w[i] ^= x[i];
-        } else {
-#pragma unroll
-            for (int i = 0; i < 16; ++i) w[i] = 0;
-        }
-        if (v >= 1 && (uint32_t)v == g.J && bad) last_unit_out(u_dst(a, rc) + 64 * (g.J - 1), tail, w);
-        __builtin_amdgcn_wave_barrier();
-        tile_put_unit(tiles, lane, w);
-        __builtin_amdgcn_wave_barrier();
-        wave_store<K>(a, io, j0, last_full, tiles, lane, badm);
-    }
+    staged_repair<K>(a, q, tiles, bad, owner_mask<4>(bad, q.lane));
 }
 
 /* ---------------- one lane per record, LDS-staged (uniform FAST batches)
@@ -1266,10 +1284,9 @@ NA_DEV void solo_blocks2(const uint32_t key[8], const ChaPre &pre, uint32_t c0, 
     }
 }
 
-/* solo_pass modes: SEAL and OPEN1 (the opt-in one-pass open,
+/* solo_pass modes: PASS_SEAL and PASS_OPEN1 (the opt-in one-pass open,
    NOISE_AEAD_FLAG_ONE_PASS) as above; the verify-first open (the default)
    runs solo_auth and then solo_dec_rev (below). */
-enum SoloMode { SOLO_SEAL, SOLO_OPEN1 };
 
 template <int MODE, bool RUNS>
 NA_DEV void solo_pass(const UniformArgs &a, const SoloRec &q, uint4 *tiles, const uint32_t key[8],
@@ -1305,7 +1322,7 @@ NA_DEV void solo_pass(const UniformArgs &a, const SoloRec &q, uint4 *tiles, cons
                     chacha20_block_pre(key, pre, j + 1, n_lo, n_hi, x);
                 }
                 uint32_t nb = 4;
-                if constexpr (MODE == SOLO_OPEN1) {
+                if constexpr (MODE == PASS_OPEN1) {
 #pragma unroll
                     for (int i = 0; i < 16; ++i) w[i] = wu[u][i];
                     if (j == q.J - 1) { /* bytes past len are never stored */
@@ -1349,7 +1366,7 @@ NA_DEV void seal_solo_staged(const UniformArgs &a, uint4 *tiles, uint32_t wave_j
     uint32_t s[4];
     P32 h;
     solo_poly_key(key, pre, n_lo, n_hi, a.ad_len ? u_ad(a, q.rc) : nullptr, a.ad_len, r, s, h);
-    solo_pass<SOLO_SEAL, RUNS>(a, q, tiles, key, pre, n_lo, n_hi, r, h);
+    solo_pass<PASS_SEAL, RUNS>(a, q, tiles, key, pre, n_lo, n_hi, r, h);
     uint32_t tag[4];
     solo_tag(h, r, a.ad_len, q.len, s, tag);
     if (q.live) tag_out(u_dst(a, q.rc) + q.len, q.len, tag);
@@ -1402,7 +1419,7 @@ NA_DEV void solo_auth(const UniformArgs &a, const SoloRec &q, uint4 *tiles, cons
    the key stream into this tile.  Round 5 measured it against the forward
    order: C2 verify-first 1396-1431 -> 1460-1468 GiB/s, three interleaved
    rounds (profiles/r05/dec_rev_ab.txt; the forward pass is NA_DEC_REV=0 at
-   the ab-arms-r5 revision, tools/ab/README.md); the last steps read by the
+   revision 9d9091d, tools/ab/README.md); the last steps read by the
    AUTH pass are also the likeliest still in L2. */
 template <bool RUNS>
 NA_DEV void solo_dec_rev(const UniformArgs &a, const SoloRec &q, uint4 *tiles, const uint32_t key[8],
@@ -1445,6 +1462,42 @@ NA_DEV void solo_dec_rev(const UniformArgs &a, const SoloRec &q, uint4 *tiles, c
     }
 }
 
+/* A one-pass open's repair of the wave's rejected records, exactly as
+   staged_repair: over the same coalesced stores, gated by badm. */
+NA_DEV void solo_repair(const UniformArgs &a, const SoloRec &q, uint4 *tiles, const uint32_t key[8],
+                        const ChaPre &pre, uint32_t n_lo, uint32_t n_hi, bool bad, uint32_t badm)
+{
+    const bool inplace = a.in == a.out && a.in_stride == a.out_stride;
+    __threadfence(); /* this wave's plaintext stores, visible to its reads below */
+    for (uint32_t m = 0; m < q.S; ++m) {
+        __builtin_amdgcn_wave_barrier();
+        if (inplace) solo_dma(a, q.rec0, q.lane, m, q.lim, tiles);
+#pragma unroll
+        for (uint32_t u = 0; u < 2; ++u) {
+            const uint32_t j = 2 * m + u;
+            if (j < q.J) {
+                uint32_t w[16];
+                if (inplace) {
+                    uint32_t x[16];
+                    chacha20_block_pre(key, pre, j + 1, n_lo, n_hi, x);
+                    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+                    __builtin_amdgcn_wave_barrier();
+                    solo_get(tiles, q.lane, u, w);
+#pragma unroll
+                    for (int i = 0; i < 16; ++i) w[i] ^= x[i];
+                } else {
+#pragma unroll
+                    for (int i = 0; i < 16; ++i) w[i] = 0;
+                }
+                if (j == q.J - 1 && bad) last_unit_out(u_dst(a, q.rc) + q.full_lim, q.tail, w);
+                __builtin_amdgcn_wave_barrier();
+                solo_put(tiles, q.lane, u, w);
+            }
+        }
+        __builtin_amdgcn_wave_barrier();
+        solo_store(a, q.rec0, q.lane, m, q.full_lim, tiles, badm);
+    }
+}
 
 /* Open.  Verify-first (a.vf: the default, the reference's order,
    cipher-chachapoly.c:135-141): an AUTH pass over the wave's records, the
@@ -1459,77 +1512,36 @@ template <bool UKEY, bool RUNS>
 NA_DEV void open_solo_staged(const UniformArgs &a, uint4 *tiles, uint32_t wave_job)
 {
     const SoloRec q = solo_rec(a, wave_job);
-    const uint32_t lane = q.lane, rec0 = q.rec0, rec_raw = q.rec_raw, rc = q.rc, len = q.len;
-    const uint32_t J = q.J, S = q.S, lim = q.lim, full_lim = q.full_lim, tail = q.tail;
-    const bool live = q.live;
     uint32_t key[8], n_lo, n_hi;
-    u_key_nonce<UKEY>(a, rec0, rc, key, n_lo, n_hi);
+    u_key_nonce<UKEY>(a, q.rec0, q.rc, key, n_lo, n_hi);
     ChaPre pre;
     chacha_pre(key, n_lo, n_hi, pre);
-    if (S) solo_dma(a, rec0, lane, 0, lim, tiles);
+    if (q.S) solo_dma(a, q.rec0, q.lane, 0, q.lim, tiles);
     R32 r;
     uint32_t s[4];
     P32 h;
-    solo_poly_key(key, pre, n_lo, n_hi, a.ad_len ? u_ad(a, rc) : nullptr, a.ad_len, r, s, h);
+    solo_poly_key(key, pre, n_lo, n_hi, a.ad_len ? u_ad(a, q.rc) : nullptr, a.ad_len, r, s, h);
     if (a.vf) solo_auth(a, q, tiles, r, h);
-    else solo_pass<SOLO_OPEN1, RUNS>(a, q, tiles, key, pre, n_lo, n_hi, r, h);
+    else solo_pass<PASS_OPEN1, RUNS>(a, q, tiles, key, pre, n_lo, n_hi, r, h);
     uint32_t tag[4], got[4];
-    solo_tag(h, r, a.ad_len, len, s, tag);
-    tag_in<true>(u_src(a, rc), len, got); /* the tag bytes are never written */
+    solo_tag(h, r, a.ad_len, q.len, s, tag);
+    tag_in<true>(u_src(a, q.rc), q.len, got); /* the tag bytes are never written */
     const bool ok = tag_equal(tag, got);
-    if (live && a.status) a.status[rec_raw] = ok ? 0 : 1;
+    if (q.live && a.status) a.status[q.rec_raw] = ok ? 0 : 1;
 #ifndef NA_SOLO_AUTH_HOOK
 #define NA_SOLO_AUTH_HOOK() /* tools/microbench/timeline_solo.hip stamps the AUTH pass's end here */
 #endif
     NA_SOLO_AUTH_HOOK();
     if (a.vf) {
-        if (__ballot(live && ok) == 0) return;
-        uint32_t okm = 0; /* bit i: the owner coalesced instruction i serves verified */
-#pragma unroll
-        for (int i = 0; i < 8; ++i)
-            okm |= (__shfl((int)ok, (int)(8u * i + (lane >> 3)), 64) != 0 ? 1u : 0u) << i;
+        if (__ballot(q.live && ok) == 0) return;
+        const uint32_t okm = owner_mask<8>(ok, q.lane);
         __builtin_amdgcn_wave_barrier(); /* the AUTH pass's tile reads are done */
         solo_dec_rev<RUNS>(a, q, tiles, key, pre, n_lo, n_hi, okm, ok);
         return;
     }
-    const bool bad = live && !ok;
+    const bool bad = q.live && !ok;
     if (__ballot(bad) == 0) return; /* wave-uniform: the common case */
-
-    /* repair pass: bit i of badm = the owner coalesced instruction i serves */
-    uint32_t badm = 0;
-#pragma unroll
-    for (int i = 0; i < 8; ++i)
-        badm |= (__shfl((int)bad, (int)(8u * i + (lane >> 3)), 64) != 0 ? 1u : 0u) << i;
-    const bool inplace = a.in == a.out && a.in_stride == a.out_stride;
-    __threadfence(); /* this wave's plaintext stores, visible to its reads below */
-    for (uint32_t m = 0; m < S; ++m) {
-        __builtin_amdgcn_wave_barrier();
-        if (inplace) solo_dma(a, rec0, lane, m, lim, tiles);
-#pragma unroll
-        for (uint32_t u = 0; u < 2; ++u) {
-            const uint32_t j = 2 * m + u;
-            if (j < J) {
-                uint32_t w[16];
-                if (inplace) {
-                    uint32_t x[16];
-                    chacha20_block_pre(key, pre, j + 1, n_lo, n_hi, x);
-                    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-                    __builtin_amdgcn_wave_barrier();
-                    solo_get(tiles, lane, u, w);
-#pragma unroll
-                    for (int i = 0; i < 16; ++i) w[i] ^= x[i];
-                } else {
-#pragma unroll
-                    for (int i = 0; i < 16; ++i) w[i] = 0;
-                }
-                if (j == J - 1 && bad) last_unit_out(u_dst(a, rc) + full_lim, tail, w);
-                __builtin_amdgcn_wave_barrier();
-                solo_put(tiles, lane, u, w);
-            }
-        }
-        __builtin_amdgcn_wave_barrier();
-        solo_store(a, rec0, lane, m, full_lim, tiles, badm);
-    }
+    solo_repair(a, q, tiles, key, pre, n_lo, n_hi, bad, owner_mask<8>(bad, q.lane));
 }
 
 /* ------------------------------------------------- contiguous (K = 1, 2) */
@@ -1596,17 +1608,27 @@ NA_DEV void key_words_bcast(const uint32_t x[16], int gbase, uint32_t kw[8])
     for (int i = 0; i < 8; ++i) kw[i] = G == 1 ? x[i] : (uint32_t)__shfl((int)x[i], gbase, 64);
 }
 
+/* r (radix 2^32 for the chains, 2^26 for ct_close's scale) and s from the
+   key block x of the group's lane 0; lane 0 absorbs the AD. */
+template <int G>
+NA_DEV void ct_poly_key(const RecView &rv, int k, const uint32_t x[16], R32 &r, Fe &r26, uint32_t s[4],
+                        P32 &acc)
+{
+    const int gbase = (int)(threadIdx.x & 63) & ~(G - 1);
+    uint32_t kw[8];
+    key_words_bcast<G>(x, gbase, kw);
+    r = r32_from_key(kw[0], kw[1], kw[2], kw[3]);
+    r26 = fe_clamp_r(kw[0], kw[1], kw[2], kw[3]);
+    s[0] = kw[4]; s[1] = kw[5]; s[2] = kw[6]; s[3] = kw[7];
+    if (k == 0 && rv.ad_len) p32_ad(acc, r, rv.ad, rv.ad_len);
+}
+
 template <int G, bool FAST>
 NA_DEV void seal_ct(const RecView &rv, int k)
 {
-    uint32_t key[8];
-    load_key(rv.key, key);
-    const uint32_t n_lo = (uint32_t)rv.nonce, n_hi = (uint32_t)(rv.nonce >> 32);
-    ChaPre pre;
-    chacha_pre(key, n_lo, n_hi, pre);
+    const RecKey c = rec_key(rv);
     const uint32_t len = rv.len;
     const CtPlan p = ct_plan<G>(len, k);
-    const int gbase = (int)(threadIdx.x & 63) & ~(G - 1);
 
     uint32_t wn[16], wc[16], x[16], wt[16];
 #pragma unroll
@@ -1621,15 +1643,8 @@ NA_DEV void seal_ct(const RecView &rv, int k)
 #pragma unroll
         for (int i = 0; i < 16; ++i) wc[i] = wn[i];
         unit_prefetch<FAST>(rv.src, v + 1 < p.v1, v, len, wn); /* unit of block v+1 */
-        chacha20_block_pre(key, pre, v, n_lo, n_hi, x);
-        if (m == 0) {
-            uint32_t kw[8];
-            key_words_bcast<G>(x, gbase, kw);
-            r = r32_from_key(kw[0], kw[1], kw[2], kw[3]);
-            r26 = fe_clamp_r(kw[0], kw[1], kw[2], kw[3]);
-            s[0] = kw[4]; s[1] = kw[5]; s[2] = kw[6]; s[3] = kw[7];
-            if (k == 0 && rv.ad_len) p32_ad(acc, r, rv.ad, rv.ad_len);
-        }
+        chacha20_block_pre(c.key, c.pre, v, c.n_lo, c.n_hi, x);
+        if (m == 0) ct_poly_key<G>(rv, k, x, r, r26, s, acc);
         if (v >= 1 && v < p.v1) {
             uint32_t w[16];
 #pragma unroll
@@ -1654,24 +1669,17 @@ NA_DEV void seal_ct(const RecView &rv, int k)
 template <int G, bool FAST>
 NA_DEV bool open_ct(const RecView &rv, int k)
 {
-    uint32_t key[8];
-    load_key(rv.key, key);
-    const uint32_t n_lo = (uint32_t)rv.nonce, n_hi = (uint32_t)(rv.nonce >> 32);
-    ChaPre pre;
-    chacha_pre(key, n_lo, n_hi, pre);
+    const RecKey c = rec_key(rv);
     const uint32_t len = rv.len;
     const CtPlan p = ct_plan<G>(len, k);
-    const int gbase = (int)(threadIdx.x & 63) & ~(G - 1);
 
     uint32_t x0[16];
-    chacha20_block_pre(key, pre, p.v0, n_lo, n_hi, x0);
-    uint32_t kw[8];
-    key_words_bcast<G>(x0, gbase, kw);
-    const R32 r = r32_from_key(kw[0], kw[1], kw[2], kw[3]);
-    const Fe r26 = fe_clamp_r(kw[0], kw[1], kw[2], kw[3]);
-    const uint32_t s[4] = {kw[4], kw[5], kw[6], kw[7]};
+    chacha20_block_pre(c.key, c.pre, p.v0, c.n_lo, c.n_hi, x0);
     P32 acc = p32_zero();
-    if (k == 0 && rv.ad_len) p32_ad(acc, r, rv.ad, rv.ad_len);
+    R32 r;
+    Fe r26;
+    uint32_t s[4];
+    ct_poly_key<G>(rv, k, x0, r, r26, s, acc);
 
     /* phase 1: authenticate (one unit ahead) */
     const uint32_t u0 = p.v0 >= 1 ? p.v0 : 1u; /* first block with data */
@@ -1707,7 +1715,7 @@ NA_DEV bool open_ct(const RecView &rv, int k)
 #pragma unroll
             for (int i = 0; i < 16; ++i) x[i] = x0[i];
         } else {
-            chacha20_block_pre(key, pre, v, n_lo, n_hi, x);
+            chacha20_block_pre(c.key, c.pre, v, c.n_lo, c.n_hi, x);
         }
         uint32_t w[16];
 #pragma unroll
@@ -1780,7 +1788,13 @@ NA_DEV uint32_t wave_of(uint32_t b) { return (b * 256u + threadIdx.x) >> 6; }
      DEC:  verified waves only — the one-pass loop's key stream and XOR, the
            stores gated per owner by the verdicts (okm), step 0's key stream
            kept from the AUTH pass (its blocks gave r and s).
-   A rejected record's output is never written. */
+   A rejected record's output is never written.
+   Not composed from StagedRec / staged_pass, and with its own owner-mask
+   loop: as staged_auth + staged_pass<DEC> (or with owner_mask<4> alone)
+   hipcc allocated its registers anew, and the `--mode separate` step's
+   opens then measured 1386-1462 GiB/s against 1456-1493 before the merge, in
+   four interleaved rounds; with this body 1384-1420 against 1391-1409
+   (profiles/refactor_passes/ab.jsonl, sets separate and separate2). */
 template <int K, bool UKEY>
 NA_DEV void open_il_staged_vf(const UniformArgs &a, uint4 *tiles, FinSlot *fin, uint32_t wave_job)
 {

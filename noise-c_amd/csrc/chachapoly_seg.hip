@@ -384,8 +384,6 @@ NA_DEV uint32_t wave_max(uint32_t v)
     return v;
 }
 
-enum SegMode { SEG_SEAL, SEG_OPEN1, SEG_DEC };
-
 /* The key block's r (first four words) from the record's leader, as R32, and
    the Fe r the combine uses */
 NA_DEV void seg_bcast_r(const SegLane &q, uint32_t lane, const uint32_t kw[4], R32 &r, uint32_t rw[4])
@@ -408,7 +406,7 @@ NA_DEV void seg_data(const SegLane &q, uint32_t j, uint32_t w[16], const uint32_
 {
     const bool last = j == q.J - 1;
     nbp = last ? (q.tail + 15) / 16 : 4u;
-    if constexpr (MODE == SEG_OPEN1) {
+    if constexpr (MODE == PASS_OPEN1) {
         if (last) mask_unit(w, q.tail);
         if constexpr (DEFER) return;
         p32_unit(h, r, w, nbp);
@@ -419,10 +417,10 @@ NA_DEV void seg_data(const SegLane &q, uint32_t j, uint32_t w[16], const uint32_
 #pragma unroll
         for (int i = 0; i < 16; ++i) w[i] ^= x[i];
         if (last) {
-            if ((MODE == SEG_SEAL || ok) && SEG_OK(q.dst + 64 * j, q.tail, 3, j)) seg_last_out(q.dst + 64 * j, q.tail, w);
-            if (MODE == SEG_SEAL) mask_unit(w, q.tail);
+            if ((MODE == PASS_SEAL || ok) && SEG_OK(q.dst + 64 * j, q.tail, 3, j)) seg_last_out(q.dst + 64 * j, q.tail, w);
+            if (MODE == PASS_SEAL) mask_unit(w, q.tail);
         }
-        if constexpr (MODE == SEG_SEAL && !DEFER) p32_unit(h, r, w, nbp);
+        if constexpr (MODE == PASS_SEAL && !DEFER) p32_unit(h, r, w, nbp);
     }
 }
 
@@ -466,7 +464,7 @@ NA_DEV void seg_step(const SegLane &q, const IO &io, uint32_t lane, uint32_t m, 
         if (q.b0 == 0 && q.live && q.ad_len && SEG_OK(q.ad, q.ad_len, 4, 0)) p32_ad(h, r, q.ad, q.ad_len);
         if (d0) {
             p32_unit(h, r, wu[0], nb0);
-            if (MODE == SEG_OPEN1) {
+            if (MODE == PASS_OPEN1) {
                 const uint32_t j = q.b0 - 1;
 #pragma unroll
                 for (int i = 0; i < 16; ++i) wu[0][i] ^= x[i];
@@ -485,12 +483,12 @@ NA_DEV void seg_step(const SegLane &q, const IO &io, uint32_t lane, uint32_t m, 
            solo_blocks2: the persistent and the K = 2 kernels hold two waves
            per SIMD) */
         uint32_t xs[2][16];
-        if (2 * m < q.nb && (MODE != SEG_DEC || ok))
+        if (2 * m < q.nb && (MODE != PASS_DEC || ok))
             solo_blocks2<true>(key, pre, q.b0 + 2 * m, q.n_lo, q.n_hi, xs[0], xs[1]);
 #pragma unroll
         for (uint32_t u = 0; u < 2; ++u) {
             const uint32_t blk = q.b0 + 2 * m + u;
-            if (2 * m + u < q.nb && blk != 0 && (MODE != SEG_DEC || ok)) {
+            if (2 * m + u < q.nb && blk != 0 && (MODE != PASS_DEC || ok)) {
                 uint32_t x[16], nbp;
 #pragma unroll
                 for (int i = 0; i < 16; ++i) x[i] = xs[u][i];
@@ -510,7 +508,7 @@ NA_DEV void seg_pass(const SegLane &q, const IO &io, uint32_t lane, uint32_t S, 
 {
     const uint64_t t0 = SegTL::now();
     uint32_t m0 = 0;
-    if (MODE != SEG_DEC && S) {
+    if (MODE != PASS_DEC && S) {
         seg_step<MODE, PRIO, true>(q, io, lane, 0u, S, tiles, key, pre, r, rw, s, h, okm, ok, tl);
         m0 = 1;
     }
@@ -615,15 +613,6 @@ NA_DEV void seg_tag(Fe acc, const SegLane &q, const uint32_t rw[4], const uint32
     fe_finish(acc, s, tag);
 }
 
-/* bit i: owner 8i + lane/8 has flag set */
-NA_DEV uint32_t seg_owner_mask(bool f, uint32_t lane)
-{
-    uint32_t m = 0;
-#pragma unroll
-    for (int i = 0; i < 8; ++i) m |= (__shfl((int)f, (int)(8u * i + (lane >> 3)), 64) != 0 ? 1u : 0u) << i;
-    return m;
-}
-
 /* A one-pass open's repair of rejected records' segments (in place: the
    plaintext XORed with the key stream again; out of place: zeroed), over
    the same coalesced stores, gated by badm.  `inplace` is per lane (a
@@ -691,7 +680,7 @@ NA_DEV void seg_job(const SegLane &q, const uint32_t key[8], const IO &io, uint3
     P32 h = p32_zero();
     if (S) io.dma(lane, 0, tiles);
     if (!OPEN) {
-        seg_pass<SEG_SEAL, PRIO>(q, io, lane, S, tiles, key, pre, r, rw, s, h, 0xffu, true, tl);
+        seg_pass<PASS_SEAL, PRIO>(q, io, lane, S, tiles, key, pre, r, rw, s, h, 0xffu, true, tl);
         after_pass();
         const uint64_t tc = SegTL::now();
         const Fe acc = seg_combine(q, rw, h, kmax);
@@ -705,7 +694,7 @@ NA_DEV void seg_job(const SegLane &q, const uint32_t key[8], const IO &io, uint3
         return;
     }
     if (vf) seg_auth(q, io, lane, S, tiles, key, pre, r, rw, s, h);
-    else seg_pass<SEG_OPEN1, PRIO>(q, io, lane, S, tiles, key, pre, r, rw, s, h, 0xffu, true, tl);
+    else seg_pass<PASS_OPEN1, PRIO>(q, io, lane, S, tiles, key, pre, r, rw, s, h, 0xffu, true, tl);
     after_pass();
     const Fe acc = seg_combine(q, rw, h, kmax);
     bool okl = false;
@@ -720,15 +709,15 @@ NA_DEV void seg_job(const SegLane &q, const uint32_t key[8], const IO &io, uint3
     const bool ok = __shfl((int)okl, seg_leader(q, lane), 64) != 0;
     if (vf) {
         if (__ballot(q.live && ok && q.nb > 0) == 0) return;
-        const uint32_t okm = seg_owner_mask(ok, lane);
+        const uint32_t okm = owner_mask<8>(ok, lane);
         __builtin_amdgcn_wave_barrier(); /* the AUTH pass's tile reads are done */
         if (S) io.dma(lane, 0, tiles);
-        seg_pass<SEG_DEC, PRIO>(q, io, lane, S, tiles, key, pre, r, rw, s, h, okm, ok, tl);
+        seg_pass<PASS_DEC, PRIO>(q, io, lane, S, tiles, key, pre, r, rw, s, h, okm, ok, tl);
         return;
     }
     const bool bad = q.live && !ok;
     if (__ballot(bad) == 0) return;
-    seg_repair(q, io, lane, S, tiles, key, pre, bad, seg_owner_mask(bad, lane), inplace);
+    seg_repair(q, io, lane, S, tiles, key, pre, bad, owner_mask<8>(bad, lane), inplace);
 }
 
 /* ---------------------------------------------------------------- uniform */

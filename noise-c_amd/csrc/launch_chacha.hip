@@ -100,35 +100,33 @@ KernelFn<RaggedArgs> chacha_ragged_fn(int k, bool open, bool fast, bool vf)
     return vf ? chacha_ragged_fn_t<true, true>(k, open) : chacha_ragged_fn_t<true, false>(k, open);
 }
 
-/* Resident workgroups of a kernel on this device (CUs x occupancy). */
-template <typename F>
-uint32_t resident_blocks(F fn)
-{
-    int dev = 0, cus = 0, per = 0;
-    if (hipGetDevice(&dev) != hipSuccess ||
-        hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess ||
-        hipOccupancyMaxActiveBlocksPerMultiprocessor(&per, fn, 256, 0) != hipSuccess || per < 1)
-        return 0;
-    return (uint32_t)(cus * per);
-}
-
-
-} // namespace
-
-/* the current device's CU count, cached per device (0: unknown) */
-static uint32_t duplex_run_chunk_cus()
+/* the current device's CU count, cached per device (a host may mix GPU
+   models); 0: unknown */
+uint32_t device_cus()
 {
     constexpr int MAX_DEV = 64;
     static std::atomic<uint32_t> cache[MAX_DEV];
     int dev = 0, cus = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= MAX_DEV) return 0;
-    uint32_t v = cache[dev].load(std::memory_order_relaxed);
+    if (hipGetDevice(&dev) != hipSuccess || dev < 0) return 0;
+    std::atomic<uint32_t> *c = dev < MAX_DEV ? &cache[dev] : nullptr; /* past the table: asked each time */
+    uint32_t v = c ? c->load(std::memory_order_relaxed) : 0;
     if (!v && hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && cus > 0) {
-        v = (uint32_t)cus;
-        cache[dev].store(v, std::memory_order_relaxed);
+        v = (uint32_t)cus; /* idempotent: a racing thread stores the same value */
+        if (c) c->store(v, std::memory_order_relaxed);
     }
     return v;
 }
+
+/* Resident workgroups of a kernel on this device (CUs x occupancy). */
+template <typename F>
+uint32_t resident_blocks(F fn)
+{
+    int per = 0;
+    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per, fn, 256, 0) != hipSuccess || per < 1) return 0;
+    return device_cus() * (uint32_t)per;
+}
+
+} // namespace
 
 int chacha_uniform(const UniformArgs &a, int k, bool open, bool fast, bool ukey, hipStream_t s)
 {
@@ -141,7 +139,7 @@ int chacha_uniform(const UniformArgs &a, int k, bool open, bool fast, bool ukey,
     }
     /* one lane per record: runs once the launch is two waves per SIMD
        (64 records per wave, four SIMDs per CU) */
-    const uint32_t cus = duplex_run_chunk_cus();
+    const uint32_t cus = device_cus();
     const bool runs = cus && (uint64_t)a.n_records >= 2ull * 4 * 64 * cus;
     KernelFn<UniformArgs> fn = chacha_uniform_fn(k, open, fast, ukey, a.vf != 0, runs);
     if (!fn) return NOISE_ERROR_INVALID_PARAM;
@@ -155,21 +153,16 @@ int chacha_uniform(const UniformArgs &a, int k, bool open, bool fast, bool ukey,
     return launch(fn, a.n_records, k, a, s);
 }
 
-/* chachapoly_duplex_solo's run length: the device's CU count (one seal and
-   one open block per CU); NOISE_AEAD_DUPLEX_RUNS=0 alternates block by
-   block (A/B runs) */
+/* chachapoly_duplex_solo's run length: the current device's CU count (one
+   seal and one open block per CU); NOISE_AEAD_DUPLEX_RUNS=0, read once,
+   alternates block by block (A/B runs) */
 static uint32_t duplex_run_chunk()
 {
-    static const uint32_t c = [] {
+    static const bool off = [] {
         const char *e = getenv("NOISE_AEAD_DUPLEX_RUNS");
-        if (e && e[0] == '0') return 0u;
-        int dev = 0, cus = 0;
-        if (hipGetDevice(&dev) != hipSuccess ||
-            hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus <= 0)
-            return 0u;
-        return (uint32_t)cus;
+        return e && e[0] == '0';
     }();
-    return c;
+    return off ? 0u : device_cus();
 }
 
 int chacha_duplex(const UniformArgs &a, const UniformArgs &b, int k, bool ukey, hipStream_t s)
@@ -179,7 +172,7 @@ int chacha_duplex(const UniformArgs &a, const UniformArgs &b, int k, bool ukey, 
     if (k == 1) {
         /* balance: the launch is one generation (two waves per SIMD at most,
            256-thread blocks of four waves; chachapoly.hip solo_blocks2) */
-        const uint32_t cus = duplex_run_chunk_cus();
+        const uint32_t cus = device_cus();
         UniformArgs a1 = a, b1 = b;
         a1.balance = b1.balance = cus && (uint64_t)(sb + ob) <= 2ull * cus;
         worker_park_for_batch(sb + ob);

@@ -164,11 +164,11 @@ def test_uniform_seal_open_vs_oracle(aead, gpu, oracle, cipher, lanes, packed, r
                 assert np.array_equal(seg, pt[i * in_stride: i * in_stride + L])
 
 
-@pytest.mark.parametrize("cipher,lanes", [(CHACHA, 0), (CHACHA, 1), (CHACHA, 4), (AES, 0)])
+@pytest.mark.parametrize("cipher,lanes", [(CHACHA, 0), (CHACHA, 1), (CHACHA, 4), (CHACHA, 8), (AES, 0)])
 @pytest.mark.parametrize("oflags", [0, FLAG_ONE_PASS])
 def test_uniform_staged_kernels(aead, gpu, oracle, cipher, lanes, oflags):
     """FAST layouts with one state per 256 records: the LDS-staged kernels
-    (ChaChaPoly wave-uniform key at one and four lanes per record, AESGCM
+    (ChaChaPoly wave-uniform key at one, four and eight lanes per record, AESGCM
     replicated T-tables) on a batch whose last workgroup is partial, every
     record vs the oracle, with AD; opens in the default (verify-first) order
     and with NOISE_AEAD_FLAG_ONE_PASS."""

@@ -25,7 +25,7 @@ REC_DT = [("in_off", "<u8"), ("out_off", "<u8"), ("nonce", "<u8"), ("ctx_off", "
           ("ad_off", "<u8"), ("len", "<u4"), ("ad_len", "<u4")]
 
 
-@pytest.mark.parametrize("cipher,lanes,rps", [(CHACHA, 4, 256), (CHACHA, 8, 256), (CHACHA, 4, 13),
+@pytest.mark.parametrize("cipher,lanes,rps", [(CHACHA, 4, 256), (CHACHA, 8, 256), (CHACHA, 4, 13), (CHACHA, 8, 13),
                                               (CHACHA, 1, 16), (CHACHA, 1, 64), (CHACHA, 64, 16), (AES, 0, 256),
                                               (AES, 0, 13)])
 @pytest.mark.parametrize("in_place", [False, True])

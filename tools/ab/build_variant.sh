@@ -8,7 +8,7 @@
 #     -> noise-c_amd/ab/libnoise_aead_hip_NAME.so (NOISE_AEAD_LIB=... selects it;
 #        tools/gpu/run.sh's `ab` step takes NAME)
 #
-# e.g. sh tools/ab/build_variant.sh authreg4 ab-arms-r5 "-DNA_AUTH_REG=4"
+# e.g. sh tools/ab/build_variant.sh authreg4 9d9091d "-DNA_AUTH_REG=4"
 set -eu
 NAME=$1 REV=$2 DEFS=${3:-}
 ROOT=$(cd "$(dirname "$0")/../.." && pwd)

@@ -1,5 +1,5 @@
 # One GPU call's steps, read from stdin, one per line (round 6: replaces the
-# per-experiment r0*_*.sh scripts; tools/gpu/README.md maps the old names).
+# per-experiment r0*_*.sh scripts; tools/ab/README.md, "The GPU scripts", maps the old names).
 #
 #   bash tools/gpu/run.sh OUTDIR <<'EOF'
 #   tests                        # every -m gpu test (pytest.log)
