@@ -26,8 +26,8 @@ REFUSED = [65520, 70000]
 
 
 def _fast_slot(L):
-    """a FAST slot: 16-B aligned, readable to roundup64(max(len, 1)), room for the tag"""
-    return max(((max(int(L), 1) + 63) // 64) * 64, int(L) + 16) + 64
+    """a FAST slot: 64-B aligned, readable to roundup64(max(len, 1)), room for the tag"""
+    return ((max(int(L), 1) + 16 + 63) // 64) * 64 + 64
 
 
 def _ragged_batch(rng, count, S):
