@@ -20,6 +20,22 @@
  *
  * Note: table-driven GHASH/AES on LDS/L1 is not constant-time, unlike the
  * reference's bit-serial GF128_mul (ghash.c:85-87); see DESIGN.md.
+ *
+ * Kernel map: three record bodies, each taking a GcmView.  Every open
+ * authenticates, takes the verdict and only then decrypts.
+ *   gcm_record (4 lanes; 256-word te/sb tables, aes_ctr_block): gcm_uniform;
+ *   gcm_record_staged<OPEN, FAST, CT, KL, RK> (4 or 8 lanes; the replicated
+ *     T-tables of GcmLds, aes_ctr_pre; round keys and Horner table passed
+ *     in): gcm_staged, gcm_duplex_staged and gcm_duplex_fused through
+ *     gcm_staged_rec (FAST, 4 lanes, the workgroup's LDS key slot) —
+ *     gcm_duplex_fused<true> alone keeps gcm_staged_rec_own, see there;
+ *     gcm_ragged_staged with a slot's keys from LDS, through the scalar
+ *     cache (seals whose wave shares a slot) or from the record's context;
+ *   gcm_wide_record (a 256-thread workgroup per record): gcm_wide and the
+ *     resident worker (worker.hip).
+ * Shared by the bodies: blk_mask, load_block / store_block<FAST>,
+ * gh_input_block, gh_step / gh_scale, gh_reduce_lanes<K>, gcm_tag_equal;
+ * by the staged kernels: te_fill<WG>, key_fill<WG, KL>, te_lane_tpl.
  */
 #include "aead_device.h"
 #include "aead_kernels.h"
@@ -229,35 +245,6 @@ NA_DEV void gh_mul_lds(uint32_t y[4], const uint4 *tab)
     y[0] = r0; y[1] = r1; y[2] = r2; y[3] = r3;
 }
 
-/* gh_mul_lds for one wave's latency (the wide record's few GHASH lanes):
-   the lookups in two batches of 16, each issued whole before one wait */
-NA_DEV void gh_mul_lds_lat(uint32_t y[4], const uint4 *tab)
-{
-    typedef uint32_t v4u __attribute__((ext_vector_type(4)));
-    const v4u *t4 = (const v4u *)tab;
-    uint32_t r0 = 0, r1 = 0, r2 = 0, r3 = 0;
-#pragma unroll
-    for (int half = 0; half < 2; ++half) {
-        v4u e[16];
-#pragma unroll
-        for (int j = 0; j < 8; ++j) {
-            const int p = 16 * half + 2 * j, b = p >> 1;
-            const uint32_t byte = (y[b >> 2] >> (8 * (b & 3))) & 255u;
-            e[2 * j] = t4[p * 16 + (byte >> 4)];
-            e[2 * j + 1] = t4[(p + 1) * 16 + (byte & 15)];
-        }
-        asm volatile("" : "+v"(e[0]), "+v"(e[1]), "+v"(e[2]), "+v"(e[3]), "+v"(e[4]), "+v"(e[5]), "+v"(e[6]),
-                          "+v"(e[7]), "+v"(e[8]), "+v"(e[9]), "+v"(e[10]), "+v"(e[11]), "+v"(e[12]), "+v"(e[13]),
-                          "+v"(e[14]), "+v"(e[15]));
-#pragma unroll
-        for (int j = 0; j < 16; j += 2) {
-            r0 = xor3(r0, e[j].x, e[j + 1].x); r1 = xor3(r1, e[j].y, e[j + 1].y);
-            r2 = xor3(r2, e[j].z, e[j + 1].z); r3 = xor3(r3, e[j].w, e[j + 1].w);
-        }
-    }
-    y[0] = r0; y[1] = r1; y[2] = r2; y[3] = r3;
-}
-
 /* The Horner step y <- y * H^4 (tables in LDS, or constant-time: y and the
    blocks in the natural domain, hn4 = H^4 there) and the final scale
    y <- y * H^(m+1) (the context's tables in global memory, or CT). */
@@ -406,7 +393,68 @@ struct GcmView {
     uint32_t len, ad_len;
 };
 
-/* Returns (seal) true; (open) whether the tag verified. */
+/* byte mask of the first nb (0..16) bytes of a 16-B block, word w */
+NA_DEV uint32_t blk_mask(uint32_t nb, int w)
+{
+    const int rb = (int)nb - 4 * w;
+    return rb >= 4 ? 0xffffffffu : (rb <= 0 ? 0u : ((1u << (8 * rb)) - 1u));
+}
+
+/* The nb (1..16) bytes of a record's data block; FAST as in chachapoly.hip
+   (16-B aligned record, input readable to roundup16): whole-block access. */
+template <bool FAST>
+NA_DEV void load_block(const uint8_t *p, uint32_t nb, uint32_t x[4])
+{
+    if (FAST) {
+        const uint4 v = *(const uint4 *)p;
+        x[0] = v.x; x[1] = v.y; x[2] = v.z; x[3] = v.w;
+    } else {
+        load16(p, nb, x);
+    }
+}
+
+template <bool FAST>
+NA_DEV void store_block(uint8_t *p, uint32_t nb, const uint32_t x[4])
+{
+    if (FAST && nb == 16) *(uint4 *)p = make_uint4(x[0], x[1], x[2], x[3]);
+    else store16(p, nb, x);
+}
+
+/* GHASH input block i of a record: AD blocks, CT blocks (zero-padded), the
+   lengths block BE64(8|AD|) || BE64(8|CT|) (cipher-aesgcm.c:135-154) */
+NA_DEV void gh_input_block(const uint8_t *ad, uint32_t ad_len, const uint8_t *ct, uint32_t len, uint32_t A,
+                           uint32_t M, uint32_t i, uint32_t x[4])
+{
+    if (i < A) {
+        const uint32_t rem = ad_len - 16 * i;
+        load16(ad + 16 * i, rem >= 16 ? 16u : rem, x);
+    } else if (i < A + M) {
+        const uint32_t b = i - A, rem = len - 16 * b;
+        load16(ct + 16 * b, rem >= 16 ? 16u : rem, x);
+    } else {
+        const uint64_t ab = (uint64_t)ad_len * 8, cb = (uint64_t)len * 8;
+        x[0] = __builtin_bswap32((uint32_t)(ab >> 32)); x[1] = __builtin_bswap32((uint32_t)ab);
+        x[2] = __builtin_bswap32((uint32_t)(cb >> 32)); x[3] = __builtin_bswap32((uint32_t)cb);
+    }
+}
+
+/* XOR of acc over the K lanes of a record group; every lane gets the sum */
+template <int K>
+NA_DEV void gh_reduce_lanes(uint32_t acc[4])
+{
+#pragma unroll
+    for (int off = 1; off < K; off <<= 1)
+#pragma unroll
+        for (int w = 0; w < 4; ++w) acc[w] ^= (uint32_t)__shfl_xor((int)acc[w], off, 64);
+}
+
+NA_DEV bool gcm_tag_equal(const uint32_t a[4], const uint32_t b[4])
+{
+    return ((a[0] ^ b[0]) | (a[1] ^ b[1]) | (a[2] ^ b[2]) | (a[3] ^ b[3])) == 0;
+}
+
+/* One record on K = 4 lanes with the small te/sb tables (gcm_uniform).
+   Returns (seal) true; (open) whether the tag verified. */
 template <bool OPEN, bool CT>
 NA_DEV bool gcm_record(const GcmView &rv, int l, const uint32_t *te, const uint32_t *sb)
 {
@@ -429,39 +477,25 @@ NA_DEV bool gcm_record(const GcmView &rv, int l, const uint32_t *te, const uint3
             else gh_mul(acc, tabH4);
         }
         uint32_t x[4];
-        if (i < A) {
-            const uint32_t rem = rv.ad_len - 16 * i;
-            load16(rv.ad + 16 * i, rem >= 16 ? 16u : rem, x);
-        } else if (i < A + M) {
+        if (!OPEN && i >= A && i < A + M) { /* seal: CTR and GHASH in one pass */
             const uint32_t d = i - A;
             const uint32_t rem = rv.len - 16 * d;
             const uint32_t nb = rem >= 16 ? 16u : rem;
             load16(rv.src + 16 * d, nb, x);
-            if (!OPEN) {
-                uint32_t ks[4];
-                aes_ctr_block(rk, te, sb, rv.nonce, 2 + d, ks);
+            uint32_t ks[4];
+            aes_ctr_block(rk, te, sb, rv.nonce, 2 + d, ks);
 #pragma unroll
-                for (int w = 0; w < 4; ++w) {
-                    const int rb = (int)nb - 4 * w;
-                    const uint32_t m = rb >= 4 ? 0xffffffffu : (rb <= 0 ? 0u : ((1u << (8 * rb)) - 1u));
-                    x[w] = (x[w] ^ ks[w]) & m;
-                }
-                store16(rv.dst + 16 * d, nb, x);
-            }
-        } else {
-            const uint64_t ab = (uint64_t)rv.ad_len * 8, cb = (uint64_t)rv.len * 8;
-            x[0] = __builtin_bswap32((uint32_t)(ab >> 32)); x[1] = __builtin_bswap32((uint32_t)ab);
-            x[2] = __builtin_bswap32((uint32_t)(cb >> 32)); x[3] = __builtin_bswap32((uint32_t)cb);
+            for (int w = 0; w < 4; ++w) x[w] = (x[w] ^ ks[w]) & blk_mask(nb, w);
+            store16(rv.dst + 16 * d, nb, x);
+        } else { /* open: any block; seal: AD or lengths (M = 0: no CT block is taken there) */
+            gh_input_block(rv.ad, rv.ad_len, rv.src, rv.len, A, OPEN ? M : 0, i, x);
         }
         if constexpr (CT) gh_to_nat(x);
         acc[0] ^= x[0]; acc[1] ^= x[1]; acc[2] ^= x[2]; acc[3] ^= x[3];
     }
     /* scale by H^(K-l) (lane l's last block has exponent K-l) */
     gh_scale<CT>(acc, ctx, K - 1 - l);
-#pragma unroll
-    for (int off = 1; off < K; off <<= 1)
-#pragma unroll
-        for (int w = 0; w < 4; ++w) acc[w] ^= (uint32_t)__shfl_xor((int)acc[w], off, 64);
+    gh_reduce_lanes<K>(acc);
     if constexpr (CT) gh_to_nat(acc); /* back to the GCM domain */
     /* tag = E_K(J0) xor S: every lane of the group computes it (one AES) */
     uint32_t ej[4];
@@ -473,8 +507,7 @@ NA_DEV bool gcm_record(const GcmView &rv, int l, const uint32_t *te, const uint3
     }
     uint32_t got[4];
     load16(rv.src + rv.len, 16, got);
-    const uint32_t diff = (tag[0] ^ got[0]) | (tag[1] ^ got[1]) | (tag[2] ^ got[2]) | (tag[3] ^ got[3]);
-    if (diff) return false; /* cipher-aesgcm.c:184-186: nothing decrypted */
+    if (!gcm_tag_equal(tag, got)) return false; /* cipher-aesgcm.c:184-186: nothing decrypted */
     for (uint32_t d = (c0 + K - (A % K)) % K; d < M; d += K) {
         const uint32_t rem = rv.len - 16 * d;
         const uint32_t nb = rem >= 16 ? 16u : rem;
@@ -517,33 +550,6 @@ __global__ __launch_bounds__(256) void gcm_uniform(UniformArgs a)
     rv.ad_len = a.ad_len;
     const bool ok = gcm_record<OPEN, CT>(rv, l, te, sb); /* open: verifies first */
     if (OPEN && l == GCM_LANES - 1 && a.status) a.status[rec] = ok ? 0 : 1;
-    if (!ok && !a.vf) scrub_rejected(rv.dst, rv.src, rv.len, (uint32_t)l, GCM_LANES);
-}
-
-template <bool OPEN, bool CT>
-__global__ __launch_bounds__(256) void gcm_ragged(RaggedArgs a)
-{
-    __shared__ uint32_t te[256], sb[256];
-    __shared__ uint32_t order[256 / GCM_LANES];
-    load_aes_tables(te, sb);
-    const uint32_t rec = window_rec<256 / GCM_LANES>(a.recs, a.n_records,
-                                                     blockIdx.x * (256u / GCM_LANES),
-                                                     threadIdx.x / GCM_LANES, order);
-    if (rec >= a.n_records) return;
-    const int l = (int)(threadIdx.x % GCM_LANES);
-    const RecDesc d = a.recs[rec];
-    if (reject_len(a, rec, d.len, l == GCM_LANES - 1)) return;
-    GcmView rv;
-    rv.src = a.in + d.in_off;
-    rv.dst = a.out + d.out_off;
-    rv.ad = a.ad ? a.ad + d.ad_off : nullptr;
-    rv.ctx = (const AesCtx *)((uintptr_t)a.keys + d.ctx_off);
-    rv.nonce = d.nonce;
-    rv.len = d.len;
-    rv.ad_len = d.ad_len;
-    const bool ok = gcm_record<OPEN, CT>(rv, l, te, sb);
-    if (l == GCM_LANES - 1 && a.status) a.status[rec] = ok ? 0 : 1;
-    if (!ok && !a.vf) scrub_rejected(rv.dst, rv.src, rv.len, (uint32_t)l, GCM_LANES);
 }
 
 /* ---------------------------- staged (uniform FAST, one state per workgroup)
@@ -563,26 +569,57 @@ __global__ __launch_bounds__(256) void gcm_ragged(RaggedArgs a)
  * The per-block work then touches no global memory but the record bytes.
  */
 
-struct GcmLds {
-    uint32_t te[2][256][64]; /* [Te0|Te1 or Te2|Te3][row][32 + 32 copies] */
+struct GcmKey { /* one state: its Horner multiply table (H^4, or H^8) and round keys */
     uint4 h4[GHASH_TAB_ENTRIES];
     uint32_t rk[60];
 };
 
-NA_DEV void gcm_lds_fill(GcmLds &L, const AesCtx *ctx)
+/* The staged kernels' LDS: the T-tables and NKEY state slots (one per
+   uniform job; ragged windows take two). */
+template <int NKEY>
+struct GcmLds {
+    uint32_t te[2][256][64]; /* [Te0|Te1 or Te2|Te3][row][32 + 32 copies] */
+    GcmKey key[NKEY];
+};
+
+/* Fills the replicated T-tables by a WG-thread workgroup (no barrier). */
+template <int WG>
+NA_DEV void te_fill(uint32_t (&te)[2][256][64])
 {
-    const int t = threadIdx.x;
-    /* 2 regions x 256 rows x 64 words = 32768 words: 8 uint4 per thread */
-    for (int q = t; q < 2 * 256 * 16; q += GCM_WG) {
+    /* 2 regions x 256 rows x 64 words = 32768 words: 8 uint4 per thread at WG = 1024 */
+    for (int q = threadIdx.x; q < 2 * 256 * 16; q += WG) {
         const int reg = q >> 12, row = (q >> 4) & 255, quad = q & 15;
         const int tab = 2 * reg + (quad >> 3); /* words 0-31: Te(2reg), 32-63: Te(2reg+1) */
         const uint32_t v = rotr(g_te0[row], 8 * tab);
-        ((uint4 *)&L.te[reg][row][0])[quad] = make_uint4(v, v, v, v);
+        ((uint4 *)&te[reg][row][0])[quad] = make_uint4(v, v, v, v);
     }
-    const uint4 *src = (const uint4 *)ctx->tab[GCM_LANES - 1];
-    for (int i = t; i < GHASH_TAB_ENTRIES; i += GCM_WG) L.h4[i] = src[i];
-    if (t < 60) L.rk[t] = ctx->rk[t];
-    __syncthreads();
+}
+
+/* the Horner multiply table of KL lanes per record: H^4, or H^8 */
+template <int KL>
+NA_DEV const uint4 *horner_tab(const AesCtx *ctx)
+{
+    return (const uint4 *)(KL == 8 ? ctx->tab8 : ctx->tab[GCM_LANES - 1]);
+}
+
+/* Fills one state slot (no barrier); tab = false leaves the multiply table
+   out (constant-time GHASH reads none). */
+template <int WG, int KL = GCM_LANES>
+NA_DEV void key_fill(GcmKey &k, const AesCtx *ctx, bool tab = true)
+{
+    const uint4 *src = horner_tab<KL>(ctx);
+    if (tab)
+        for (int i = threadIdx.x; i < GHASH_TAB_ENTRIES; i += WG) k.h4[i] = src[i];
+    if (threadIdx.x < 60) k.rk[threadIdx.x] = ctx->rk[threadIdx.x];
+}
+
+/* The per-lane lookup template word of te_lookup: byte0 = 4c (Te0/Te2 copy
+   c = lane mod 32), byte1 = 128 + 4c (Te1/Te3), byte2 = 1 (the Te2|Te3
+   region at 64 KB) */
+NA_DEV uint32_t te_lane_tpl()
+{
+    const uint32_t c = threadIdx.x & 31;
+    return (1u << 16) | ((128u + 4u * c) << 8) | (4u * c);
 }
 
 /* te: the LDS base of the replicated Te0|Te1, Te2|Te3 regions (GcmLds::te) */
@@ -595,46 +632,6 @@ NA_DEV uint32_t te_lookup(const uint8_t *te, uint32_t s, uint32_t lane_tpl)
                              (TAB & 1 ? 1u : 0u);
     const uint32_t addr = __builtin_amdgcn_perm(s, lane_tpl, sel);
     return *(const uint32_t *)(te + addr);
-}
-
-template <typename RK>
-NA_DEV void aes256_lds(const uint8_t *L, RK rk, uint32_t tpl, uint32_t &s0,
-                       uint32_t &s1, uint32_t &s2, uint32_t &s3)
-{
-    s0 ^= rk[0]; s1 ^= rk[1]; s2 ^= rk[2]; s3 ^= rk[3];
-#pragma unroll
-    for (int r = 1; r < 14; ++r) {
-        /* Te0[a>>24] ^ Te1[(b>>16)&255] ^ Te2[(c>>8)&255] ^ Te3[d&255] ^ rk */
-#define NA_COL(a, b, c, d, k)                                                        \
-    xor3(xor3(te_lookup<0, 3>(L, a, tpl), te_lookup<1, 2>(L, b, tpl),                   \
-              te_lookup<2, 1>(L, c, tpl)),                                             \
-         te_lookup<3, 0>(L, d, tpl), rk[k])
-        const uint32_t t0 = NA_COL(s0, s1, s2, s3, 4 * r);
-        const uint32_t t1 = NA_COL(s1, s2, s3, s0, 4 * r + 1);
-        const uint32_t t2 = NA_COL(s2, s3, s0, s1, 4 * r + 2);
-        const uint32_t t3 = NA_COL(s3, s0, s1, s2, 4 * r + 3);
-#undef NA_COL
-        s0 = t0; s1 = t1; s2 = t2; s3 = t3;
-    }
-    /* last round: S-box bytes out of the T-tables (Te0 = [2s,s,s,3s] MSB first,
-       Te1 = [3s,2s,s,s], Te2 = [s,3s,2s,s], Te3 = [s,s,3s,2s]) */
-#define NA_SB4(a, b, c, d)                                                          \
-    ((te_lookup<2, 3>(L, a, tpl) & 0xff000000u) | (te_lookup<3, 2>(L, b, tpl) & 0x00ff0000u) | \
-     (te_lookup<0, 1>(L, c, tpl) & 0x0000ff00u) | (te_lookup<1, 0>(L, d, tpl) & 0x000000ffu))
-    const uint32_t o0 = NA_SB4(s0, s1, s2, s3), o1 = NA_SB4(s1, s2, s3, s0);
-    const uint32_t o2 = NA_SB4(s2, s3, s0, s1), o3 = NA_SB4(s3, s0, s1, s2);
-#undef NA_SB4
-    s0 = o0 ^ rk[56]; s1 = o1 ^ rk[57]; s2 = o2 ^ rk[58]; s3 = o3 ^ rk[59];
-}
-
-template <typename RK>
-NA_DEV void aes_ctr_lds(const uint8_t *te, RK rk, uint32_t tpl, uint32_t n_hi,
-                        uint32_t n_lo, uint32_t ctr, uint32_t ks[4])
-{
-    uint32_t s0 = 0, s1 = n_hi, s2 = n_lo, s3 = ctr;
-    aes256_lds(te, rk, tpl, s0, s1, s2, s3);
-    ks[0] = __builtin_bswap32(s0); ks[1] = __builtin_bswap32(s1);
-    ks[2] = __builtin_bswap32(s2); ks[3] = __builtin_bswap32(s3);
 }
 
 /* Counter-mode caching.  Within one record the CTR input blocks
@@ -674,7 +671,7 @@ NA_DEV AesPre aes_pre_lds(const uint8_t *L, RK rk, uint32_t tpl, uint32_t n_hi,
 }
 
 /* E_K(0^32 || BE64(n) || BE32(ctr)) from the record's AesPre (ctr < 2^16),
-   as little-endian memory words; equals aes_ctr_lds. */
+   as little-endian memory words. */
 template <typename RK>
 NA_DEV void aes_ctr_pre(const uint8_t *L, RK rk, uint32_t tpl, const AesPre &p,
                         uint32_t ctr, uint32_t ks[4])
@@ -709,15 +706,8 @@ NA_DEV void aes_ctr_pre(const uint8_t *L, RK rk, uint32_t tpl, const AesPre &p,
     ks[2] = __builtin_bswap32(o2 ^ rk[58]); ks[3] = __builtin_bswap32(o3 ^ rk[59]);
 }
 
-/* byte mask of the first nb (0..16) bytes of a 16-B block, word w */
-NA_DEV uint32_t blk_mask(uint32_t nb, int w)
-{
-    const int rb = (int)nb - 4 * w;
-    return rb >= 4 ? 0xffffffffu : (rb <= 0 ? 0u : ((1u << (8 * rb)) - 1u));
-}
-
 /* CTR over one lane's data blocks d = d0, d0 + K, ... < M of a record, src to
-   dst: the decrypt pass of a VERIFY_FIRST open, after the tag verified. */
+   dst: the decrypt pass of an open, after the tag verified. */
 template <bool FAST = true, typename RK = const uint32_t *>
 NA_DEV void gcm_ctr_lane(const uint8_t *TE, RK rk, uint32_t tpl, const AesPre &pre,
                          const uint8_t *src, uint8_t *dst, uint32_t len, uint32_t d0, uint32_t M,
@@ -727,18 +717,88 @@ NA_DEV void gcm_ctr_lane(const uint8_t *TE, RK rk, uint32_t tpl, const AesPre &p
     for (uint32_t d = d0; d < M; d += K) {
         const uint32_t nb = min(len - 16 * d, 16u);
         uint32_t x[4], ks[4];
-        if (FAST) {
-            const uint4 v = *(const uint4 *)(src + 16 * d);
-            x[0] = v.x; x[1] = v.y; x[2] = v.z; x[3] = v.w;
-        } else {
-            load16(src + 16 * d, nb, x);
-        }
+        load_block<FAST>(src + 16 * d, nb, x);
         aes_ctr_pre(TE, rk, tpl, pre, 2 + d, ks);
 #pragma unroll
         for (int w = 0; w < 4; ++w) x[w] ^= ks[w];
-        if (FAST && nb == 16) *(uint4 *)(dst + 16 * d) = make_uint4(x[0], x[1], x[2], x[3]);
-        else store16(dst + 16 * d, nb, x);
+        store_block<FAST>(dst + 16 * d, nb, x);
     }
+}
+
+/* One record on KL lanes (l = 0..KL-1; 4, or 8 with the H^8 Horner table)
+   with the T-tables at TE and the record's round keys rk and Horner multiply
+   table h4 (H^KL) passed in: LDS slots, the scalar cache, or the context in
+   global memory.  FAST as in chachapoly.hip (16-B aligned record, input
+   readable to roundup16).  The seal runs CTR and GHASH in one pass over the
+   blocks; the open only authenticates there, takes the verdict, and decrypts
+   (gcm_ctr_lane) a record that verified: no byte of a rejected record is
+   written (cipher-aesgcm.c:184-186).  Returns (seal) true; (open) whether
+   the tag verified. */
+template <bool OPEN, bool FAST, bool CT, int KL = GCM_LANES, typename RK = const uint32_t *>
+NA_DEV bool gcm_record_staged(const GcmView &rv, int l, const uint8_t *TE, uint32_t tpl,
+                              RK rk, const uint4 *h4)
+{
+    constexpr int K = KL;
+    static_assert(K == 4 || K == 8, "lanes per AES-GCM record");
+    uint32_t h4n[4] = {0, 0, 0, 0};
+    if constexpr (CT) {
+#pragma unroll
+        for (int w = 0; w < 4; ++w) h4n[w] = K == 8 ? rv.ctx->hn8[w] : rv.ctx->hn[K - 1][w];
+    }
+    const uint32_t n_hi = (uint32_t)(rv.nonce >> 32), n_lo = (uint32_t)rv.nonce;
+    const uint32_t len = rv.len, ad_len = rv.ad_len;
+    const uint32_t A = (ad_len + 15) / 16, M = (len + 15) / 16;
+    const uint32_t n = A + M + 1;
+    const uint32_t c0 = ((uint32_t)l + n) % K;
+    /* GHASH (and, sealing, CTR) over this lane's blocks i = c0, c0+K, ... */
+    uint32_t acc[4] = {0, 0, 0, 0};
+    const AesPre pre = aes_pre_lds(TE, rk, tpl, n_hi, n_lo);
+#pragma unroll 1
+    for (uint32_t i = c0; i < n; i += K) {
+        if (i != c0) gh_step<CT>(acc, h4, h4n);
+        uint32_t x[4];
+        if (i >= A && i < A + M) {
+            const uint32_t d = i - A;
+            const uint32_t nb = min(len - 16 * d, 16u);
+            load_block<FAST>(rv.src + 16 * d, nb, x);
+            if (!OPEN) {
+                uint32_t ks[4];
+                aes_ctr_pre(TE, rk, tpl, pre, 2 + d, ks);
+#pragma unroll
+                for (int w = 0; w < 4; ++w) x[w] ^= ks[w];
+                store_block<FAST>(rv.dst + 16 * d, nb, x);
+            }
+#pragma unroll
+            for (int w = 0; w < 4; ++w) x[w] &= blk_mask(nb, w);
+        } else { /* an AD block or the lengths block (M = 0: no CT block is taken there) */
+            gh_input_block(rv.ad, ad_len, nullptr, len, A, 0, i, x);
+        }
+        if constexpr (CT) gh_to_nat(x);
+        acc[0] ^= x[0]; acc[1] ^= x[1]; acc[2] ^= x[2]; acc[3] ^= x[3];
+    }
+    /* scale by H^(K-l) from the context's tables (once per lane) */
+    gh_scale<CT, K>(acc, rv.ctx, K - 1 - l);
+    gh_reduce_lanes<K>(acc);
+    if constexpr (CT) gh_to_nat(acc);
+    uint32_t ej[4];
+    aes_ctr_pre(TE, rk, tpl, pre, 1u, ej);
+    const uint32_t tag[4] = {acc[0] ^ ej[0], acc[1] ^ ej[1], acc[2] ^ ej[2], acc[3] ^ ej[3]};
+    if (!OPEN) {
+        if (l == K - 1) {
+            uint8_t *t = rv.dst + len;
+            if (FAST && (len & 15) == 0) *(uint4 *)t = make_uint4(tag[0], tag[1], tag[2], tag[3]);
+            else if (FAST && (len & 7) == 0) {
+                *(uint2 *)t = make_uint2(tag[0], tag[1]);
+                *(uint2 *)(t + 8) = make_uint2(tag[2], tag[3]);
+            } else store16(t, 16, tag);
+        }
+        return true;
+    }
+    uint32_t got[4];
+    load16(rv.src + len, 16, got);
+    const bool ok = gcm_tag_equal(tag, got);
+    if (ok) gcm_ctr_lane<FAST>(TE, rk, tpl, pre, rv.src, rv.dst, len, (c0 + K - (A % K)) % K, M, K);
+    return ok;
 }
 
 /* This thread's record of block blk (records [blk * 256, blk * 256 + 256))
@@ -746,6 +806,38 @@ NA_DEV void gcm_ctr_lane(const uint8_t *TE, RK rk, uint32_t tpl, const AesPre &p
    multiply-by-H^4 table and round keys (h4_lds, rk) in LDS. */
 template <bool OPEN, bool CT, typename RK>
 NA_DEV void gcm_staged_rec(const UniformArgs &a, const uint8_t *TE, const uint4 *h4_lds,
+                           RK rk, uint32_t blk)
+{
+    const uint32_t rec0 = blk * (uint32_t)GCM_WG_RECS;
+    const uint32_t st = rec0 / a.rps; /* one state per workgroup (host-checked) */
+    const uint32_t rec = rec0 + threadIdx.x / GCM_LANES;
+    if (rec >= a.n_records) return;
+    const int l = (int)(threadIdx.x % GCM_LANES);
+    GcmView rv;
+    rv.src = a.in + (size_t)rec * a.in_stride;
+    rv.dst = a.out + (size_t)rec * a.out_stride;
+    /* no null test on a.ad (read only when ad_len > 0): with one the standalone
+       seal measured 1.3 % slower */
+    rv.ad = a.ad + (size_t)rec * a.ad_stride;
+    rv.ctx = (const AesCtx *)a.keys + st;
+    rv.nonce = a.nonce_base[st] + (uint64_t)(rec - st * a.rps);
+    rv.len = a.len;
+    rv.ad_len = a.ad_len;
+    const bool ok = gcm_record_staged<OPEN, true, CT, GCM_LANES, RK>(rv, l, TE, te_lane_tpl(), rk, h4_lds);
+    if (OPEN && l == GCM_LANES - 1 && a.status) a.status[rec] = ok ? 0 : 1;
+}
+
+/* gcm_staged_rec as the body it had before it called gcm_record_staged, text
+   unchanged (the one-pass open order under !a.vf included, which no caller
+   can request: open_vf), kept for gcm_duplex_fused<true> alone.  Through the
+   shared body the constant-time fused duplex measured 0.2 % slower than
+   before, under its A/B range; the order of the hn load and an inline
+   lengths block did not bring it back, and this body with only the one-pass
+   order cut measured under the range once more (DESIGN.md 5,
+   profiles/refactor_aes/ab.jsonl).  A fix to gcm_record_staged belongs here
+   too. */
+template <bool OPEN, bool CT, typename RK>
+NA_DEV void gcm_staged_rec_own(const UniformArgs &a, const uint8_t *TE, const uint4 *h4_lds,
                            RK rk, uint32_t blk)
 {
     constexpr int K = GCM_LANES;
@@ -866,17 +958,19 @@ NA_DEV void gcm_staged_rec(const UniformArgs &a, const uint8_t *TE, const uint4 
 
 /* One 1024-thread workgroup of a uniform staged job. */
 template <bool OPEN, bool CT>
-NA_DEV void gcm_staged_wg(const UniformArgs &a, GcmLds &L, uint32_t blk)
+NA_DEV void gcm_staged_wg(const UniformArgs &a, GcmLds<1> &L, uint32_t blk)
 {
     const uint32_t st = blk * (uint32_t)GCM_WG_RECS / a.rps;
-    gcm_lds_fill(L, (const AesCtx *)a.keys + st);
-    gcm_staged_rec<OPEN, CT>(a, (const uint8_t *)&L.te[0][0][0], L.h4, L.rk, blk);
+    te_fill<GCM_WG>(L.te);
+    key_fill<GCM_WG>(L.key[0], (const AesCtx *)a.keys + st);
+    __syncthreads();
+    gcm_staged_rec<OPEN, CT>(a, (const uint8_t *)&L.te[0][0][0], L.key[0].h4, L.key[0].rk, blk);
 }
 
 template <bool OPEN, bool CT>
 __global__ __launch_bounds__(GCM_WG) void gcm_staged(UniformArgs a)
 {
-    __shared__ GcmLds L;
+    __shared__ GcmLds<1> L;
     gcm_staged_wg<OPEN, CT>(a, L, blockIdx.x);
 }
 
@@ -889,7 +983,7 @@ template <bool CT>
 __global__ __launch_bounds__(GCM_WG) void gcm_duplex_staged(UniformArgs s, UniformArgs o,
                                                              uint32_t s_blocks, uint32_t o_blocks)
 {
-    __shared__ GcmLds L;
+    __shared__ GcmLds<1> L;
     const uint32_t n = min(s_blocks, o_blocks);
     uint32_t b = blockIdx.x;
     bool open;
@@ -910,6 +1004,26 @@ __global__ __launch_bounds__(GCM_WG) void gcm_duplex_staged(UniformArgs s, Unifo
    record as soon as its seal record is done, so a CU's SIMDs stay busy
    through the first half's uneven finish and the workgroup drains once, not
    twice.  Results are those of the separate kernels (same per-record code). */
+template <bool CT>
+__global__ __launch_bounds__(GCM_WG) void gcm_duplex_fused(UniformArgs s, UniformArgs o,
+                                                            uint32_t s_blocks, uint32_t o_blocks)
+{
+    __shared__ GcmLds<2> L;
+    const uint32_t b = blockIdx.x;
+    te_fill<GCM_WG>(L.te);
+    if (b < s_blocks) key_fill<GCM_WG>(L.key[0], (const AesCtx *)s.keys + b * (uint32_t)GCM_WG_RECS / s.rps);
+    if (b < o_blocks) key_fill<GCM_WG>(L.key[1], (const AesCtx *)o.keys + b * (uint32_t)GCM_WG_RECS / o.rps);
+    __syncthreads();
+    const uint8_t *TE = (const uint8_t *)&L.te[0][0][0];
+    if constexpr (CT) { /* its own record body: see gcm_staged_rec_own */
+        if (b < s_blocks) gcm_staged_rec_own<false, CT>(s, TE, L.key[0].h4, L.key[0].rk, b);
+        if (b < o_blocks) gcm_staged_rec_own<true, CT>(o, TE, L.key[1].h4, L.key[1].rk, b);
+    } else {
+        if (b < s_blocks) gcm_staged_rec<false, CT>(s, TE, L.key[0].h4, L.key[0].rk, b);
+        if (b < o_blocks) gcm_staged_rec<true, CT>(o, TE, L.key[1].h4, L.key[1].rk, b);
+    }
+}
+
 /* Round keys through the scalar cache.  Where a wave's records share one
    state its 60 round-key words are wave-uniform: read with s_load from the
    context in global memory they cost no LDS cycle, where the LDS copy costs
@@ -930,41 +1044,6 @@ NA_DEV RkS rk_scalar(const uint32_t *p)
     return (RkS)(uintptr_t)(((uint64_t)hi << 32) | lo);
 }
 
-struct GcmLds2 {
-    uint32_t te[2][256][64];
-    uint4 h4[2][GHASH_TAB_ENTRIES];
-    uint32_t rk[2][60];
-};
-
-NA_DEV void gcm_key_fill(uint4 *h4, uint32_t *rk, const AesCtx *ctx)
-{
-    const uint4 *src = (const uint4 *)ctx->tab[GCM_LANES - 1];
-    for (int i = threadIdx.x; i < GHASH_TAB_ENTRIES; i += GCM_WG) h4[i] = src[i];
-    if (threadIdx.x < 60) rk[threadIdx.x] = ctx->rk[threadIdx.x];
-}
-
-template <bool CT>
-__global__ __launch_bounds__(GCM_WG) void gcm_duplex_fused(UniformArgs s, UniformArgs o,
-                                                            uint32_t s_blocks, uint32_t o_blocks)
-{
-    __shared__ GcmLds2 L;
-    const uint32_t b = blockIdx.x;
-    const int t = threadIdx.x;
-    for (int q = t; q < 2 * 256 * 16; q += GCM_WG) {
-        const int reg = q >> 12, row = (q >> 4) & 255, quad = q & 15;
-        const int tab = 2 * reg + (quad >> 3);
-        const uint32_t v = rotr(g_te0[row], 8 * tab);
-        ((uint4 *)&L.te[reg][row][0])[quad] = make_uint4(v, v, v, v);
-    }
-    if (b < s_blocks) gcm_key_fill(L.h4[0], L.rk[0], (const AesCtx *)s.keys + b * (uint32_t)GCM_WG_RECS / s.rps);
-    if (b < o_blocks) gcm_key_fill(L.h4[1], L.rk[1], (const AesCtx *)o.keys + b * (uint32_t)GCM_WG_RECS / o.rps);
-    __syncthreads();
-    const uint8_t *TE = (const uint8_t *)&L.te[0][0][0];
-    if (b < s_blocks) gcm_staged_rec<false, CT>(s, TE, L.h4[0], L.rk[0], b);
-    if (b < o_blocks) gcm_staged_rec<true, CT>(o, TE, L.h4[1], L.rk[1], b);
-}
-
-
 /* ------------------------------ staged ragged (any mix of states / lengths)
  *
  * 1024-thread workgroups over windows of 256 descriptors, with the same
@@ -972,192 +1051,48 @@ __global__ __launch_bounds__(GCM_WG) void gcm_duplex_fused(UniformArgs s, Unifor
  * the GHASH Horner table and the round keys of up to two states are staged
  * in LDS slots (the states of the window's first and last records: a window
  * that spans a run boundary of per-state records holds exactly these two);
- * a record of any other state reads its own context from global memory.
+ * a record of any other state reads its own context from global memory (the
+ * cold path, inlined: as an out-of-line call its frame and caller-saved
+ * registers cost the slot path scratch traffic and C5's AES kernels 2-5 %,
+ * profiles/r01_aes_inline_ab.jsonl).
  * Records are taken in length order inside the window (window_rec) so the
  * 16 records of a wave have near-equal lengths.
- */
-template <int NREC>
-struct GcmLdsR {
-    uint32_t te[2][256][64];
-    uint4 h4[2][GHASH_TAB_ENTRIES];
-    uint32_t rk[2][60];
-    uint32_t order[NREC];
-};
-
-/* One record, 4 lanes (l = 0..3): gcm_staged's GHASH/CTR core with the
-   record's tables passed in; FAST as in chachapoly.hip (16-B aligned record,
-   input readable to roundup16). */
-template <bool OPEN, bool FAST, bool CT, int KL = GCM_LANES, typename RK = const uint32_t *>
-NA_DEV bool gcm_record_staged(const GcmView &rv, int l, const uint8_t *TE, uint32_t tpl,
-                              RK rk, const uint4 *h4, bool vf)
-{
-    /* KL lanes per record (4, or 8 with the H^8 Horner table): the Horner
-       step is H^KL, h4 its multiply table */
-    constexpr int K = KL;
-    static_assert(K == 4 || K == 8, "lanes per AES-GCM record");
-    uint32_t h4n[4] = {0, 0, 0, 0};
-    if constexpr (CT) {
-#pragma unroll
-        for (int w = 0; w < 4; ++w) h4n[w] = K == 8 ? rv.ctx->hn8[w] : rv.ctx->hn[K - 1][w];
-    }
-    const uint32_t n_hi = (uint32_t)(rv.nonce >> 32), n_lo = (uint32_t)rv.nonce;
-    const uint32_t len = rv.len, ad_len = rv.ad_len;
-    const uint32_t A = (ad_len + 15) / 16, M = (len + 15) / 16;
-    const uint32_t n = A + M + 1;
-    const uint32_t c0 = ((uint32_t)l + n) % K;
-    uint32_t acc[4] = {0, 0, 0, 0};
-    const AesPre pre = aes_pre_lds(TE, rk, tpl, n_hi, n_lo);
-#pragma unroll 1
-    for (uint32_t i = c0; i < n; i += K) {
-        if (i != c0) gh_step<CT>(acc, h4, h4n);
-        uint32_t x[4];
-        if (i >= A && i < A + M) {
-            const uint32_t d = i - A;
-            const uint32_t nb = min(len - 16 * d, 16u);
-            if (FAST) {
-                const uint4 v = *(const uint4 *)(rv.src + 16 * d);
-                x[0] = v.x; x[1] = v.y; x[2] = v.z; x[3] = v.w;
-            } else {
-                load16(rv.src + 16 * d, nb, x);
-            }
-            /* one pass for both directions (gcm_staged): open decrypts as it
-               authenticates and repairs on a MAC failure; VERIFY_FIRST opens
-               decrypt after the verdict */
-            if (!OPEN || !vf) {
-                uint32_t ks[4], y[4];
-                aes_ctr_pre(TE, rk, tpl, pre, 2 + d, ks);
-#pragma unroll
-                for (int w = 0; w < 4; ++w) y[w] = x[w] ^ ks[w];
-                if (FAST && nb == 16) *(uint4 *)(rv.dst + 16 * d) = make_uint4(y[0], y[1], y[2], y[3]);
-                else store16(rv.dst + 16 * d, nb, y);
-                if (!OPEN) {
-#pragma unroll
-                    for (int w = 0; w < 4; ++w) x[w] = y[w];
-                }
-            }
-#pragma unroll
-            for (int w = 0; w < 4; ++w) x[w] &= blk_mask(nb, w);
-        } else if (i < A) {
-            const uint32_t rem = ad_len - 16 * i;
-            load16(rv.ad + 16 * i, rem >= 16 ? 16u : rem, x);
-        } else {
-            const uint64_t ab = (uint64_t)ad_len * 8, cb = (uint64_t)len * 8;
-            x[0] = __builtin_bswap32((uint32_t)(ab >> 32)); x[1] = __builtin_bswap32((uint32_t)ab);
-            x[2] = __builtin_bswap32((uint32_t)(cb >> 32)); x[3] = __builtin_bswap32((uint32_t)cb);
-        }
-        if constexpr (CT) gh_to_nat(x);
-        acc[0] ^= x[0]; acc[1] ^= x[1]; acc[2] ^= x[2]; acc[3] ^= x[3];
-    }
-    gh_scale<CT, K>(acc, rv.ctx, K - 1 - l);
-#pragma unroll
-    for (int off = 1; off < K; off <<= 1)
-#pragma unroll
-        for (int w = 0; w < 4; ++w) acc[w] ^= (uint32_t)__shfl_xor((int)acc[w], off, 64);
-    if constexpr (CT) gh_to_nat(acc);
-    uint32_t ej[4];
-    aes_ctr_pre(TE, rk, tpl, pre, 1u, ej);
-    const uint32_t tag[4] = {acc[0] ^ ej[0], acc[1] ^ ej[1], acc[2] ^ ej[2], acc[3] ^ ej[3]};
-    if (!OPEN) {
-        if (l == K - 1) store16(rv.dst + len, 16, tag);
-        return true;
-    }
-    uint32_t got[4];
-    load16(rv.src + len, 16, got);
-    const bool ok = ((tag[0] ^ got[0]) | (tag[1] ^ got[1]) | (tag[2] ^ got[2]) | (tag[3] ^ got[3])) == 0;
-    if (vf) {
-        if (ok) gcm_ctr_lane<FAST>(TE, rk, tpl, pre, rv.src, rv.dst, len, (c0 + K - (A % K)) % K, M, K);
-        return ok;
-    }
-    if (ok) return true;
-    /* MAC failure: in place, the lane's blocks XORed with their key stream
-       once more give back the ciphertext as given (the reference leaves the
-       buffer untouched, cipher-aesgcm.c:184-186); out of place the caller's
-       scrub_rejected zeroes the plaintext written */
-    if (rv.dst == rv.src) {
-        for (uint32_t d = (c0 + K - (A % K)) % K; d < M; d += K) {
-            const uint32_t nb = min(len - 16 * d, 16u);
-            uint32_t x[4], ks[4];
-            if (FAST) {
-                const uint4 v = *(const uint4 *)(rv.dst + 16 * d);
-                x[0] = v.x; x[1] = v.y; x[2] = v.z; x[3] = v.w;
-            } else {
-                load16(rv.dst + 16 * d, nb, x);
-            }
-            aes_ctr_pre(TE, rk, tpl, pre, 2 + d, ks);
-#pragma unroll
-            for (int w = 0; w < 4; ++w) x[w] ^= ks[w];
-            if (FAST && nb == 16) *(uint4 *)(rv.dst + 16 * d) = make_uint4(x[0], x[1], x[2], x[3]);
-            else store16(rv.dst + 16 * d, nb, x);
-        }
-    }
-    return false;
-}
-
-/* the cold path: a record whose state has no LDS slot.  Inlined: as an
-   out-of-line call its frame and caller-saved registers cost the slot path
-   scratch traffic (open 176 -> 104 B/lane, seal 64 -> 0) and C5's AES
-   kernels 2-5 % (profiles/r01_aes_inline_ab.jsonl). */
-template <int KL>
-NA_DEV const uint4 *horner_tab(const AesCtx *ctx)
-{
-    return (const uint4 *)(KL == 8 ? ctx->tab8 : ctx->tab[GCM_LANES - 1]);
-}
-
-template <bool OPEN, bool FAST, bool CT, int KL>
-__device__ __forceinline__ bool gcm_record_global(const GcmView &rv, int l,
-                                                  const uint8_t *TE, uint32_t tpl, bool vf)
-{
-    return gcm_record_staged<OPEN, FAST, CT, KL>(rv, l, TE, tpl, rv.ctx->rk, horner_tab<KL>(rv.ctx),
-                                                 vf);
-}
-
-/* WG threads per workgroup (1024, or 256 for batches too small to give
-   every CU a 1024-thread workgroup); WG / KL record groups of KL lanes (4,
-   or 8 with the H^8 Horner table), each running R records of the window's
-   R * WG / KL one after another (snake_rank).  The T-tables hold the CU's
-   LDS, so a workgroup owns its CU until its longest wave ends: with R = 1 a
-   window of mixed lengths leaves most waves idle while the one holding the
-   longest records finishes; R = 2 pairs long with short records so every
-   wave carries about the window's mean (KL = 8 keeps that at 256 records
-   per window). */
+ *
+ * WG threads per workgroup (1024, or 256 for batches too small to give
+ * every CU a 1024-thread workgroup); WG / KL record groups of KL lanes (4,
+ * or 8 with the H^8 Horner table), each running R records of the window's
+ * R * WG / KL one after another (snake_rank).  The T-tables hold the CU's
+ * LDS, so a workgroup owns its CU until its longest wave ends: with R = 1 a
+ * window of mixed lengths leaves most waves idle while the one holding the
+ * longest records finishes; R = 2 pairs long with short records so every
+ * wave carries about the window's mean (KL = 8 keeps that at 256 records
+ * per window). */
 template <bool OPEN, bool FAST, int WG, bool CT, int R = 1, int KL = GCM_LANES>
 __global__ __launch_bounds__(WG) void gcm_ragged_staged(RaggedArgs a)
 {
     constexpr int K = KL, NG = WG / KL, NREC = NG * R;
-    __shared__ GcmLdsR<NREC> L;
+    __shared__ GcmLds<2> L;
+    __shared__ uint32_t order[NREC];
     const uint8_t *TE = (const uint8_t *)&L.te[0][0][0];
     const uint32_t base = blockIdx.x * (uint32_t)NREC;
     const uint32_t last = min(base + (uint32_t)NREC, a.n_records) - 1;
     const uint64_t slot_off[2] = {a.recs[base].ctx_off, a.recs[last].ctx_off};
-    /* T-tables (as gcm_lds_fill) and the two slots' tables */
-    for (int q = threadIdx.x; q < 2 * 256 * 16; q += WG) {
-        const int reg = q >> 12, row = (q >> 4) & 255, quad = q & 15;
-        const int tab = 2 * reg + (quad >> 3);
-        const uint32_t v = rotr(g_te0[row], 8 * tab);
-        ((uint4 *)&L.te[reg][row][0])[quad] = make_uint4(v, v, v, v);
-    }
+    te_fill<WG>(L.te);
 #pragma unroll
-    for (int sl = 0; sl < 2; ++sl) {
-        const AesCtx *ctx = (const AesCtx *)(a.keys + slot_off[sl]);
-        const uint4 *src = horner_tab<KL>(ctx);
-        if (!CT)
-            for (int i = threadIdx.x; i < GHASH_TAB_ENTRIES; i += WG) L.h4[sl][i] = src[i];
-        if (threadIdx.x < 60) L.rk[sl][threadIdx.x] = ctx->rk[threadIdx.x];
-    }
+    for (int sl = 0; sl < 2; ++sl) key_fill<WG, KL>(L.key[sl], (const AesCtx *)(a.keys + slot_off[sl]), !CT);
     const uint32_t g = threadIdx.x / K;
     if constexpr (R > 1) { /* sort the whole window; groups take ranks by snake_rank */
-        window_rec<NREC>(a.recs, a.n_records, base, 0, L.order);
+        window_rec<NREC>(a.recs, a.n_records, base, 0, order);
     }
     const int l = (int)(threadIdx.x % K);
-    const uint32_t lane = threadIdx.x & 63;
-    const uint32_t tpl = (1u << 16) | ((128u + 4u * (lane & 31)) << 8) | (4u * (lane & 31));
+    const uint32_t tpl = te_lane_tpl();
 #pragma unroll 1
     for (int p = 0; p < R; ++p) {
         uint32_t rec;
         if constexpr (R == 1) {
-            rec = window_rec<NREC>(a.recs, a.n_records, base, g, L.order);
+            rec = window_rec<NREC>(a.recs, a.n_records, base, g, order);
         } else {
-            const uint32_t key = L.order[snake_rank<NG>(g, p)];
+            const uint32_t key = order[snake_rank<NG>(g, p)];
             rec = key != 0xFFFFFFFFu ? base + (key & (NREC <= 256 ? 0xFFu : 0x1FFu)) : 0xFFFFFFFFu;
         }
         if (rec >= a.n_records) continue;
@@ -1173,41 +1108,21 @@ __global__ __launch_bounds__(WG) void gcm_ragged_staged(RaggedArgs a)
         rv.ad_len = d.ad_len;
         bool ok = false; /* every path below sets it */
         const int sl = d.ctx_off == slot_off[0] ? 0 : (d.ctx_off == slot_off[1] ? 1 : -1);
-        const bool vf = OPEN && a.vf;
         bool done = false;
         if constexpr (!OPEN) { /* seals only: measured slower in the opens and in C3's fused duplex */
             const int s0 = __builtin_amdgcn_readfirstlane(sl);
             if (s0 >= 0 && __all(sl == s0)) { /* the wave's records share an LDS slot */
                 ok = gcm_record_staged<OPEN, FAST, CT, KL>(
-                    rv, l, TE, tpl, rk_scalar(((const AesCtx *)(a.keys + slot_off[s0]))->rk), L.h4[s0], vf);
+                    rv, l, TE, tpl, rk_scalar(((const AesCtx *)(a.keys + slot_off[s0]))->rk), L.key[s0].h4);
                 done = true;
             }
         }
         if (done) {
         } else if (sl >= 0)
-            ok = gcm_record_staged<OPEN, FAST, CT, KL>(rv, l, TE, tpl, L.rk[sl], L.h4[sl], vf);
+            ok = gcm_record_staged<OPEN, FAST, CT, KL>(rv, l, TE, tpl, L.key[sl].rk, L.key[sl].h4);
         else /* a third state in the window: its own context, from global memory */
-            ok = gcm_record_global<OPEN, FAST, CT, KL>(rv, l, TE, tpl, vf);
+            ok = gcm_record_staged<OPEN, FAST, CT, KL>(rv, l, TE, tpl, rv.ctx->rk, horner_tab<KL>(rv.ctx));
         if (l == K - 1 && a.status) a.status[rec] = ok ? 0 : 1;
-        if (!ok && !vf) scrub_rejected(rv.dst, rv.src, rv.len, (uint32_t)l, K);
-    }
-}
-
-/* GHASH input block i of a record: AD blocks, CT blocks (zero-padded), the
-   lengths block BE64(8|AD|) || BE64(8|CT|) (cipher-aesgcm.c:135-154) */
-NA_DEV void gh_input_block(const uint8_t *ad, uint32_t ad_len, const uint8_t *ct, uint32_t len, uint32_t A,
-                           uint32_t M, uint32_t i, uint32_t x[4])
-{
-    if (i < A) {
-        const uint32_t rem = ad_len - 16 * i;
-        load16(ad + 16 * i, rem >= 16 ? 16u : rem, x);
-    } else if (i < A + M) {
-        const uint32_t b = i - A, rem = len - 16 * b;
-        load16(ct + 16 * b, rem >= 16 ? 16u : rem, x);
-    } else {
-        const uint64_t ab = (uint64_t)ad_len * 8, cb = (uint64_t)len * 8;
-        x[0] = __builtin_bswap32((uint32_t)(ab >> 32)); x[1] = __builtin_bswap32((uint32_t)ab);
-        x[2] = __builtin_bswap32((uint32_t)(cb >> 32)); x[3] = __builtin_bswap32((uint32_t)cb);
     }
 }
 
@@ -1284,8 +1199,8 @@ NA_DEV uint32_t gh_input_byte(const uint8_t *ad, uint32_t ad_len, const uint8_t 
 /* One record on a 256-thread workgroup (the whole workgroup calls it):
    te/sb/hk are the LDS tables (hk: the record's H^K multiply table when not
    CT), wl five LDS words (verdict, E_K(J0)).  Returns (open) whether the tag
-   verified; writes status when given; a rejected record's output is left
-   alone here (the caller scrubs).  Shared by gcm_wide and the resident
+   verified; writes status when given; a rejected record's output is never
+   written.  Shared by gcm_wide and the resident
    worker (worker.hip); dbg, when given, takes thread 0's s_memtime stamps. */
 template <bool OPEN, bool CT, int K = 8>
 NA_DEV bool gcm_wide_record(const uint8_t *src, uint8_t *dst, const uint8_t *ad, uint32_t ad_len,
@@ -1453,9 +1368,8 @@ __global__ __launch_bounds__(256) void gcm_wide(RaggedArgs a)
         for (uint32_t i = t; i < (uint32_t)GHASH_TAB_ENTRIES; i += 256)
             h8[i] = ((const uint4 *)ctx->tab8)[i];
     __syncthreads();
-    const bool ok = gcm_wide_record<OPEN, CT>(src, dst, a.ad + d.ad_off, d.ad_len, d.len, d.nonce, ctx,
-                                              te, sb, h8, wl, a.status ? a.status + rec : nullptr);
-    if (OPEN && !ok && !a.vf) scrub_rejected(dst, src, d.len, t, 256);
+    gcm_wide_record<OPEN, CT>(src, dst, a.ad + d.ad_off, d.ad_len, d.len, d.nonce, ctx, te, sb, h8, wl,
+                              a.status ? a.status + rec : nullptr);
 }
 
 } // namespace na

@@ -3,6 +3,14 @@
  * per-device table build, key preparation, and the choice of kernel and
  * launch shape for uniform, duplex and ragged jobs.  Called by the C-ABI
  * layer (aead_api.hip) through launch.h.
+ *
+ * UniformArgs::vf and RaggedArgs::vf are ChaChaPoly's: the AES-GCM kernels
+ * do not read them (but gcm_duplex_fused<true>, whose record body is kept as
+ * it was, aesgcm.hip gcm_staged_rec_own; vf is always set there).  Every
+ * AES-GCM open verifies first (aead_api.hip open_vf) — it authenticates,
+ * takes the verdict, then decrypts — because an AES-GCM open never writes a
+ * byte of a rejected record (cipher-aesgcm.c:184-186), so the other kernels
+ * compile no other order.
  */
 #include "launch.h"
 #include "aesgcm.hip"

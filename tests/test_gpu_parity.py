@@ -261,29 +261,14 @@ SLOT_CASES = [((1400, 1024, 512), (1400, 768, 256)), ((1400, 512, 256), (1024, 2
               ((1, 256, 256), (1400, 300, 256)), ((1400, 1000, 256), (4096, 256, 256))]
 
 
-@pytest.mark.parametrize("cipher,lanes,layout,flags", [
-    (CHACHA, 4, "fast", FLAG_ONE_PASS), (CHACHA, 8, "fast", FLAG_ONE_PASS), (CHACHA, 4, "packed", 0),
-    (AES, 0, "fast", 0), (CHACHA, 1, "fast", FLAG_ONE_PASS), (CHACHA, 1, "slot128", FLAG_ONE_PASS),
-    (CHACHA, 0, "slot128", FLAG_ONE_PASS), (CHACHA, 4, "slot128", FLAG_ONE_PASS),
-    (CHACHA, 8, "slot128", FLAG_ONE_PASS), (AES, 0, "slot128", 0),
-    (AES, 0, "slot128", FLAG_CT_GHASH), (CHACHA, 4, "slot128", FLAG_VERIFY_FIRST),
-    (AES, 0, "slot128", FLAG_VERIFY_FIRST), (CHACHA, 1, "slot128", FLAG_VERIFY_FIRST),
-    (CHACHA, 1, "fast", 0), (CHACHA, 0, "slot128", 0), (CHACHA, 4, "slot128", 0),
-    (CHACHA, 1, "slot128", FLAG_ONE_PASS | FLAG_VERIFY_FIRST)])
-def test_duplex_vs_oracle(aead, gpu, oracle, cipher, lanes, layout, flags):
-    """noise_aead_dev_duplex_uniform: seal job A and open job B (other keys,
-    nonces, length, record count; some records tampered) in one call must
-    equal the two separate calls — i.e. the oracle — byte for byte.  ChaCha
-    FAST layouts run the one-launch chachapoly_duplex_staged kernel; AES-GCM
-    with one state per 256 records runs gcm_duplex_fused (plain and CT
-    GHASH); a verify-first open (the default; VERIFY_FIRST also overrides
-    ONE_PASS) shares the launch with the one-lane ChaCha kernel (AUTH + DEC
-    passes) and the AES duplex kernels, the others run two launches.  A
-    rejected record's output is zeroed (NOISE_AEAD_FLAG_ONE_PASS opens) or
-    never written (verify-first)."""
+def duplex_cases_check(aead, oracle, cipher, cases, layout, lanes, flags, rng):
+    """One noise_aead_dev_duplex_uniform call per case, written ((len, records,
+    records per state) of the seal job, the same of the open job), checked
+    against the oracle (test_duplex_vs_oracle; tests/aes_shapes_check.py runs
+    it under the AES-GCM environment switches).  Returns the last case's
+    device buffers."""
     torch = _torch()
-    rng = np.random.default_rng(3131 + lanes + (cipher & 3) + len(layout) + flags)
-    for (La, na, rpsa), (Lb, nb_, rpsb) in (SLOT_CASES if layout == "slot128" else DUPLEX_CASES):
+    for (La, na, rpsa), (Lb, nb_, rpsb) in cases:
         def strides(L):
             if layout == "packed":
                 return L, L + 16
@@ -331,6 +316,32 @@ def test_duplex_vs_oracle(aead, gpu, oracle, cipher, lanes, layout, flags):
             else:
                 assert st[i] == 0, f"duplex open len={Lb} rec={i}"
                 assert np.array_equal(seg, ptb[i * ib: i * ib + Lb]), f"len={Lb} rec={i}"
+    return ctxa, d_nba, d_pta, d_outa, d_outb, d_st
+
+
+@pytest.mark.parametrize("cipher,lanes,layout,flags", [
+    (CHACHA, 4, "fast", FLAG_ONE_PASS), (CHACHA, 8, "fast", FLAG_ONE_PASS), (CHACHA, 4, "packed", 0),
+    (AES, 0, "fast", 0), (CHACHA, 1, "fast", FLAG_ONE_PASS), (CHACHA, 1, "slot128", FLAG_ONE_PASS),
+    (CHACHA, 0, "slot128", FLAG_ONE_PASS), (CHACHA, 4, "slot128", FLAG_ONE_PASS),
+    (CHACHA, 8, "slot128", FLAG_ONE_PASS), (AES, 0, "slot128", 0),
+    (AES, 0, "slot128", FLAG_CT_GHASH), (CHACHA, 4, "slot128", FLAG_VERIFY_FIRST),
+    (AES, 0, "slot128", FLAG_VERIFY_FIRST), (CHACHA, 1, "slot128", FLAG_VERIFY_FIRST),
+    (CHACHA, 1, "fast", 0), (CHACHA, 0, "slot128", 0), (CHACHA, 4, "slot128", 0),
+    (CHACHA, 1, "slot128", FLAG_ONE_PASS | FLAG_VERIFY_FIRST)])
+def test_duplex_vs_oracle(aead, gpu, oracle, cipher, lanes, layout, flags):
+    """noise_aead_dev_duplex_uniform: seal job A and open job B (other keys,
+    nonces, length, record count; some records tampered) in one call must
+    equal the two separate calls — i.e. the oracle — byte for byte.  ChaCha
+    FAST layouts run the one-launch chachapoly_duplex_staged kernel; AES-GCM
+    with one state per 256 records runs gcm_duplex_fused (plain and CT
+    GHASH); a verify-first open (the default; VERIFY_FIRST also overrides
+    ONE_PASS) shares the launch with the one-lane ChaCha kernel (AUTH + DEC
+    passes) and the AES duplex kernels, the others run two launches.  A
+    rejected record's output is zeroed (NOISE_AEAD_FLAG_ONE_PASS opens) or
+    never written (verify-first)."""
+    rng = np.random.default_rng(3131 + lanes + (cipher & 3) + len(layout) + flags)
+    ctxa, d_nba, d_pta, d_outa, d_outb, d_st = duplex_cases_check(
+        aead, oracle, cipher, SLOT_CASES if layout == "slot128" else DUPLEX_CASES, layout, lanes, flags, rng)
     # overlapping jobs are refused (the seal's output is the open's input)
     sj = aead.uniform_job(ctx=ctxa.data_ptr(), nonce_base=d_nba.data_ptr(), inp=d_pta.data_ptr(),
                           out=d_outa.data_ptr(), in_stride=64, out_stride=64, length=10,

@@ -292,28 +292,23 @@ __global__ __launch_bounds__(GCM_WG) void tt_ctr(const uint32_t *__restrict__ rk
 {
     const uint64_t c0 = __builtin_amdgcn_s_memtime(), r0 = __builtin_amdgcn_s_memrealtime();
     extern __shared__ __align__(16) uint8_t smem[];
-    GcmLds &L = *(GcmLds *)smem;
+    GcmLds<1> &L = *(GcmLds<1> *)smem;
     const int t = threadIdx.x;
-    for (int q = t; q < 2 * 256 * 16; q += GCM_WG) {
-        const int reg = q >> 12, row = (q >> 4) & 255, quad = q & 15;
-        const int tab = 2 * reg + (quad >> 3);
-        const uint32_t v = rotr(g_te0[row], 8 * tab);
-        ((uint4 *)&L.te[reg][row][0])[quad] = make_uint4(v, v, v, v);
-    }
-    if (t < 60) L.rk[t] = rk_g[t];
+    uint32_t *rk = L.key[0].rk;
+    te_fill<GCM_WG>(L.te);
+    if (t < 60) rk[t] = rk_g[t];
     __syncthreads();
-    const uint32_t lane = t & 63;
-    const uint32_t tpl = (1u << 16) | ((128u + 4u * (lane & 31)) << 8) | (4u * (lane & 31));
+    const uint32_t tpl = te_lane_tpl();
     const uint8_t *TE = (const uint8_t *)&L.te[0][0][0];
     const uint32_t g = blockIdx.x * GCM_WG + t;
     /* each lane: its own record nonce (n + g), counters 2 .. 2 + blocks */
     const uint64_t n = (((uint64_t)n_hi << 32) | n_lo) + g;
-    const AesPre pre = aes_pre_lds(TE, L.rk, tpl, (uint32_t)(n >> 32), (uint32_t)n);
+    const AesPre pre = aes_pre_lds(TE, rk, tpl, (uint32_t)(n >> 32), (uint32_t)n);
     uint32_t acc = 0;
 #pragma unroll 1
     for (uint32_t d = 0; d < blocks_per_lane; ++d) {
         uint32_t ks[4];
-        aes_ctr_pre(TE, L.rk, tpl, pre, 2 + d, ks);
+        aes_ctr_pre(TE, rk, tpl, pre, 2 + d, ks);
         if (mode == 0) {
             for (int w = 0; w < 4; ++w) out[((size_t)g * blocks_per_lane + d) * 4 + w] = ks[w];
         } else {
@@ -363,7 +358,7 @@ int main(int argc, char **argv)
     const size_t out_words = 64u << 20;
     CK(hipMalloc(&dout, out_words * 4)); CK(hipMalloc(&dclk, 24));
     hipLaunchKernelGGL(aes_tables_init, dim3(1), dim3(256), 0, 0);
-    CK(hipFuncSetAttribute((const void *)tt_ctr, hipFuncAttributeMaxDynamicSharedMemorySize, sizeof(GcmLds)));
+    CK(hipFuncSetAttribute((const void *)tt_ctr, hipFuncAttributeMaxDynamicSharedMemorySize, sizeof(GcmLds<1>)));
 
     /* correctness: 64 lanes x 32 blocks (bitsliced), 1024 lanes x 8 blocks (T-table) */
     {
@@ -397,7 +392,7 @@ int main(int argc, char **argv)
         printf("bitsliced two-lane check: %s (%d bad of %d)\n", bad3 ? "FAIL" : "ok", bad3, 32 * 32);
         bad += bad3;
         const uint32_t bpl = 8;
-        hipLaunchKernelGGL(tt_ctr, dim3(1), dim3(GCM_WG), sizeof(GcmLds), 0, drk, n_hi, n_lo, bpl, dout, 0, nullptr);
+        hipLaunchKernelGGL(tt_ctr, dim3(1), dim3(GCM_WG), sizeof(GcmLds<1>), 0, drk, n_hi, n_lo, bpl, dout, 0, nullptr);
         std::vector<uint32_t> t(GCM_WG * bpl * 4);
         CK(hipMemcpy(t.data(), dout, t.size() * 4, hipMemcpyDeviceToHost));
         int bad2 = 0;
@@ -460,9 +455,9 @@ int main(int argc, char **argv)
     {
         const int grid = 256 * 4; const uint32_t bpl = 256;
         const double blocks1 = (double)grid * GCM_WG * bpl;
-        for (int w = 0; w < 100; ++w) hipLaunchKernelGGL(tt_ctr, dim3(grid), dim3(GCM_WG), sizeof(GcmLds), 0, drk, n_hi, n_lo, bpl, dout, 1, nullptr);
+        for (int w = 0; w < 100; ++w) hipLaunchKernelGGL(tt_ctr, dim3(grid), dim3(GCM_WG), sizeof(GcmLds<1>), 0, drk, n_hi, n_lo, bpl, dout, 1, nullptr);
         hipEventRecord(e0);
-        for (int i = 0; i < reps; ++i) hipLaunchKernelGGL(tt_ctr, dim3(grid), dim3(GCM_WG), sizeof(GcmLds), 0, drk, n_hi, n_lo, bpl, dout, 1, dck);
+        for (int i = 0; i < reps; ++i) hipLaunchKernelGGL(tt_ctr, dim3(grid), dim3(GCM_WG), sizeof(GcmLds<1>), 0, drk, n_hi, n_lo, bpl, dout, 1, dck);
         hipEventRecord(e1);
         CK(hipEventSynchronize(e1));
         float ms; hipEventElapsedTime(&ms, e0, e1);
