@@ -5,42 +5,60 @@
  * :293-410, the call pattern of examples/echo) is one record of 1 B - 64 KiB.
  * Launching a kernel and waiting for it costs ~20 us on its own, 5x the
  * reference's whole ~4 us CPU call.  Instead, the first call on a device
- * starts ONE resident workgroup (256 threads) on a private stream; it polls
- * a request slot and serves records as they are posted.  The request (header
- * and input stream) sits in fine-grained device memory that the CPU writes
- * through the BAR where the device has a large BAR, else in pinned host
- * memory; results, status and the done word always go to pinned host memory,
- * so each side polls memory of its own and writes the other's:
+ * starts resident workgroups (256 threads each) on private streams; each
+ * polls a request slot and serves records as they are posted.  The request
+ * (header and input stream) sits in fine-grained device memory that the CPU
+ * writes through the BAR where the device has a large BAR, else in pinned
+ * host memory; results, status and the done word always go to pinned host
+ * memory, so each side polls memory of its own and writes the other's:
  *
- *   host                                    worker (aead_worker)
- *   write AD || record || tag to data[]
- *   write op, cipher, ctx, nonce, lengths
- *   seq = k        (release, system)  --->  sees seq != last (acquire, system)
- *                                           copies AD || record into LDS,
- *                                           runs the record (the same device
- *                                           code as the ragged kernels),
- *                                           writes it back, fences,
- *   spins until done == k       <------     done = k (release, system)
- *   reads status, copies out
+ *   host (na_worker_crypt)                  worker (aead_worker)
+ *   post: key || AD || record || tag
+ *         as the request's stream,
+ *         then its header, numbered k --->  poll:  sees a whole header with a
+ *                                                  new number
+ *                                           fetch: the stream (and the AES-GCM
+ *                                                  context) into LDS
+ *                                           run:   the record (the device code
+ *                                                  of the ragged kernels, or
+ *                                                  the latency-first engine)
+ *   await: spins until done == k  <------   reply: results, status, fence,
+ *                                                  done = k (release, system)
+ *   collect_and_scrub: copies out,          scrub: the record out of LDS
+ *         zeroes the shared memory
+ *
+ * The unit is three files:
+ *   worker_proto.h   the request protocol, both halves side by side: slot
+ *                    layout, chunk formats of the two placements, header,
+ *                    stop word, poison, scrub (plain C++: also checked on
+ *                    the CPU, asan/worker_proto_check.cpp)
+ *   worker_chacha.h  the latency-first ChaChaPoly engine (worker_chacha_fast
+ *                    for one-pass records, worker_chacha_multi past them)
+ *   worker.hip       the kernel loop (aead_worker, one body: poll, fetch,
+ *                    run, reply, scrub; AES-GCM records run aesgcm.hip's
+ *                    gcm_wide_record) and the host driver (groups, launch /
+ *                    park / recover, na_worker_crypt: claim_and_ensure, post,
+ *                    await, collect_and_scrub)
  *
  * The worker exits on its own after IDLE of no requests (and after at most
  * LIFETIME), or when the host sets stop; every exit path is reached by every
  * thread of the workgroup (one barrier-synchronised loop).  Before leaving it
- * sets `exiting` and looks at seq once more, so a request posted meanwhile
- * is either served or seen by the host (exiting set, done behind): the host
- * then waits for the stream and starts the worker again, which resumes at
- * the slot's `done`.
+ * sets `exiting` and looks at the header once more, so a request posted
+ * meanwhile is either served or seen by the host (exiting set, done behind):
+ * the host then waits for the stream and starts the group again, which
+ * resumes at the slot's `done`.
  *
  * Workers come in GROUPS: one kernel of S workgroups (request slots) on one
  * high-priority stream, so S calling threads share a hardware queue (a queue
  * runs nothing else while a resident kernel holds it).  A device runs one
- * group per high-priority queue but one (3 by default, the last left to the
- * application), S = ceil(8 / groups) slots each: 9 slots, one per calling
- * thread up to 9, each a workgroup on its own CU, claimed without waiting
- * while one is free.  A group leaves as a whole (aead_worker: the closing
- * word), for idleness only once all its slots are idle.  Batch launches that
- * fill every CU ask the resident groups to leave first
- * (worker_park_for_batch), so no batch workgroup waits for a worker's CU.
+ * group per high-priority queue but one (GPU_MAX_HW_QUEUES - 1: 3 by default,
+ * the last left to the application), S = ceil(8 / groups) slots each (at most
+ * WORKER_MAX_SLOTS = 4): 3 x 3 = 9 slots by default, one per calling thread
+ * up to 9, each a workgroup on its own CU, claimed without waiting while one
+ * is free.  A group leaves as a whole (aead_worker: the closing word), for
+ * idleness only once all its slots are idle.  Batch launches that fill every
+ * CU ask the resident groups to leave first (worker_park_for_batch), so no
+ * batch workgroup waits for a worker's CU.
  *
  * Key material reaches the worker through the slot as well: the ChaCha key
  * itself, or for AES-GCM a pinned host copy of the state's device context
@@ -58,439 +76,21 @@
 #include "chachapoly.hip"
 #define NA_NO_SETUP_KERNELS
 #include "aesgcm.hip"
-#include <cstddef>
-#include <emmintrin.h>
+#include "worker_proto.h"
+#include "worker_chacha.h"
 #include <cstdlib>
-#include <cstring>
 #include <atomic>
 #include <mutex>
 #include <ctime>
 
 namespace na {
 
-constexpr uint32_t WORKER_MAX_LEN = 65535 - 16; /* whole records only */
-constexpr uint32_t WORKER_MAX_AD = 256;
-/* data area: ChaCha key (32 B) || AD (padded to 16) || record || tag */
-constexpr uint32_t WORKER_DATA = 32 + WORKER_MAX_AD + 65536 + 64;
-/* The request's input stream (key || AD padded to 16 || record || tag) is
-   posted as 16-byte chunks of 12 stream bytes and the request's sequence
-   number, each written with one 16-byte store: a chunk carries its own
-   proof of freshness.  So the worker can read the first WORKER_SPEC chunks
-   speculatively with every poll of the header (4 KiB per poll, one PCIe
-   round trip for header and data together) and keep the ones stamped with
-   the new number, re-reading only stale ones. */
-constexpr uint32_t WCHUNK_BYTES = 12;
-constexpr uint32_t WORKER_SPEC = 256; /* chunks read with every poll: one per thread */
-constexpr uint32_t WORKER_HEAD = WORKER_SPEC * WCHUNK_BYTES; /* stream bytes sent as chunks */
-/* the stream past the head (records over ~3 KiB) is posted raw, read after the header */
-constexpr uint32_t WORKER_TAIL = WORKER_DATA - WORKER_HEAD;
-static_assert(WORKER_HEAD % 16 == 0, "the raw tail lands 16-B aligned in LDS");
-/* With the request in device memory the CPU's stores reach it through
-   write-combining buffers, which may write a 16-byte store as two 8-byte
-   pieces: there every 8-byte half carries the number, {4 stream bytes, seq}
-   (header chunks {seq, field, seq, field}), so a chunk is 8 stream bytes. */
-constexpr uint32_t VCHUNK_BYTES = 8;
-constexpr uint32_t VWORKER_HEAD = WORKER_SPEC * VCHUNK_BYTES;
-constexpr uint32_t VWORKER_TAIL = WORKER_DATA - VWORKER_HEAD;
 /* AES-GCM contexts the worker keeps in LDS (an echo session uses two) */
 constexpr int WORKER_CTX_SLOTS = 2;
 constexpr uint32_t WORKER_CTX_BYTES = sizeof(AesCtx); /* rk, H, the H^1..H^4 and H^8 tables */
 
-/* The request slot (host pinned, fine-grained).  The request header is four
-   16-byte chunks, each starting with the request's sequence number; the host
-   writes each chunk with one 16-byte store after the data area, and the
-   worker takes the header only when all four chunks carry the same new
-   number — one read round trip, no torn header.  The worker's words sit on
-   their own 128-B line. */
-struct alignas(128) WorkerSlot {
-    /* host -> worker */
-    uint32_t c0[4];    /* seq, op | ct << 8, len, ad_len */
-    uint32_t c1[4];    /* seq, nonce lo, nonce hi, cipher */
-    uint32_t c2[4];    /* seq, ctx lo, ctx hi, stop */
-    uint32_t c3[4];    /* seq, ctx generation, 0, 0 */
-    /* stop (word 0): its own chunk, written only by park / stop / launch —
-       never by a request's header (a header written after a
-       park used to carry stop = 0 and cancel it) */
-    uint32_t c4[4];
-    uint8_t pad0[128 - 80];
-    /* worker -> host */
-    uint64_t done;     /* last request completed */
-    uint32_t status;   /* 0 ok, 1 MAC failure, 2 input never arrived */
-    uint32_t exiting;  /* the worker is leaving (or has left) */
-    uint32_t stamps[8]; /* debug: s_memrealtime (10 ns) of the last request's phases */
-    uint32_t fstamps[8]; /* debug: s_memtime (cycles) through the latency-first path */
-    uint32_t leave[4];   /* debug: the last leave's born, now (10 ns ticks, low words), lifetime, gen */
-    uint8_t pad1[128 - 96];
-};
-static_assert(sizeof(WorkerSlot) == 256, "slot layout");
-
 #define NA_SYS_LOAD(p) __hip_atomic_load((p), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM)
 #define NA_SYS_STORE(p, v) __hip_atomic_store((p), (v), __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM)
-
-/* ---------------------------------------------- latency-first ChaChaPoly
- *
- * One record on the whole workgroup, built for the depth of its dependency
- * chains rather than its instruction count (a lone wave issues about one
- * instruction per 4.7 cycles, so depth and count both cost time):
- *  - ChaCha20 four lanes per block (quad q = block q, lane c = column c:
- *    words c, 4+c, 8+c, 12+c), the diagonal rounds by quad DPP rotations of
- *    rows b, c, d: ~330 instructions per lane instead of ~1000;
- *  - Poly1305 one 16-byte block per lane (AD blocks, CT blocks, the length
- *    block: n of them), right-justified in N = 2^ceil(log2 n) lanes, and the
- *    polynomial sum_i b_i r^(n-i) as a left-aligned tree: level L sets
- *    v_j = v_j r^L + v_{j+L} for j = 0 mod 2L (in-wave shuffles below 64,
- *    LDS for 64 and 128), then * r: log2(n) multiplies deep;
- *  - open verifies first and writes plaintext only on a match.
- * Records of up to WFAST_BLOCKS - 1 units with n <= 256 take it
- * (worker_fast_fits), longer ones worker_chacha_multi; the result equals
- * seal_il / open_il's bit for bit (the same Poly1305 value:
- * sum_i b_i r^(n-i+1) mod 2^130-5 + s). */
-constexpr uint32_t WFAST_BLOCKS = 64; /* ChaCha blocks: 4 lanes each on 256 threads */
-
-NA_DEV bool worker_fast_fits(uint32_t len, uint32_t ad_len)
-{
-    const uint32_t blocks = (len + 63) / 64 + 1;
-    const uint32_t n = (ad_len + 15) / 16 + (len + 15) / 16 + 1;
-    return blocks <= WFAST_BLOCKS && n <= 256;
-}
-
-template <int CTRL>
-NA_DEV uint32_t quad_perm(uint32_t v) { return (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, CTRL, 0xf, 0xf, false); }
-
-/* quad_perm controls: lane i of a quad reads lane perm[i] */
-constexpr int QP_NEXT1 = 0x39; /* [1,2,3,0] */
-constexpr int QP_NEXT2 = 0x4e; /* [2,3,0,1] */
-constexpr int QP_NEXT3 = 0x93; /* [3,0,1,2] */
-
-/* ChaCha20 block `ctr` on the four lanes of a quad; lane c returns words
-   c, 4+c, 8+c, 12+c of the key stream (chacha.c:74-133 layout). */
-NA_DEV void chacha_quad(const uint32_t key[8], uint32_t ctr, uint32_t n_lo, uint32_t n_hi, int c,
-                        uint32_t &oa, uint32_t &ob, uint32_t &oc, uint32_t &od)
-{
-    const uint32_t a0 = c == 0 ? 0x61707865u : c == 1 ? 0x3320646eu : c == 2 ? 0x79622d32u : 0x6b206574u;
-    const uint32_t b0 = c == 0 ? key[0] : c == 1 ? key[1] : c == 2 ? key[2] : key[3];
-    const uint32_t c0 = c == 0 ? key[4] : c == 1 ? key[5] : c == 2 ? key[6] : key[7];
-    const uint32_t d0 = c == 0 ? ctr : c == 1 ? 0u : c == 2 ? n_lo : n_hi;
-    uint32_t a = a0, b = b0, cc = c0, d = d0;
-#pragma unroll
-    for (int r = 0; r < 10; ++r) {
-        NA_QR(a, b, cc, d);                                   /* columns */
-        b = quad_perm<QP_NEXT1>(b); cc = quad_perm<QP_NEXT2>(cc); d = quad_perm<QP_NEXT3>(d);
-        NA_QR(a, b, cc, d);                                   /* diagonals */
-        b = quad_perm<QP_NEXT3>(b); cc = quad_perm<QP_NEXT2>(cc); d = quad_perm<QP_NEXT1>(d);
-    }
-    oa = a + a0; ob = b + b0; oc = cc + c0; od = d + d0;
-}
-
-/* chacha_quad for two blocks at once (blocks ctr0 and ctr1 on the same
-   quad): two independent dependency chains in one instruction stream, so a
-   lone wave's issue slots fill with the other block's work (the multi-pass
-   records' passes, two per step) */
-NA_DEV void chacha_quad_x2(const uint32_t key[8], uint32_t ctr0, uint32_t ctr1, uint32_t n_lo, uint32_t n_hi,
-                           int c, uint32_t o0[4], uint32_t o1[4])
-{
-    const uint32_t a0 = c == 0 ? 0x61707865u : c == 1 ? 0x3320646eu : c == 2 ? 0x79622d32u : 0x6b206574u;
-    const uint32_t b0 = c == 0 ? key[0] : c == 1 ? key[1] : c == 2 ? key[2] : key[3];
-    const uint32_t c0 = c == 0 ? key[4] : c == 1 ? key[5] : c == 2 ? key[6] : key[7];
-    const uint32_t d0 = c == 0 ? ctr0 : c == 1 ? 0u : c == 2 ? n_lo : n_hi;
-    const uint32_t d1 = c == 0 ? ctr1 : d0;
-    uint32_t a = a0, b = b0, cc = c0, d = d0;
-    uint32_t e = a0, f = b0, g = c0, h = d1;
-#pragma unroll
-    for (int r = 0; r < 10; ++r) {
-        NA_QR(a, b, cc, d);
-        NA_QR(e, f, g, h);
-        b = quad_perm<QP_NEXT1>(b); cc = quad_perm<QP_NEXT2>(cc); d = quad_perm<QP_NEXT3>(d);
-        f = quad_perm<QP_NEXT1>(f); g = quad_perm<QP_NEXT2>(g); h = quad_perm<QP_NEXT3>(h);
-        NA_QR(a, b, cc, d);
-        NA_QR(e, f, g, h);
-        b = quad_perm<QP_NEXT3>(b); cc = quad_perm<QP_NEXT2>(cc); d = quad_perm<QP_NEXT1>(d);
-        f = quad_perm<QP_NEXT3>(f); g = quad_perm<QP_NEXT2>(g); h = quad_perm<QP_NEXT1>(h);
-    }
-    o0[0] = a + a0; o0[1] = b + b0; o0[2] = cc + c0; o0[3] = d + d0;
-    o1[0] = e + a0; o1[1] = f + b0; o1[2] = g + c0; o1[3] = h + d1;
-}
-
-/* 16 bytes at p (16-B aligned LDS), bytes from `n` on cleared */
-NA_DEV void lds_block(const uint8_t *p, uint32_t n, uint32_t w[4])
-{
-    const uint4 v = *(const uint4 *)p;
-    w[0] = v.x; w[1] = v.y; w[2] = v.z; w[3] = v.w;
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-        const int rem = (int)n - 4 * i;
-        w[i] &= rem >= 4 ? 0xffffffffu : (rem <= 0 ? 0u : ((1u << (8 * rem)) - 1u));
-    }
-}
-
-struct FastLds {
-    uint32_t dbg[8];         /* s_memtime stamps of thread 0 (debug hook) */
-    uint32_t rs[8];          /* r, s (key stream words 0..7 of block 0) */
-    uint32_t v[4][5];        /* the tree's cross-wave partners (levels 64, 128) */
-    uint32_t verdict;
-};
-
-/* v of lane t + L (the tree's partner) for L < 64: DPP where the partner is
-   in the same row of 16 lanes, a lane shuffle otherwise */
-template <uint32_t L>
-NA_DEV uint32_t from_plus(uint32_t x, int lane)
-{
-    if constexpr (L == 1) return (uint32_t)__builtin_amdgcn_update_dpp(0, (int)x, 0xb1, 0xf, 0xf, false);  /* quad [1,0,3,2] */
-    else if constexpr (L == 2) return (uint32_t)__builtin_amdgcn_update_dpp(0, (int)x, 0x4e, 0xf, 0xf, false); /* quad [2,3,0,1] */
-    else if constexpr (L == 4) return (uint32_t)__builtin_amdgcn_update_dpp(0, (int)x, 0x104, 0xf, 0xf, false); /* row_shl:4 */
-    else if constexpr (L == 8) return (uint32_t)__builtin_amdgcn_update_dpp(0, (int)x, 0x108, 0xf, 0xf, false); /* row_shl:8 */
-    else return (uint32_t)__shfl((int)x, lane + (int)L, 64);
-}
-
-/* One level of the Poly1305 tree: lanes j = 0 mod 2L set v_j = v_j r^L + v_{j+L};
-   mP holds r^L on entry and r^(2L) on exit (when a next level exists). */
-template <uint32_t L>
-NA_DEV void tree_level(Fe &v, Mul &mP, int t, uint32_t N, FastLds &F)
-{
-    if (L >= N) return; /* uniform */
-    const int lane = t & 63;
-    Fe w;
-    if constexpr (L < 64) {
-        w.l0 = from_plus<L>(v.l0, lane);
-        w.l1 = from_plus<L>(v.l1, lane);
-        w.l2 = from_plus<L>(v.l2, lane);
-        w.l3 = from_plus<L>(v.l3, lane);
-        w.l4 = from_plus<L>(v.l4, lane);
-    } else {
-        /* partner t + L sits in another wave: through LDS */
-        if (lane == 0 && (t & (int)(2 * L - 1)) == (int)L) {
-            const int slot = t >> 6;
-            F.v[slot][0] = v.l0; F.v[slot][1] = v.l1; F.v[slot][2] = v.l2;
-            F.v[slot][3] = v.l3; F.v[slot][4] = v.l4;
-        }
-        __syncthreads();
-        const int slot = min((t + (int)L) >> 6, 3); /* receivers: 1, 2 or 3 */
-        w = Fe{F.v[slot][0], F.v[slot][1], F.v[slot][2], F.v[slot][3], F.v[slot][4]};
-        __syncthreads();
-    }
-    const Mul cur = mP;
-    if (2 * L < N) mP = mk_mul(fe_mul(mul_fe(cur), cur)); /* r^(2L), off the chain */
-    if ((t & (int)(2 * L - 1)) == 0) v = fe_carry(fe_add(fe_mul(v, cur), w));
-}
-
-/* rec: len bytes (+ the tag for open) in LDS, 16-B aligned; ad: ad_len bytes
-   (16-B aligned, padded).  256 threads, every one calls this. */
-template <bool OPEN>
-NA_DEV bool worker_chacha_fast(uint8_t *rec, const uint8_t *ad, uint32_t ad_len, uint32_t len,
-                               const uint8_t *key8, uint64_t nonce, FastLds &F)
-{
-    const int t = (int)threadIdx.x, c = t & 3;
-    const uint32_t q = (uint32_t)t >> 2; /* ChaCha block */
-    const uint64_t c00 = __builtin_amdgcn_s_memtime();
-#define NA_FSTAMP(k) do { if (t == 0) F.dbg[k] = (uint32_t)(__builtin_amdgcn_s_memtime() - c00); } while (0)
-    uint32_t key[8];
-    load_key(key8, key);
-    const uint32_t n_lo = (uint32_t)nonce, n_hi = (uint32_t)(nonce >> 32);
-    const uint32_t J = (len + 63) / 64; /* data blocks 1..J */
-    uint32_t ks[4] = {0, 0, 0, 0};
-    if (q <= J) chacha_quad(key, q, n_lo, n_hi, c, ks[0], ks[1], ks[2], ks[3]);
-    if (q == 0) { F.rs[c] = ks[0]; F.rs[4 + c] = ks[1]; }
-    NA_FSTAMP(0); /* ChaCha done (thread 0's quad) */
-    /* data words 64(q-1) + 4c + 16i, i = 0..3: key stream word 4i + c */
-    uint32_t pt[4] = {0, 0, 0, 0};
-    if (q >= 1 && q <= J) {
-        uint32_t *w = (uint32_t *)(rec + 64 * (q - 1) + 4 * c);
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            pt[i] = w[4 * i] ^ ks[i];
-            if (!OPEN) w[4 * i] = pt[i]; /* CT; bytes past len are overwritten by the tag */
-        }
-    }
-    __syncthreads();
-    NA_FSTAMP(1); /* CT in LDS, r and s published */
-    /* Poly1305 block of this lane, right-justified in N lanes */
-    const uint32_t a = (ad_len + 15) / 16, m = (len + 15) / 16, n = a + m + 1;
-    const uint32_t N = n <= 1 ? 1u : 1u << (32 - __builtin_clz(n - 1));
-    const int i = t - (int)(N - n);
-    Fe v = fe_zero();
-    if (i >= 0 && (uint32_t)i < n) {
-        uint32_t b[4];
-        if ((uint32_t)i < a) {
-            lds_block(ad + 16 * i, ad_len - 16 * i, b);
-        } else if ((uint32_t)i < a + m) {
-            const uint32_t j = (uint32_t)i - a;
-            lds_block(rec + 16 * j, len - 16 * j, b);
-        } else {
-            b[0] = ad_len; b[1] = 0; b[2] = len; b[3] = 0;
-        }
-        fe_add_block(v, b[0], b[1], b[2], b[3]);
-    }
-    const Fe r = fe_clamp_r(F.rs[0], F.rs[1], F.rs[2], F.rs[3]);
-    Mul mP = mk_mul(r); /* r^L */
-    NA_FSTAMP(2); /* Poly block loaded */
-    /* levels 1..8 by DPP (quad swaps, row shifts), 16 and 32 by lane
-       shuffles, 64 and 128 through LDS; each level a uniform branch on N */
-    tree_level<1>(v, mP, t, N, F);
-    tree_level<2>(v, mP, t, N, F);
-    tree_level<4>(v, mP, t, N, F);
-    tree_level<8>(v, mP, t, N, F);
-    tree_level<16>(v, mP, t, N, F);
-    tree_level<32>(v, mP, t, N, F);
-    tree_level<64>(v, mP, t, N, F);
-    tree_level<128>(v, mP, t, N, F);
-    NA_FSTAMP(3); /* tree done */
-    /* thread 0: the tag; every lane of the group got the same tree, so
-       only thread 0's value is the sum */
-    if (t == 0) {
-        v = fe_mul(v, mk_mul(r));
-        const uint32_t s[4] = {F.rs[4], F.rs[5], F.rs[6], F.rs[7]};
-        uint32_t tag[4];
-        fe_finish(v, s, tag);
-        if (OPEN) {
-            uint32_t got[4];
-            load16(rec + len, 16, got);
-            F.verdict = tag_equal(tag, got) ? 1u : 0u;
-        } else {
-            store16(rec + len, 16, tag);
-        }
-    }
-    NA_FSTAMP(4); /* tag */
-    if (!OPEN) return true;
-    __syncthreads();
-    const bool ok = F.verdict != 0;
-    if (ok && q >= 1 && q <= J) {
-        uint32_t *w = (uint32_t *)(rec + 64 * (q - 1) + 4 * c);
-#pragma unroll
-        for (int i2 = 0; i2 < 4; ++i2) w[4 * i2] = pt[i2]; /* bytes past len: not copied out */
-    }
-    NA_FSTAMP(5);
-#undef NA_FSTAMP
-    return ok;
-}
-
-/* Records past one pass (more than 63 units, or a Poly1305 input of more
-   than 256 blocks): the same layout over P = ceil((J + 1) / 64) ChaCha
-   passes, and G = ceil(n / 256) Poly1305 blocks per lane — lane j runs
-   Horner with r over its G consecutive blocks (right-justified chunks),
-   then the tree of worker_chacha_fast sums the chunks with unit R = r^G:
-     poly = (sum_j h_j R^(NL-1-j)) r,  h_j = sum_k b_(jG+k-pad) r^(G-1-k),
-   which is sum_i b_i r^(n-i+1) again.  Seal XORs each pass into the record
-   in LDS, then authenticates the ciphertext; open authenticates first (pass
-   0 for r and s) and decrypts only a verified record.  A separate
-   instantiation, so records of one pass keep worker_chacha_fast unchanged
-   (round 3 measured a merged version costing them 0.3-0.8 us). */
-/* XOR the key stream of blocks 1..J into the record in LDS: pass p holds
-   blocks 64p + q (pass 0's key stream, ks0, computed already); the other
-   passes two at a time (chacha_quad_x2) */
-NA_DEV void multi_xor_one(uint8_t *rec, uint32_t v, uint32_t J, int c, const uint32_t ks[4])
-{
-    if (v >= 1 && v <= J) {
-        uint32_t *w = (uint32_t *)(rec + 64 * (v - 1) + 4 * c);
-#pragma unroll
-        for (int i = 0; i < 4; ++i) w[4 * i] ^= ks[i];
-    }
-}
-
-NA_DEV void multi_xor_passes(uint8_t *rec, const uint32_t key[8], uint32_t n_lo, uint32_t n_hi, int c, uint32_t q,
-                             uint32_t J, uint32_t P, const uint32_t ks0[4])
-{
-    multi_xor_one(rec, q, J, c, ks0);
-    for (uint32_t p = 1; p < P; p += 2) {
-        const uint32_t v0 = 64 * p + q, v1 = v0 + 64;
-        uint32_t k0[4], k1[4];
-        if (p + 1 < P) { /* uniform */
-            chacha_quad_x2(key, v0, v1, n_lo, n_hi, c, k0, k1);
-            multi_xor_one(rec, v0, J, c, k0);
-            multi_xor_one(rec, v1, J, c, k1);
-        } else {
-            chacha_quad(key, v0, n_lo, n_hi, c, k0[0], k0[1], k0[2], k0[3]);
-            multi_xor_one(rec, v0, J, c, k0);
-        }
-    }
-}
-
-template <bool OPEN>
-NA_DEV bool worker_chacha_multi(uint8_t *rec, const uint8_t *ad, uint32_t ad_len, uint32_t len,
-                                const uint8_t *key8, uint64_t nonce, FastLds &F)
-{
-    const int t = (int)threadIdx.x, c = t & 3;
-    const uint32_t q = (uint32_t)t >> 2;
-    const uint64_t c00 = __builtin_amdgcn_s_memtime();
-#define NA_FSTAMP(k) do { if (t == 0) F.dbg[k] = (uint32_t)(__builtin_amdgcn_s_memtime() - c00); } while (0)
-    uint32_t key[8];
-    load_key(key8, key);
-    const uint32_t n_lo = (uint32_t)nonce, n_hi = (uint32_t)(nonce >> 32);
-    const uint32_t J = (len + 63) / 64, P = (J + 1 + 63) / 64; /* blocks 0..J in P passes */
-    /* ChaCha pass p: block v = 64p + q; data words 64(v-1) + 4c + 16i */
-    uint32_t ks0[4] = {0, 0, 0, 0}; /* pass 0 (open: XORed after the verdict) */
-    chacha_quad(key, q, n_lo, n_hi, c, ks0[0], ks0[1], ks0[2], ks0[3]);
-    if (q == 0) { F.rs[c] = ks0[0]; F.rs[4 + c] = ks0[1]; }
-    if (!OPEN) multi_xor_passes(rec, key, n_lo, n_hi, c, q, J, P, ks0); /* CT; bytes past len: the tag overwrites */
-    __syncthreads();
-    NA_FSTAMP(0); /* seal: CT in LDS; both: r and s published */
-    const uint32_t a = (ad_len + 15) / 16, m = (len + 15) / 16, n = a + m + 1;
-    const uint32_t G = (n + 255) / 256, NL = (n + G - 1) / G, pad = NL * G - n;
-    const uint32_t N = NL <= 1 ? 1u : 1u << (32 - __builtin_clz(NL - 1));
-    const int j = t - (int)(N - NL); /* this lane's chunk */
-    const Fe r = fe_clamp_r(F.rs[0], F.rs[1], F.rs[2], F.rs[3]);
-    const Mul mr = mk_mul(r);
-    Fe h = fe_zero();
-    if (j >= 0 && (uint32_t)j < NL) {
-        for (uint32_t k = 0; k < G; ++k) {
-            const int idx = j * (int)G + (int)k - (int)pad; /* 0-based block of the Poly input */
-            if (idx < 0) continue;                          /* leading padding of chunk 0 */
-            uint32_t b[4];
-            const uint32_t i = (uint32_t)idx;
-            if (i < a) {
-                lds_block(ad + 16 * i, ad_len - 16 * i, b);
-            } else if (i < a + m) {
-                const uint32_t jj = i - a;
-                lds_block(rec + 16 * jj, len - 16 * jj, b);
-            } else {
-                b[0] = ad_len; b[1] = 0; b[2] = len; b[3] = 0;
-            }
-            h = fe_mul(h, mr);
-            fe_add_block(h, b[0], b[1], b[2], b[3]);
-        }
-    }
-    NA_FSTAMP(1); /* chunks' Horner done */
-    /* R = r^G (G <= 17), square-and-multiply, the same in every lane */
-    Fe R = r;
-    {
-        const int top = 31 - __builtin_clz(G);
-        for (int bit = top - 1; bit >= 0; --bit) {
-            R = fe_mul(R, mk_mul(R));
-            if ((G >> bit) & 1u) R = fe_mul(R, mr);
-        }
-    }
-    Mul mP = mk_mul(R);
-    Fe vv = h;
-    tree_level<1>(vv, mP, t, N, F);
-    tree_level<2>(vv, mP, t, N, F);
-    tree_level<4>(vv, mP, t, N, F);
-    tree_level<8>(vv, mP, t, N, F);
-    tree_level<16>(vv, mP, t, N, F);
-    tree_level<32>(vv, mP, t, N, F);
-    tree_level<64>(vv, mP, t, N, F);
-    tree_level<128>(vv, mP, t, N, F);
-    NA_FSTAMP(2); /* tree done */
-    if (t == 0) {
-        vv = fe_mul(vv, mr);
-        const uint32_t s[4] = {F.rs[4], F.rs[5], F.rs[6], F.rs[7]};
-        uint32_t tag[4];
-        fe_finish(vv, s, tag);
-        if (OPEN) {
-            uint32_t got[4];
-            load16(rec + len, 16, got);
-            F.verdict = tag_equal(tag, got) ? 1u : 0u;
-        } else {
-            store16(rec + len, 16, tag);
-        }
-    }
-    NA_FSTAMP(3); /* tag */
-    if (!OPEN) return true;
-    __syncthreads();
-    const bool ok = F.verdict != 0;
-    if (ok) multi_xor_passes(rec, key, n_lo, n_hi, c, q, J, P, ks0); /* decrypt the verified record in LDS */
-    NA_FSTAMP(4);
-#undef NA_FSTAMP
-    return ok;
-}
 
 /* One 16-byte system-coherent load (a single request: the chunk is read
    whole, never half before and half after the host's 16-byte store). */
@@ -540,7 +140,7 @@ constexpr uint64_t POLL_BACKOFF = 2000;
 constexpr int WORKER_MAX_SLOTS = 4;
 struct WorkerSlotArgs {
     WorkerSlot *slot;      /* device view of the slot */
-    const uint32_t *req;   /* the header chunks (4 in host memory; 8 in device memory, vram) */
+    const uint32_t *req;   /* the header chunks and the stop chunk */
     const uint4 *in;       /* the stream's stamped chunks */
     const uint8_t *tail;   /* the rest of the stream, raw */
     uint8_t *out;          /* results */
@@ -569,7 +169,7 @@ __global__ __launch_bounds__(256) void aead_worker(WorkerArgs a)
     /* the last request served on this slot (a relaunched group starts where
        the one before it stopped: a request it left unserved is served) */
     uint32_t last = (uint32_t)NA_SYS_LOAD(&slot->done);
-    const uint32_t head = vram ? VWORKER_HEAD : WORKER_HEAD, cbytes = vram ? VCHUNK_BYTES : WCHUNK_BYTES;
+    const Placement p = placement(vram);
     __shared__ uint32_t te[256], sb[256];
     __shared__ __attribute__((aligned(16))) uint8_t cbuf[WORKER_CTX_SLOTS][WORKER_CTX_BYTES];
     __shared__ uint64_t ctag[WORKER_CTX_SLOTS]; /* host address of the cached context */
@@ -611,33 +211,26 @@ __global__ __launch_bounds__(256) void aead_worker(WorkerArgs a)
            A wave may see the previous poll's setting: both are correct. */
         uint4 c = make_uint4(0, 0, 0, 0), mine = make_uint4(0, 0, 0, 0);
         /* lanes 14 and 15 of every 16 read the group words instead */
-        const uint32_t *hp = (t & 15) >= 14 ? a.group + 4 * (t & 1) : req + 4 * (t & (vram ? 15 : 7));
+        const uint32_t *hp = (t & 15) >= 14 ? a.group + 4 * (t & 1) : poll_chunk(vram != 0, req, t);
         if (!s_slow) load_sys16x2(hp, (const uint32_t *)(in + t), c, mine);
         else if (t < 64) c = load_sys16(hp);
         if (t == 0) s_stale = 0;
         if (t < 64) {
-            const uint32_t s0 = __shfl((int)c.x, 0, 64);
+            /* the header is taken when all its chunks carry one new number
+               (worker_proto.h: 4 chunks in host memory, 8 in device memory) */
+            const uint32_t s0 = __shfl((int)hdr_seq(c), 0, 64);
             uint32_t stop;
             bool fresh;
-            if (!vram) { /* chunk k = {seq, A_k, B_k, C_k} */
-                const uint32_t s1 = __shfl((int)c.x, 1, 64);
-                const uint32_t s2 = __shfl((int)c.x, 2, 64), s3 = __shfl((int)c.x, 3, 64);
-                stop = __shfl((int)c.x, 4, 64); /* chunk 4: the stop word */
+            if (!vram) {
+                const uint32_t s1 = __shfl((int)hdr_seq(c), 1, 64);
+                const uint32_t s2 = __shfl((int)hdr_seq(c), 2, 64), s3 = __shfl((int)hdr_seq(c), 3, 64);
+                stop = __shfl((int)stop_of(c), (int)placement(false).stop_chunk, 64);
                 fresh = s0 != last && s0 == s1 && s0 == s2 && s0 == s3;
-                if (t < 4) {
-                    hdr[4 * t] = c.x; hdr[4 * t + 1] = c.y; hdr[4 * t + 2] = c.z; hdr[4 * t + 3] = c.w;
-                }
-            } else { /* chunk 2k = {seq, A_k, seq, B_k}, 2k + 1 = {seq, C_k, seq, 0} */
-                stop = __shfl((int)c.x, 8, 64); /* chunk 8: the stop word */
-                fresh = s0 != last && __all(t >= 8 || (c.x == s0 && c.z == s0));
-                if (t < 8) {
-                    const uint32_t k = t >> 1;
-                    if (t & 1) {
-                        hdr[4 * k + 3] = c.y;
-                    } else {
-                        hdr[4 * k] = c.x; hdr[4 * k + 1] = c.y; hdr[4 * k + 2] = c.w;
-                    }
-                }
+                if (t < placement(false).hdr_chunks) hdr_unpack(false, c, t, hdr);
+            } else {
+                stop = __shfl((int)stop_of(c), (int)placement(true).stop_chunk, 64);
+                fresh = s0 != last && __all(t >= placement(true).hdr_chunks || hdr_stamped(true, c, s0));
+                if (t < placement(true).hdr_chunks) hdr_unpack(true, c, t, hdr);
             }
             /* the group words: closing, then the slots' last-request times */
             const bool closing = (uint32_t)__shfl((int)c.x, 14, 64) == a.gen;
@@ -690,34 +283,37 @@ __global__ __launch_bounds__(256) void aead_worker(WorkerArgs a)
         /* serve request hdr[0]: the data area was written before the header;
            the acquire orders the reads below after the header's */
         __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "");
-        const uint32_t seq = hdr[0], op = hdr[1] & 0xff, ct = (hdr[1] >> 8) & 1;
-        const uint32_t len = hdr[2], ad_len = hdr[3];
-        const uint64_t nonce = (uint64_t)hdr[5] | ((uint64_t)hdr[6] << 32);
-        const uint32_t cipher = hdr[7];
-        const uint64_t ctx_addr = (uint64_t)hdr[9] | ((uint64_t)hdr[10] << 32);
-        const uint32_t gen = hdr[13];
-        const uint32_t ad_pad = (ad_len + 15) & ~15u;
+        const uint32_t seq = request_seq(hdr);
+        const Request rq = request_of(hdr);
+        const uint32_t op = rq.op, ct = rq.ct, len = rq.len, ad_len = rq.ad_len, cipher = rq.cipher, gen = rq.gen;
+        const uint64_t nonce = rq.nonce, ctx_addr = rq.ctx;
+        const uint32_t ad_pad = pad16(ad_len);
         const uint32_t bytes = 32 + ad_pad + len + 16;
         const uint32_t t_fence = now10ns();
         /* the input stream: the head as stamped chunks (chunk t read
            speculatively with the poll, re-read while stale), the rest raw
-           (written before the header, read after it) */
+           (written before the header, read after it).  Three rules of
+           worker_proto.h are restated here, not called — stream_total (total),
+           chunk_fresh (the stamp test) and chunk_unpack (d[]): calling them
+           assembled differently from the text below, which is the measured
+           one; asan/worker_proto_check.cpp checks the
+           rules, so a change there must be made here too */
         const uint32_t total = 32 + ad_pad + len + (op ? 16u : 0u);
-        const uint32_t nchunks = min((total + cbytes - 1) / cbytes, WORKER_SPEC);
+        const uint32_t nchunks = stream_chunks(p, total);
         if (t < nchunks) {
             uint4 v = mine;
             for (uint32_t tries = 0; (v.w != seq || (vram && v.y != seq)) && tries < (1u << 20); ++tries)
                 v = load_sys16((const uint32_t *)(in + t));
             if (v.w != seq || (vram && v.y != seq)) s_stale = 1; /* never in practice: written before the header */
-            uint32_t *d = (uint32_t *)(buf + cbytes * t);
+            uint32_t *d = (uint32_t *)(buf + p.chunk_bytes * t);
             if (vram) {
                 d[0] = v.x; d[1] = v.z;
             } else {
                 d[0] = v.x; d[1] = v.y; d[2] = v.z;
             }
         }
-        for (uint32_t o = 16 * t; head + o < total; o += 16 * 256)
-            *(uint4 *)(buf + head + o) = load_sys16_raw(tail + o);
+        for (uint32_t o = 16 * t; p.head + o < total; o += 16 * 256)
+            *(uint4 *)(buf + p.head + o) = load_sys16_raw(tail + o);
         int cs = 0;
         if (cipher == NOISE_CIPHER_AESGCM) { /* the context: cached, or copied into the LRU slot */
             cs = ctag[0] == ctx_addr && cgen[0] == gen ? 0 : (ctag[1] == ctx_addr && cgen[1] == gen ? 1 : -1);
@@ -851,6 +447,21 @@ struct WorkerGroup {
 constexpr int kMaxDev = 64;
 constexpr int kMaxGroups = 8;
 
+/* The environment switches: each read once, by its getter's static.
+   env_flag: a switch that is on by default goes off with "0", one that is
+   off goes on with "1"; env_int: a positive number, else dflt. */
+bool env_flag(const char *name, bool on)
+{
+    const char *e = getenv(name);
+    return e ? (on ? e[0] != '0' : e[0] == '1') : on;
+}
+
+int env_int(const char *name, int dflt)
+{
+    const char *e = getenv(name);
+    return e && atoi(e) > 0 ? atoi(e) : dflt;
+}
+
 /* A resident group never ends while calls keep coming (up to LIFETIME), so
    it must own its hardware queue: a kernel queued behind it on the same AQL
    queue waits for it to leave.  HIP maps streams onto GPU_MAX_HW_QUEUES
@@ -874,18 +485,11 @@ int worker_stream_prio()
     return v;
 }
 
-int hw_queues()
-{
-    const char *e = getenv("GPU_MAX_HW_QUEUES");
-    const int q = e ? atoi(e) : 4;
-    return q < 1 ? 4 : q;
-}
-
 int groups_per_dev()
 {
     static const int v = [] {
-        const char *e = getenv("NOISE_AEAD_WORKER_QUEUES");
-        int g = e && atoi(e) > 0 ? atoi(e) : (hw_queues() > 1 ? hw_queues() - 1 : 1);
+        const int q = env_int("GPU_MAX_HW_QUEUES", 4);
+        const int g = env_int("NOISE_AEAD_WORKER_QUEUES", q > 1 ? q - 1 : 1);
         return g < kMaxGroups ? g : kMaxGroups;
     }();
     return v;
@@ -899,8 +503,7 @@ int groups_per_dev()
 int slots_per_group()
 {
     static const int v = [] {
-        const char *e = getenv("NOISE_AEAD_WORKER_SLOTS");
-        int s = e && atoi(e) > 0 ? atoi(e) : (8 + groups_per_dev() - 1) / groups_per_dev();
+        const int s = env_int("NOISE_AEAD_WORKER_SLOTS", (8 + groups_per_dev() - 1) / groups_per_dev());
         return s < WORKER_MAX_SLOTS ? s : WORKER_MAX_SLOTS;
     }();
     return v;
@@ -916,11 +519,8 @@ constexpr uint64_t IDLE_TICKS = 200000;       /* 2 ms at 100 MHz */
 /* Test hook: NOISE_AEAD_DEBUG_WORKER_IDLE_MS overrides the idle timeout. */
 uint64_t idle_ticks()
 {
-    static const uint64_t v = [] {
-        const char *e = getenv("NOISE_AEAD_DEBUG_WORKER_IDLE_MS");
-        return e && atoi(e) > 0 ? (uint64_t)atoi(e) * 100000ull : IDLE_TICKS;
-    }();
-    return v;
+    static const int ms = env_int("NOISE_AEAD_DEBUG_WORKER_IDLE_MS", 0);
+    return ms ? (uint64_t)ms * 100000ull : IDLE_TICKS;
 }
 constexpr uint64_t LIFETIME_TICKS = 500000000; /* 5 s */
 /* The longest request (a 65519-B AES-GCM record) takes ~0.4 ms; a group
@@ -928,15 +528,10 @@ constexpr uint64_t LIFETIME_TICKS = 500000000; /* 5 s */
    the launch path and the group is drained before it is used again. */
 constexpr uint64_t WAIT_LIMIT_NS = 2000000000ull; /* 2 s */
 
-/* the stop word: chunk 4 of the host slot, chunk 8 of the device request
-   area — a chunk of its own, apart from the request header the calls
-   rewrite */
-uint32_t *stop_word(Worker &w) { return w.vram ? &w.req[4 * 8] : &w.req[4 * 4]; }
-
 void set_stops(WorkerGroup &g, uint32_t v)
 {
     for (int i = 0; i < g.nslots; ++i)
-        if (g.slot[i].state == 1) __atomic_store_n(stop_word(g.slot[i]), v, __ATOMIC_RELEASE);
+        if (g.slot[i].state == 1) __atomic_store_n(stop_word(g.slot[i].vram, g.slot[i].req), v, __ATOMIC_RELEASE);
     _mm_sfence();
 }
 
@@ -989,13 +584,19 @@ void worker_abandon(Worker &w, uint32_t k)
        lock: a caller holding it may be waiting in group_launch for this very
        group to leave */
     set_stops(g, 1u);
-    const uint32_t bad = k ^ 0x80000000u;
-    const __m128i c = w.vram ? _mm_set_epi32(0, (int)bad, 0, (int)bad) : _mm_set_epi32(0, 0, 0, (int)bad);
-    _mm_store_si128((__m128i *)w.req, c);
+    poison_header(w.vram, w.req, k);
     _mm_sfence();
     std::lock_guard<std::mutex> gl(g.mu);
     g.abandoned |= 1u << (int)(&w - g.slot);
     g.state = -2;
+}
+
+/* (under g.mu, the group's stream idle) the result areas of the slots whose
+   request was abandoned, in case a late workgroup wrote them */
+void scrub_abandoned(WorkerGroup &g)
+{
+    for (int i = 0; i < g.nslots; ++i)
+        if (g.abandoned & (1u << i)) explicit_bzero(g.slot[i].out, WORKER_DATA);
 }
 
 /* (under g.mu) a drained group whose stream has gone idle: the abandoned
@@ -1003,8 +604,7 @@ void worker_abandon(Worker &w, uint32_t k)
 void worker_recover(WorkerGroup &g)
 {
     if (g.state != -2 || hipStreamQuery(g.stream) != hipSuccess) return;
-    for (int i = 0; i < g.nslots; ++i)
-        if (g.abandoned & (1u << i)) explicit_bzero(g.slot[i].out, WORKER_DATA);
+    scrub_abandoned(g);
     g.abandoned = 0;
     __atomic_store_n(&g.launched, false, __ATOMIC_RELEASE);
     g.state = 1;
@@ -1019,19 +619,15 @@ void worker_stop_all()
             if ((g.state != 1 && g.state != -2) || !g.launched) continue;
             set_stops(g, 1u);
             (void)hipStreamSynchronize(g.stream);
-            for (int s = 0; s < g.nslots; ++s) /* a late workgroup's results */
-                if (g.abandoned & (1u << s)) explicit_bzero(g.slot[s].out, WORKER_DATA);
+            scrub_abandoned(g);
             __atomic_store_n(&g.launched, false, __ATOMIC_RELEASE);
         }
 }
 
 bool worker_enabled()
 {
-    static const int v = [] {
-        const char *e = getenv("NOISE_AEAD_WORKER");
-        return e && e[0] == '0' ? 0 : 1;
-    }();
-    return v != 0;
+    static const bool v = env_flag("NOISE_AEAD_WORKER", true);
+    return v;
 }
 
 /* The request goes to device memory when the CPU can store to it (a large
@@ -1042,8 +638,7 @@ bool worker_enabled()
    it in host memory. */
 bool vram_wanted(int dev)
 {
-    const char *e = getenv("NOISE_AEAD_WORKER_VRAM");
-    if (e && e[0] == '0') return false;
+    if (!env_flag("NOISE_AEAD_WORKER_VRAM", true)) return false;
     int large_bar = 0;
     return hipDeviceGetAttribute(&large_bar, hipDeviceAttributeIsLargeBar, dev) == hipSuccess && large_bar;
 }
@@ -1052,7 +647,8 @@ int slot_setup(Worker &w, int dev)
 {
     if (w.state) return w.state;
     w.state = -1;
-    const size_t in_bytes = (size_t)WORKER_SPEC * 16, tail_bytes = WORKER_TAIL + 64;
+    /* the worker reads the raw tail in 16-byte pieces: 64 bytes of slack */
+    const size_t in_bytes = WORKER_IN_BYTES, tail_bytes = worker_tail_bytes(false) + 64;
     const size_t total = sizeof(WorkerSlot) + in_bytes + tail_bytes + WORKER_DATA;
     if (hipHostMalloc((void **)&w.slot, total, hipHostMallocMapped | hipHostMallocCoherent) != hipSuccess)
         return -1;
@@ -1066,16 +662,16 @@ int slot_setup(Worker &w, int dev)
     w.dout = w.dtail + tail_bytes;
     w.req = w.slot->c0;
     w.dreq = w.dslot->c0;
-    /* device-memory request: 8 header chunks and the stop chunk (256 B), the
+    /* device-memory request: the polled request area (worker_proto.h), the
        stamped chunks, then the raw tail */
-    const size_t vbytes = 256 + in_bytes + VWORKER_TAIL + 64;
+    const size_t vbytes = worker_req_area(true) + in_bytes + worker_tail_bytes(true) + 64;
     if (vram_wanted(dev) && hipExtMallocWithFlags(&w.vbase, vbytes, hipDeviceMallocFinegrained) == hipSuccess) {
         memset(w.vbase, 0, vbytes); /* through the BAR mapping */
         _mm_sfence();
         w.vram = true;
         w.req = (uint32_t *)w.vbase;
         w.dreq = (const uint32_t *)w.vbase;
-        w.in = w.din = (uint4 *)((uint8_t *)w.vbase + 256);
+        w.in = w.din = (uint4 *)((uint8_t *)w.vbase + worker_req_area(true));
         w.tail = w.dtail = (uint8_t *)(w.in + WORKER_SPEC);
     }
     w.state = 1;
@@ -1124,10 +720,7 @@ int group_setup(WorkerGroup &g, int dev)
    (tests/test_gpu_worker.py: the calls must then take the launch path). */
 bool debug_launch_fails()
 {
-    static const bool v = [] {
-        const char *e = getenv("NOISE_AEAD_DEBUG_WORKER_FAIL");
-        return e && e[0] == '1';
-    }();
+    static const bool v = env_flag("NOISE_AEAD_DEBUG_WORKER_FAIL", false);
     return v;
 }
 
@@ -1137,10 +730,7 @@ bool debug_launch_fails()
    tests/worker_mode_check.py --relaunch-free). */
 bool debug_leave_before_post()
 {
-    static const bool v = [] {
-        const char *e = getenv("NOISE_AEAD_DEBUG_WORKER_LEAVE");
-        return e && e[0] == '1';
-    }();
+    static const bool v = env_flag("NOISE_AEAD_DEBUG_WORKER_LEAVE", false);
     return v;
 }
 
@@ -1148,10 +738,7 @@ bool debug_leave_before_post()
    A/B of tests/test_gpu_worker.py's batch-beside-worker measurement). */
 bool park_enabled()
 {
-    static const bool v = [] {
-        const char *e = getenv("NOISE_AEAD_WORKER_PARK");
-        return !(e && e[0] == '0');
-    }();
+    static const bool v = env_flag("NOISE_AEAD_WORKER_PARK", true);
     return v;
 }
 
@@ -1170,7 +757,7 @@ int group_launch(WorkerGroup &g, Worker &own)
     for (int i = 0; i < g.nslots; ++i) {
         Worker &w = g.slot[i];
         __atomic_store_n(&w.slot->exiting, 0u, __ATOMIC_RELEASE);
-        __atomic_store_n(stop_word(w), 0u, __ATOMIC_RELEASE);
+        __atomic_store_n(stop_word(w.vram, w.req), 0u, __ATOMIC_RELEASE);
         /* a fresh group caches nothing: the history restarts for slots not
            in a call (a slot in a call may be noting a context right now) */
         if (&w == &own) {
@@ -1268,8 +855,135 @@ Worker *claim_worker(int dev, std::unique_lock<std::mutex> &lk)
 
 int g_cus[kMaxDev]; /* compute units per device (0: not read yet) */
 
-} // namespace
+/* the current device, or -1 (none, or past the tables here) */
+int current_dev()
+{
+    int dev = 0;
+    return hipGetDevice(&dev) == hipSuccess && dev >= 0 && dev < kMaxDev ? dev : -1;
+}
 
+bool ct_env()
+{
+    static const bool v = env_flag("NOISE_AEAD_CT_GHASH", false);
+    return v;
+}
+
+/* host-side phase times of the last request (ns, CLOCK_MONOTONIC): packed,
+   doorbell written, done seen, returned — relative to the call's start */
+thread_local uint64_t t_host[4];
+inline uint64_t host_ns()
+{
+    struct timespec ts;
+    clock_gettime(CLOCK_MONOTONIC, &ts);
+    return (uint64_t)ts.tv_sec * 1000000000ull + (uint64_t)ts.tv_nsec;
+}
+
+/* A slot of device dev, locked (lk), its group running; ctx: the device
+   address of h_ctx.  Nothing is posted yet when this fails. */
+int claim_and_ensure(int dev, const void *h_ctx, std::unique_lock<std::mutex> &lk, Worker *&wp, uint64_t &ctx)
+{
+    wp = claim_worker(dev, lk);
+    if (!wp) return NOISE_ERROR_NOT_APPLICABLE;
+    Worker &w = *wp;
+    t_last = wp;
+    void *d_hctx = nullptr;
+    if (h_ctx && hipHostGetDevicePointer(&d_hctx, (void *)h_ctx, 0) != hipSuccess)
+        return NOISE_ERROR_NOT_APPLICABLE;
+    ctx = (uint64_t)(uintptr_t)d_hctx;
+    WorkerGroup &g = *w.g;
+    {   /* the generation first, then launched / exiting (group_ensure) */
+        const uint32_t gen0 = __atomic_load_n(&g.gen, __ATOMIC_ACQUIRE);
+        const bool up = __atomic_load_n(&g.launched, __ATOMIC_ACQUIRE);
+        if (!up || __atomic_load_n(&w.slot->exiting, __ATOMIC_ACQUIRE)) {
+            const int rc = group_ensure(w, gen0, up ? 1 : 0);
+            if (rc) return rc;
+        }
+    }
+    /* after the launch (which starts the history afresh): this context may
+       now sit in the workgroup's LDS cache */
+    if (h_ctx) worker_note_ctx(w, h_ctx);
+    if (debug_leave_before_post()) { /* test hook: the group leaves before k is posted */
+        park_group(g);
+        const uint64_t t0 = host_ns();
+        while ((!__atomic_load_n(&w.slot->exiting, __ATOMIC_ACQUIRE) || hipStreamQuery(g.stream) != hipSuccess) &&
+               host_ns() - t0 < 1000000000ull)
+            __builtin_ia32_pause();
+    }
+    return NOISE_ERROR_NONE;
+}
+
+/* The next request of slot w: its stream, then its header (worker_proto.h).
+   Returns its number; h1: the stream is packed. */
+uint32_t post(Worker &w, const Request &rq, const uint8_t *key, const uint8_t *ad, const uint8_t *data, uint64_t &h1)
+{
+    const uint32_t k = ++w.seq;
+    encode_stream(w.vram, (uint32_t *)w.in, w.tail, k, key, ad, rq.ad_len, data, rq.len + (rq.op ? 16u : 0u));
+    h1 = host_ns();
+    /* the data area before the header: sfence drains the write-combining
+       buffers (device memory) and orders the stores (both) */
+    _mm_sfence();
+    __atomic_thread_fence(__ATOMIC_RELEASE);
+    encode_header(w.vram, w.req, k, rq);
+    _mm_sfence(); /* out of the write-combining buffer now, not later */
+    return k;
+}
+
+/* Wait for the answer to request k, posted at h2.  A failure the worker
+   caused (a relaunch that fails, no answer within WAIT_LIMIT_NS) is
+   NOISE_ERROR_NOT_APPLICABLE: the caller runs the record through the launch
+   path with the same nonce instead — the result is the same bytes, and the
+   worker only ever writes w.out and the slot. */
+int await(Worker &w, uint32_t k, const void *h_ctx, uint64_t h2)
+{
+    WorkerSlot *s = w.slot;
+    WorkerGroup &g = *w.g;
+    uint64_t spins = 0;
+    while (__atomic_load_n(&s->done, __ATOMIC_ACQUIRE) != k) {
+        __builtin_ia32_pause();
+        if ((++spins & 1023) != 0) continue;
+        const uint32_t gen0 = __atomic_load_n(&g.gen, __ATOMIC_ACQUIRE);
+        if (__atomic_load_n(&s->exiting, __ATOMIC_ACQUIRE) && __atomic_load_n(&s->done, __ATOMIC_ACQUIRE) != k) {
+            /* the group left before this slot took k: start it again (its
+               workgroup starts at done = k - 1 and serves k) */
+            const int rc = group_ensure(w, gen0, 2);
+            if (rc) return rc;
+            /* a relaunch by group_launch starts this slot's context history
+               afresh, and the new workgroup serves k and caches h_ctx: note it
+               again, or freeing the state would not park this group and the
+               round keys would stay in its LDS (ADVICE r5) */
+            if (h_ctx) worker_note_ctx(w, h_ctx);
+        }
+        if (host_ns() - h2 > WAIT_LIMIT_NS) { /* no answer: drained, then reused */
+            worker_abandon(w, k);
+            return NOISE_ERROR_NOT_APPLICABLE;
+        }
+    }
+    return NOISE_ERROR_NONE;
+}
+
+/* The answer to request k (st: what await returned) copied out, and the
+   request scrubbed from the shared memory whatever became of it.  A stale
+   input (status 2) is the worker's failure too: NOISE_ERROR_NOT_APPLICABLE. */
+int collect_and_scrub(Worker &w, uint32_t k, const Request &rq, int st, uint8_t *data)
+{
+    if (st == NOISE_ERROR_NONE) {
+        const uint32_t status = w.slot->status;
+        st = status == 2 ? NOISE_ERROR_NOT_APPLICABLE : (status ? NOISE_ERROR_MAC_FAILURE : NOISE_ERROR_NONE);
+        if (st == NOISE_ERROR_NONE) memcpy(data, w.out, rq.op ? rq.len : rq.len + 16);
+    }
+    scrub_request(w.vram, (uint32_t *)w.in, w.tail, w.out, k, rq.op, rq.len, rq.ad_len);
+    return st;
+}
+
+/* the host view of slot `slot` of group `group` on the current device (debug hooks) */
+const WorkerSlot *debug_slot(int group, int slot)
+{
+    const int dev = current_dev();
+    if (dev < 0 || group < 0 || group >= kMaxGroups || slot < 0 || slot >= WORKER_MAX_SLOTS) return nullptr;
+    return g_group[dev][group].slot[slot].slot;
+}
+
+} // namespace
 
 extern "C" NA_HIDDEN int na_worker_enabled(void) { return worker_enabled() ? 1 : 0; }
 
@@ -1282,8 +996,8 @@ extern "C" NA_HIDDEN int na_worker_enabled(void) { return worker_enabled() ? 1 :
    would run a second generation on another CU. */
 NA_HIDDEN void worker_park_for_batch(uint32_t workgroups)
 {
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= kMaxDev) return;
+    const int dev = current_dev();
+    if (dev < 0) return;
     int cus = __atomic_load_n(&g_cus[dev], __ATOMIC_RELAXED);
     if (!cus) {
         if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus <= 0)
@@ -1309,43 +1023,12 @@ extern "C" NA_HIDDEN void na_worker_forget_ctx(const void *h_ctx)
         }
 }
 
-namespace {
-
-bool ct_env()
-{
-    static const bool v = [] {
-        const char *e = getenv("NOISE_AEAD_CT_GHASH");
-        return e && e[0] == '1';
-    }();
-    return v;
-}
-
-} // namespace
-
-/* 16-byte chunk store: one aligned SSE store, which the x86-64 hosts of
-   MI355X (AVX-capable) perform atomically, so the worker never sees half of
-   a chunk; the sequence number in every chunk catches a torn header */
-static inline void store_chunk(uint32_t *dst, uint32_t a, uint32_t b, uint32_t c, uint32_t d)
-{
-    _mm_store_si128((__m128i *)dst, _mm_set_epi32((int)d, (int)c, (int)b, (int)a));
-}
-
 /* One record through the resident worker: data holds len bytes (+ the tag
    for open) and receives CT || tag (seal) or, verified, the plaintext.  key:
    the raw ChaCha key; h_ctx / gen: AES-GCM, the pinned host copy of the
    state's context and the generation it was written at.  Returns
    NOISE_ERROR_NONE, _MAC_FAILURE, _SYSTEM, or _NOT_APPLICABLE (take the
    launch path). */
-/* host-side phase times of the last request (ns, CLOCK_MONOTONIC): packed,
-   doorbell written, done seen, returned — relative to the call's start */
-static thread_local uint64_t t_host[4];
-static inline uint64_t host_ns()
-{
-    struct timespec ts;
-    clock_gettime(CLOCK_MONOTONIC, &ts);
-    return (uint64_t)ts.tv_sec * 1000000000ull + (uint64_t)ts.tv_nsec;
-}
-
 extern "C" NA_HIDDEN int na_worker_crypt(int cipher_id, const uint8_t *key, const void *h_ctx,
                                          uint32_t gen, uint64_t nonce, const uint8_t *ad,
                                          size_t ad_len, uint8_t *data, size_t len, int open)
@@ -1354,132 +1037,27 @@ extern "C" NA_HIDDEN int na_worker_crypt(int cipher_id, const uint8_t *key, cons
     if (cipher_id == NOISE_CIPHER_AESGCM && !h_ctx) return NOISE_ERROR_NOT_APPLICABLE;
     if (!worker_enabled() || len > WORKER_MAX_LEN || ad_len > WORKER_MAX_AD)
         return NOISE_ERROR_NOT_APPLICABLE;
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= kMaxDev) return NOISE_ERROR_NOT_APPLICABLE;
+    const int dev = current_dev();
+    if (dev < 0) return NOISE_ERROR_NOT_APPLICABLE;
     std::unique_lock<std::mutex> lk;
-    Worker *wp = claim_worker(dev, lk);
-    if (!wp) return NOISE_ERROR_NOT_APPLICABLE;
-    Worker &w = *wp;
-    t_last = wp;
-    void *d_hctx = nullptr;
-    if (h_ctx && hipHostGetDevicePointer(&d_hctx, (void *)h_ctx, 0) != hipSuccess)
-        return NOISE_ERROR_NOT_APPLICABLE;
-    const size_t ad_pad = (ad_len + 15) & ~(size_t)15;
-    WorkerSlot *s = w.slot;
-    WorkerGroup &g = *w.g;
-    {   /* the generation first, then launched / exiting (group_ensure) */
-        const uint32_t gen0 = __atomic_load_n(&g.gen, __ATOMIC_ACQUIRE);
-        const bool up = __atomic_load_n(&g.launched, __ATOMIC_ACQUIRE);
-        if (!up || __atomic_load_n(&s->exiting, __ATOMIC_ACQUIRE)) {
-            const int rc = group_ensure(w, gen0, up ? 1 : 0);
-            if (rc) return rc; /* nothing posted yet */
-        }
-    }
-    /* after the launch (which starts the history afresh): this context may
-       now sit in the workgroup's LDS cache */
-    if (h_ctx) worker_note_ctx(w, h_ctx);
-    if (debug_leave_before_post()) { /* test hook: the group leaves before k is posted */
-        park_group(g);
-        const uint64_t t0 = host_ns();
-        while ((!__atomic_load_n(&s->exiting, __ATOMIC_ACQUIRE) || hipStreamQuery(g.stream) != hipSuccess) &&
-               host_ns() - t0 < 1000000000ull)
-            __builtin_ia32_pause();
-    }
-    const uint32_t k = ++w.seq;
-    /* the input stream key || AD || pad || record (|| tag): its first head
-       bytes as stamped chunks, the rest raw.  Host memory: 12 stream bytes +
-       k per chunk; device memory: {4 bytes, k, 4 bytes, k} */
-    const size_t in_len = len + (open ? 16 : 0), total = 32 + ad_pad + in_len;
-    const size_t cbytes = w.vram ? VCHUNK_BYTES : WCHUNK_BYTES;
-    const size_t hmax = w.vram ? VWORKER_HEAD : WORKER_HEAD;
-    const size_t head = total < hmax ? total : hmax;
-    const size_t nchunks = (head + cbytes - 1) / cbytes;
-    const __m128i keep = _mm_set_epi32(0, -1, -1, -1), stamp = _mm_set_epi32((int)k, 0, 0, 0);
-    const __m128i kk = _mm_set1_epi32((int)k);
-    const __m128i vstamp = _mm_set_epi32((int)k, 0, (int)k, 0); /* a scrubbed device chunk */
-    alignas(16) uint8_t tmp[WORKER_HEAD + 16];
-    memset(tmp, 0, 32 + ad_pad);
-    if (cipher_id == NOISE_CIPHER_CHACHAPOLY) memcpy(tmp, key, 32);
-    if (ad_len) memcpy(tmp + 32, ad, ad_len);
-    memcpy(tmp + 32 + ad_pad, data, head - 32 - ad_pad);
-    memset(tmp + head, 0, 16); /* the last chunk's bytes past the stream */
-    if (w.vram) {
-        for (size_t c = 0; c < nchunks; ++c) {
-            const __m128i v = _mm_loadl_epi64((const __m128i *)(tmp + VCHUNK_BYTES * c));
-            _mm_store_si128((__m128i *)(w.in + c), _mm_unpacklo_epi32(v, kk)); /* {b0, k, b1, k} */
-        }
-    } else {
-        for (size_t c = 0; c < nchunks; ++c) {
-            const __m128i v = _mm_loadu_si128((const __m128i *)(tmp + WCHUNK_BYTES * c));
-            _mm_store_si128((__m128i *)(w.in + c), _mm_or_si128(_mm_and_si128(v, keep), stamp));
-        }
-    }
-    explicit_bzero(tmp, head);
-    if (total > head) memcpy(w.tail, data + (head - 32 - ad_pad), total - head);
-    const uint64_t ctx = (uint64_t)(uintptr_t)d_hctx;
-    const uint64_t h1 = host_ns();
-    /* the data area before the header: sfence drains the write-combining
-       buffers (device memory) and orders the stores (both) */
-    _mm_sfence();
-    __atomic_thread_fence(__ATOMIC_RELEASE);
-    const uint32_t f[4][3] = {{(open ? 1u : 0u) | (ct_env() ? 1u << 8 : 0u), (uint32_t)len, (uint32_t)ad_len},
-                              {(uint32_t)nonce, (uint32_t)(nonce >> 32), (uint32_t)cipher_id},
-                              {(uint32_t)ctx, (uint32_t)(ctx >> 32), 0u},
-                              {gen, 0u, 0u}};
-    for (int c = 0; c < 4; ++c) {
-        if (w.vram) { /* chunk 2c = {k, A, k, B}, 2c + 1 = {k, C, k, 0} */
-            store_chunk(w.req + 8 * c, k, f[c][0], k, f[c][1]);
-            store_chunk(w.req + 8 * c + 4, k, f[c][2], k, 0u);
-        } else {
-            store_chunk(w.req + 4 * c, k, f[c][0], f[c][1], f[c][2]);
-        }
-    }
-    _mm_sfence(); /* out of the write-combining buffer now, not later */
+    Worker *wp = nullptr;
+    Request rq = {};
+    const int rc = claim_and_ensure(dev, h_ctx, lk, wp, rq.ctx);
+    if (rc) return rc;
+    rq.op = open ? 1u : 0u;
+    rq.ct = ct_env() ? 1u : 0u;
+    rq.len = (uint32_t)len;
+    rq.ad_len = (uint32_t)ad_len;
+    rq.nonce = nonce;
+    rq.cipher = (uint32_t)cipher_id;
+    rq.gen = gen;
+    uint64_t h1;
+    const uint32_t k = post(*wp, rq, cipher_id == NOISE_CIPHER_CHACHAPOLY ? key : nullptr, ad, data, h1);
     const uint64_t h2 = host_ns();
-    /* From here on every exit scrubs the shared memory below.  A failure the
-       worker caused (a relaunch that fails, a stale input, no answer within
-       WAIT_LIMIT_NS) is NOISE_ERROR_NOT_APPLICABLE: the caller runs the
-       record through the launch path with the same nonce instead — the result
-       is the same bytes, and the worker only ever writes w.out and the slot. */
-    int st = NOISE_ERROR_NONE;
-    uint64_t spins = 0;
-    while (__atomic_load_n(&s->done, __ATOMIC_ACQUIRE) != k) {
-        __builtin_ia32_pause();
-        if ((++spins & 1023) != 0) continue;
-        const uint32_t gen0 = __atomic_load_n(&g.gen, __ATOMIC_ACQUIRE);
-        if (__atomic_load_n(&s->exiting, __ATOMIC_ACQUIRE) && __atomic_load_n(&s->done, __ATOMIC_ACQUIRE) != k) {
-            /* the group left before this slot took k: start it again (its
-               workgroup starts at done = k - 1 and serves k) */
-            const int rc = group_ensure(w, gen0, 2);
-            if (rc) {
-                st = rc;
-                break;
-            }
-            /* a relaunch by group_launch starts this slot's context history
-               afresh, and the new workgroup serves k and caches h_ctx: note it
-               again, or freeing the state would not park this group and the
-               round keys would stay in its LDS (ADVICE r5) */
-            if (h_ctx) worker_note_ctx(w, h_ctx);
-        }
-        if (host_ns() - h2 > WAIT_LIMIT_NS) { /* no answer: drained, then reused */
-            worker_abandon(w, k);
-            st = NOISE_ERROR_NOT_APPLICABLE;
-            break;
-        }
-    }
+    /* from here on every exit scrubs the shared memory */
+    int st = await(*wp, k, h_ctx, h2);
     const uint64_t h3 = host_ns();
-    if (st == NOISE_ERROR_NONE) {
-        const uint32_t status = s->status;
-        st = status == 2 ? NOISE_ERROR_NOT_APPLICABLE : (status ? NOISE_ERROR_MAC_FAILURE : NOISE_ERROR_NONE);
-        if (st == NOISE_ERROR_NONE) memcpy(data, w.out, open ? len : len + 16);
-    }
-    /* key, plaintext and results out of the shared host memory; the stamps
-       stay (a zeroed chunk would carry number 0, which no request has).  The
-       worker writes its results in 16-B pieces: up to roundup16(len + 16). */
-    for (size_t c = 0; c < nchunks; ++c) _mm_store_si128((__m128i *)(w.in + c), w.vram ? vstamp : stamp);
-    if (total > head) explicit_bzero(w.tail, total - head);
-    if (w.vram) _mm_sfence();
-    explicit_bzero(w.out, (len + 16 + 15) & ~(size_t)15);
+    st = collect_and_scrub(*wp, k, rq, st, data);
     const uint64_t h4 = host_ns();
     t_host[0] = h1 - h0; t_host[1] = h2 - h0; t_host[2] = h3 - h0; t_host[3] = h4 - h0;
     return st;
@@ -1522,8 +1100,9 @@ extern "C" int noise_aead_debug_worker_placement(void)
    (each slot is one workgroup of its group's kernel). */
 extern "C" int noise_aead_debug_workers_resident(void)
 {
-    int dev = 0, n = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= kMaxDev) return -1;
+    const int dev = current_dev();
+    if (dev < 0) return -1;
+    int n = 0;
     for (int i = 0; i < kMaxGroups; ++i) {
         WorkerGroup &g = g_group[dev][i];
         std::lock_guard<std::mutex> lk(g.mu);
@@ -1536,37 +1115,34 @@ extern "C" int noise_aead_debug_workers_resident(void)
    parked worker that is called again is relaunched). */
 extern "C" unsigned noise_aead_debug_worker_launches(void)
 {
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= kMaxDev) return 0;
+    const int dev = current_dev();
     unsigned n = 0;
-    for (int i = 0; i < kMaxGroups; ++i) n += __atomic_load_n(&g_group[dev][i].launches, __ATOMIC_RELAXED);
+    for (int i = 0; dev >= 0 && i < kMaxGroups; ++i) n += __atomic_load_n(&g_group[dev][i].launches, __ATOMIC_RELAXED);
     return n;
+}
+
+/* Test hook: why slot `slot` of group `group` last left (stamps[7]: 1 stop,
+   2 closing, 4 idle, 8 lifetime). */
+extern "C" unsigned noise_aead_debug_worker_leave_reason(int group, int slot)
+{
+    const WorkerSlot *s = debug_slot(group, slot);
+    return s ? s->stamps[7] : 0;
+}
+
+/* Test hook: that leave's born, now (10-ns ticks, low words), lifetime and
+   launch number. */
+extern "C" void noise_aead_debug_worker_leave_info(int group, int slot, unsigned *out)
+{
+    const WorkerSlot *s = debug_slot(group, slot);
+    for (int i = 0; s && i < 4; ++i) out[i] = s->leave[i];
 }
 
 /* Test hook: per group of the current device, kernels launched (out[0..n)
    for groups 0..n-1), then the group_ensure counts by cause (debug). */
-extern "C" unsigned noise_aead_debug_worker_leave_reason(int group, int slot)
-{
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= kMaxDev || group < 0 || group >= kMaxGroups ||
-        slot < 0 || slot >= WORKER_MAX_SLOTS || !g_group[dev][group].slot[slot].slot)
-        return 0;
-    return g_group[dev][group].slot[slot].slot->stamps[7];
-}
-
-extern "C" void noise_aead_debug_worker_leave_info(int group, int slot, unsigned *out)
-{
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= kMaxDev || group < 0 || group >= kMaxGroups ||
-        slot < 0 || slot >= WORKER_MAX_SLOTS || !g_group[dev][group].slot[slot].slot)
-        return;
-    for (int i = 0; i < 4; ++i) out[i] = g_group[dev][group].slot[slot].slot->leave[i];
-}
-
 extern "C" void noise_aead_debug_worker_group_launches(unsigned *out, int n)
 {
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= kMaxDev) return;
+    const int dev = current_dev();
+    if (dev < 0) return;
     for (int i = 0; i < n; ++i)
         out[i] = i < kMaxGroups ? __atomic_load_n(&g_group[dev][i].launches, __ATOMIC_RELAXED)
                                 : (i - kMaxGroups < 4 ? g_dbg_ensure[i - kMaxGroups].load() : 0u);

@@ -89,6 +89,22 @@ def test_worker_request_placement(aead, gpu, vram):
     assert placement == 1 if vram == "0" else placement in (1, 2)
 
 
+@pytest.mark.parametrize("vram", ["0", "1"])
+def test_worker_stream_head_edges(aead, gpu, vram):
+    """The stream's head/tail boundary (worker_proto.h: the first 3072 stream
+    bytes in host memory, 2048 in device memory, travel as stamped chunks,
+    the rest raw): records whose stream total sits at head - 1 .. head + 17
+    for both heads, both ciphers, AD 0 and 17, seal and open, in either
+    placement (tests/worker_mode_check.py --head-edges)."""
+    env = dict(os.environ, NOISE_AEAD_WORKER_VRAM=vram)
+    r = subprocess.run([sys.executable, "-u", os.path.join(os.path.dirname(__file__), "worker_mode_check.py"),
+                        "--head-edges"], env=env, timeout=110, capture_output=True, text=True)
+    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
+    assert int(r.stdout.split("head_edges")[-1].split()[0]) == 72
+    placement = int(r.stdout.split("placement")[-1].split()[0])
+    assert placement == 1 if vram == "0" else placement in (1, 2)
+
+
 def test_worker_in_place_buffer_semantics(aead, gpu, oracle):
     """encrypt_with_ad on a NoiseBuffer: size grows by 16, max_size checked
     first (cipherstate.c:299-333); the worker's fast path leaves bytes past

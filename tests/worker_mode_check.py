@@ -238,7 +238,62 @@ def group_idle():
     return 0 if ok else 1
 
 
+def head_edges():
+    """--head-edges: the transport edge of the request's input stream (key ||
+    AD padded to 16 || record [|| tag]).  Its first `head` bytes travel as
+    stamped chunks, the rest raw: head is 3072 stream bytes with the request
+    in host memory and 2048 in device memory.  For both heads, both ciphers,
+    AD 0 and 17 and both directions (open's stream carries the 16-byte tag),
+    every record length whose stream total is head - 1, head, head + 1,
+    head + 15, head + 16 or head + 17: seal against the oracle, tampered open
+    rejected with buffer and nonce untouched, open back.  Prints
+    "head_edges N" (cases run) and "placement P"."""
+    if not os.path.exists(O.ORACLE_SO):
+        O.build(ref=False)
+    orc = O.Oracle()
+    aead.lib()
+    cases = 0
+    for cipher in (0x4301, 0x4302):
+        rnd = random.Random(cipher ^ 0x4EAD)
+        key = bytes(rnd.randrange(256) for _ in range(32))
+        _, tx = aead.CipherState.new_by_id(cipher)
+        _, rx = aead.CipherState.new_by_id(cipher)
+        assert tx.init_key(key) == 0 and rx.init_key(key) == 0
+        n = 0
+        for A in (0, 17):
+            ad_pad = (A + 15) & ~15
+            lens = sorted({head + d - 32 - ad_pad - tag
+                           for head in (2048, 3072) for tag in (0, 16) for d in (-1, 0, 1, 15, 16, 17)})
+            assert len(lens) == 18 and max(lens) + 16 <= 3100
+            ad = bytes(rnd.randrange(256) for _ in range(A))
+            for L in lens:
+                pt = rnd.getrandbits(8 * L).to_bytes(L, "little")
+                ct = tx.seal(pt, ad)
+                if ct != orc.encrypt(cipher, key, n, pt, ad):
+                    print("seal mismatch", hex(cipher), L, A)
+                    return 1
+                bad = bytearray(ct)
+                bad[rnd.randrange(len(bad))] ^= 1 << rnd.randrange(8)
+                rc, back = rx.open(bytes(bad), ad)
+                if rc != aead.ERROR_MAC_FAILURE or back != bytes(bad) or rx.nonce != n:
+                    print("tamper not rejected", hex(cipher), L, A)
+                    return 1
+                rc, back = rx.open(ct, ad)
+                if rc != 0 or back != pt:
+                    print("open mismatch", hex(cipher), L, A)
+                    return 1
+                n += 1
+                cases += 1
+        tx.free()
+        rx.free()
+    print("head_edges", cases)
+    print("placement", aead.lib().noise_aead_debug_worker_placement())
+    return 0
+
+
 if __name__ == "__main__":
+    if "--head-edges" in sys.argv:
+        sys.exit(head_edges())
     if "--group-idle" in sys.argv:
         sys.exit(group_idle())
     if "--free-check" in sys.argv:
