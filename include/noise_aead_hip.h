@@ -437,6 +437,11 @@ void noise_aead_debug_worker_group_launches(unsigned *out, int n);
  *   8 lifetime) and its born / leave times (10-ns ticks), lifetime, launch. */
 unsigned noise_aead_debug_worker_leave_reason(int group, int slot);
 void noise_aead_debug_worker_leave_info(int group, int slot, unsigned *out);
+/* noise_aead_debug_last_plan: the printed form of the last batch kernel the
+ *   calling thread launched through a noise_aead_dev_* entry point, as
+ *   "kernel<template arguments> grid=.. block=.. ..." (dispatch.h plan_print);
+ *   "none ..." before the first.  Returns the length it has (snprintf's). */
+int noise_aead_debug_last_plan(char *buf, size_t n);
 
 /* Default lanes per record the library picks for a standalone uniform seal
  * or open of n records (noise_aead_dev_{seal,open}_uniform, lanes 0) in a

@@ -105,6 +105,12 @@ void na_worker_forget_ctx(const void *h_ctx) { (void)h_ctx; }
 
 int noise_aead_debug_workers_resident(void) { return 0; }
 
+int noise_aead_debug_last_plan(char *buf, size_t n)
+{
+    if (n) buf[0] = 0;
+    return 0;
+}
+
 void noise_aead_debug_worker_stamps(uint32_t *out, int n)
 {
     for (int i = 0; i < n; ++i) out[i] = 0;

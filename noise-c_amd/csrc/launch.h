@@ -1,12 +1,14 @@
 /*
  * launch.h — the kernel launchers of each translation unit, as seen by the
  * C-ABI layer (aead_api.hip).  launch_chacha.hip holds the ChaChaPoly
- * kernels, launch_aes.hip the AES-GCM ones; they compile in parallel.
+ * kernels, launch_aes.hip the AES-GCM ones; they compile in parallel.  Each
+ * launches the Plan that dispatch.h made of a job.
  * Internal (hidden visibility); the public ABI is include/noise_aead_hip.h.
  */
 #pragma once
 #include "noise_aead_hip.h"
 #include "aead_kernels.h"
+#include "dispatch.h"
 #include <hip/hip_runtime.h>
 
 #define NA_HIDDEN __attribute__((visibility("hidden")))
@@ -19,26 +21,36 @@ inline int hip_rc(hipError_t e) { return e == hipSuccess ? NOISE_ERROR_NONE : NO
    device's resident single-call workers to leave when it fills every CU) */
 NA_HIDDEN void worker_park_for_batch(uint32_t workgroups);
 
-/* ---- launch_chacha.hip.  k = lanes per record; every call returns a
-   NOISE_ERROR_* code (NOISE_ERROR_INVALID_PARAM for an unsupported k). */
-/* uniform batch; fast = FAST layout, ukey = every wave's records share one
-   state; a.vf selects the two-pass open */
-NA_HIDDEN int chacha_uniform(const UniformArgs &a, int k, bool open, bool fast, bool ukey, hipStream_t s);
-/* one launch sealing job a and opening job b (k = 4 or 8, FAST layouts) */
-NA_HIDDEN int chacha_duplex(const UniformArgs &a, const UniformArgs &b, int k, bool ukey, hipStream_t s);
-NA_HIDDEN int chacha_ragged(const RaggedArgs &a, int k, bool open, bool fast, hipStream_t s);
-/* FAST ragged batch through the segmented one-lane kernel (per-launch plan,
-   chachapoly_seg.hip) */
-NA_HIDDEN int chacha_ragged_seg(const RaggedArgs &a, bool open, hipStream_t s);
+/* The one launch: fn is the plan's kernel (nullptr: the plan names none this
+   unit holds), args its arguments. */
+template <typename... A>
+int launch(const Plan &p, void (*fn)(A...), hipStream_t s, const A &...args)
+{
+    if (!fn) return NOISE_ERROR_INVALID_PARAM;
+    if (!p.grid) return NOISE_ERROR_NONE;
+    if (p.park) worker_park_for_batch(p.park);
+    hipLaunchKernelGGL(fn, dim3(p.grid), dim3(p.block), 0, s, args...);
+    return hip_rc(hipGetLastError());
+}
+
+/* The arguments of a plan's kernel: a and b the (seal and open) jobs of a
+   uniform or duplex plan, r the job of a ragged one; the others are null. */
+struct PlanArgs {
+    const UniformArgs *a, *b;
+    const RaggedArgs *r;
+};
+
+/* ---- launch_chacha.hip */
+NA_HIDDEN int chacha_launch(const Plan &p, const PlanArgs &args, hipStream_t s);
+/* the current device's CU count (0: unknown), and its resident workgroups of
+   chachapoly_seg_ragged<open>: what the plans ask of the device */
+NA_HIDDEN uint32_t device_cus();
+NA_HIDDEN uint32_t seg_resident(bool open);
 
 /* ---- launch_aes.hip */
+NA_HIDDEN int aes_launch(const Plan &p, const PlanArgs &args, hipStream_t s);
 /* S-box / T-table of the current device, built once (private stream) */
 NA_HIDDEN hipError_t ensure_aes_tables();
 NA_HIDDEN int aes_prepare(const uint8_t *raw_keys, uint32_t n_states, void *ctx, hipStream_t s);
-/* staged = FAST layout with one state per GCM_WG_RECS records */
-NA_HIDDEN int aes_uniform(const UniformArgs &a, bool open, bool ct, bool staged, hipStream_t s);
-NA_HIDDEN int aes_duplex(const UniformArgs &a, const UniformArgs &b, bool ct, hipStream_t s);
-/* wide = one record per workgroup (small batches, automatic lanes) */
-NA_HIDDEN int aes_ragged(const RaggedArgs &a, bool open, bool fast, bool ct, bool wide, hipStream_t s);
 
 } // namespace na

@@ -1,21 +1,19 @@
 /*
- * launch_aes.hip — launchers of the AES-GCM kernels (aesgcm.hip): the
- * per-device table build, key preparation, and the choice of kernel and
- * launch shape for uniform, duplex and ragged jobs.  Called by the C-ABI
- * layer (aead_api.hip) through launch.h.
+ * launch_aes.hip — launcher of the AES-GCM kernels (aesgcm.hip): the
+ * per-device table build, key preparation, and the launch of a Plan
+ * (dispatch.h) as the instantiation it names.  Called by the C-ABI layer
+ * (aead_api.hip) through launch.h.
  *
  * UniformArgs::vf and RaggedArgs::vf are ChaChaPoly's: the AES-GCM kernels
  * do not read them (but gcm_duplex_fused<true>, whose record body is kept as
  * it was, aesgcm.hip gcm_staged_rec_own; vf is always set there).  Every
- * AES-GCM open verifies first (aead_api.hip open_vf) — it authenticates,
+ * AES-GCM open verifies first (dispatch.h open_vf) — it authenticates,
  * takes the verdict, then decrypts — because an AES-GCM open never writes a
  * byte of a rejected record (cipher-aesgcm.c:184-186), so the other kernels
  * compile no other order.
  */
 #include "launch.h"
 #include "aesgcm.hip"
-#include <cstdlib>
-#include <cstring>
 #include <mutex>
 
 namespace na {
@@ -51,59 +49,52 @@ hipError_t ensure_aes_tables()
     return e;
 }
 
+static_assert(PLAN_GCM_LANES == GCM_LANES && PLAN_GCM_WG == GCM_WG && PLAN_GCM_WG_RECS == GCM_WG_RECS,
+              "dispatch.h counts grids with the kernels' geometry");
+
 namespace {
 
-template <typename Args>
-using KernelFn = void (*)(Args);
+using AnyKernel = void (*)();
+template <typename... A>
+AnyKernel any(void (*fn)(A...)) { return (AnyKernel)fn; }
 
 template <bool CT, int WG, int R, int KL = GCM_LANES>
-KernelFn<RaggedArgs> gcm_ragged_pick(bool open, bool fast)
+AnyKernel gcm_ragged_pick(bool open, bool fast)
 {
-    return open ? (fast ? gcm_ragged_staged<true, true, WG, CT, R, KL>
-                        : gcm_ragged_staged<true, false, WG, CT, R, KL>)
-                : (fast ? gcm_ragged_staged<false, true, WG, CT, R, KL>
-                        : gcm_ragged_staged<false, false, WG, CT, R, KL>);
+    return any(open ? (fast ? gcm_ragged_staged<true, true, WG, CT, R, KL>
+                            : gcm_ragged_staged<true, false, WG, CT, R, KL>)
+                    : (fast ? gcm_ragged_staged<false, true, WG, CT, R, KL>
+                            : gcm_ragged_staged<false, false, WG, CT, R, KL>));
 }
 
-/* Ragged AES-GCM launch shape: threads per workgroup, records per group
-   and lanes per record (gcm_ragged_staged).  A workgroup owns its CU (the
-   LDS T-tables), so its time is its longest wave's; pairing a long with a
-   short record per group (R = 2) evens the waves out: +21 % records per
-   CU-second on C5's 64 B-16 KiB mix (profiles/r02/c5_gcm_shape_ab.jsonl).
-   From 131072 records on every CU gets a 512-record window of 4-lane groups;
-   from 65536 on, 256-record windows of 8-lane groups (KL = 8, H^8 Horner)
-   keep all CUs busy with the same pairing (4-lane pairs there would idle
-   half the CUs: 1.55 vs 0.94 ms); smaller batches take 256-thread
-   workgroups over 64-record windows.  NOISE_AEAD_GCM_SHAPE=w1024r1 |
-   w1024r2 | w1024r2k8 forces a shape (A/B runs). */
-struct GcmShape { int wg, r, kl; };
+/* the kernels whose template arguments are OPEN and CT */
+#define NA_OPEN_CT(kernel) \
+    any(p.ct ? (p.open ? kernel<true, true> : kernel<false, true>) : (p.open ? kernel<true, false> : kernel<false, false>))
 
-GcmShape gcm_ragged_shape(uint32_t n)
-{
-    static const int forced = [] {
-        const char *e = getenv("NOISE_AEAD_GCM_SHAPE");
-        if (!e) return 0;
-        if (!strcmp(e, "w1024r1")) return 1;
-        if (!strcmp(e, "w1024r2")) return 2;
-        if (!strcmp(e, "w1024r2k8")) return 3;
-        return 0;
-    }();
-    if (forced == 1) return {1024, 1, 4};
-    if (forced == 2) return {1024, 2, 4};
-    if (forced == 3) return {1024, 2, 8};
-    if (n >= 256u * 2 * GCM_WG_RECS) return {1024, 2, 4};
-    if (n >= 256u * GCM_WG_RECS) return {1024, 2, 8};
-    return {256, 1, 4};
-}
-
+/* The plan's kernel value and template arguments as the function pointer
+   (nullptr: no such instantiation). */
 template <bool CT>
-KernelFn<RaggedArgs> gcm_ragged_fn(bool open, bool fast, GcmShape sh)
+AnyKernel gcm_ragged_kernel(const Plan &p)
 {
-    if (sh.kl == 8) return gcm_ragged_pick<CT, 1024, 2, 8>(open, fast);
-    if (sh.wg == 1024 && sh.r == 2) return gcm_ragged_pick<CT, 1024, 2>(open, fast);
-    if (sh.wg == 1024) return gcm_ragged_pick<CT, 1024, 1>(open, fast);
-    return gcm_ragged_pick<CT, 256, 1>(open, fast);
+    if (p.lanes == 8) return gcm_ragged_pick<CT, 1024, 2, 8>(p.open, p.fast);
+    if (p.wg == 1024 && p.r == 2) return gcm_ragged_pick<CT, 1024, 2>(p.open, p.fast);
+    if (p.wg == 1024) return gcm_ragged_pick<CT, 1024, 1>(p.open, p.fast);
+    return gcm_ragged_pick<CT, 256, 1>(p.open, p.fast);
 }
+
+AnyKernel aes_kernel(const Plan &p)
+{
+    switch (p.kernel) {
+    case K_GCM_UNIFORM: return NA_OPEN_CT(gcm_uniform);
+    case K_GCM_STAGED: return NA_OPEN_CT(gcm_staged);
+    case K_GCM_WIDE: return NA_OPEN_CT(gcm_wide);
+    case K_GCM_DUPLEX_FUSED: return any(p.ct ? gcm_duplex_fused<true> : gcm_duplex_fused<false>);
+    case K_GCM_DUPLEX_STAGED: return any(p.ct ? gcm_duplex_staged<true> : gcm_duplex_staged<false>);
+    case K_GCM_RAGGED: return p.ct ? gcm_ragged_kernel<true>(p) : gcm_ragged_kernel<false>(p);
+    default: return nullptr;
+    }
+}
+#undef NA_OPEN_CT
 
 } // namespace
 
@@ -113,73 +104,19 @@ int aes_prepare(const uint8_t *raw_keys, uint32_t n_states, void *ctx, hipStream
     return hip_rc(hipGetLastError());
 }
 
-
-int aes_uniform(const UniformArgs &a, bool open, bool ct, bool staged, hipStream_t s)
+int aes_launch(const Plan &p, const PlanArgs &args, hipStream_t s)
 {
-    if (a.n_records == 0) return NOISE_ERROR_NONE;
-    if (staged) { /* one state per 256-record workgroup + FAST layout */
-        const uint32_t blocks = (a.n_records + GCM_WG_RECS - 1) / GCM_WG_RECS;
-        worker_park_for_batch(blocks);
-        hipLaunchKernelGGL(ct ? (open ? gcm_staged<true, true> : gcm_staged<false, true>)
-                              : (open ? gcm_staged<true, false> : gcm_staged<false, false>),
-                           dim3(blocks), dim3(GCM_WG), 0, s, a);
-        return hip_rc(hipGetLastError());
+    using UniformFn = void (*)(UniformArgs);
+    using RaggedFn = void (*)(RaggedArgs);
+    using DuplexFn = void (*)(UniformArgs, UniformArgs, uint32_t, uint32_t);
+    const AnyKernel fn = aes_kernel(p);
+    switch (p.kernel) {
+    case K_GCM_DUPLEX_FUSED:
+    case K_GCM_DUPLEX_STAGED: return launch(p, (DuplexFn)fn, s, *args.a, *args.b, p.sb, p.ob);
+    case K_GCM_WIDE:
+    case K_GCM_RAGGED: return launch(p, (RaggedFn)fn, s, *args.r);
+    default: return launch(p, (UniformFn)fn, s, *args.a);
     }
-    const uint32_t blocks = (uint32_t)(((uint64_t)a.n_records * GCM_LANES + 255) / 256);
-    worker_park_for_batch(blocks);
-    hipLaunchKernelGGL(ct ? (open ? gcm_uniform<true, true> : gcm_uniform<false, true>)
-                          : (open ? gcm_uniform<true, false> : gcm_uniform<false, false>),
-                       dim3(blocks), dim3(256), 0, s, a);
-    return hip_rc(hipGetLastError());
-}
-
-/* The fused duplex kernel (one LDS fill, seal then open per workgroup) by
-   default: C3 +0.7-0.9 % in three interleaved rounds
-   (profiles/r03/gcm_fused_ab.jsonl); NOISE_AEAD_GCM_DUPLEX=staged selects
-   gcm_duplex_staged (A/B runs). */
-static bool gcm_duplex_fused_on()
-{
-    static const bool v = [] {
-        const char *e = getenv("NOISE_AEAD_GCM_DUPLEX");
-        return !(e && !strcmp(e, "staged"));
-    }();
-    return v;
-}
-
-int aes_duplex(const UniformArgs &a, const UniformArgs &b, bool ct, hipStream_t s)
-{
-    const uint32_t sb = (a.n_records + GCM_WG_RECS - 1) / GCM_WG_RECS;
-    const uint32_t ob = (b.n_records + GCM_WG_RECS - 1) / GCM_WG_RECS;
-    worker_park_for_batch(sb > ob ? sb : ob);
-    if (gcm_duplex_fused_on()) {
-        hipLaunchKernelGGL(ct ? gcm_duplex_fused<true> : gcm_duplex_fused<false>,
-                           dim3(sb > ob ? sb : ob), dim3(GCM_WG), 0, s, a, b, sb, ob);
-        return hip_rc(hipGetLastError());
-    }
-    hipLaunchKernelGGL(ct ? gcm_duplex_staged<true> : gcm_duplex_staged<false>, dim3(sb + ob),
-                       dim3(GCM_WG), 0, s, a, b, sb, ob);
-    return hip_rc(hipGetLastError());
-}
-
-int aes_ragged(const RaggedArgs &a, bool open, bool fast, bool ct, bool wide, hipStream_t s)
-{
-    if (a.n_records == 0) return NOISE_ERROR_NONE;
-    if (wide) { /* small batch: a workgroup per record (latency, not throughput) */
-        hipLaunchKernelGGL(ct ? (open ? gcm_wide<true, true> : gcm_wide<false, true>)
-                              : (open ? gcm_wide<true, false> : gcm_wide<false, false>),
-                           dim3(a.n_records), dim3(256), 0, s, a);
-        return hip_rc(hipGetLastError());
-    }
-    /* LDS-staged kernel: 1024-thread workgroups over 256-record windows; a
-       batch too small to give every CU one of those uses 256-thread
-       workgroups over 64-record windows instead (4x the workgroups) */
-    const GcmShape sh = gcm_ragged_shape(a.n_records);
-    const uint32_t per = (uint32_t)(sh.wg / sh.kl * sh.r); /* records per window */
-    const uint32_t blocks = (a.n_records + per - 1) / per;
-    KernelFn<RaggedArgs> fn = ct ? gcm_ragged_fn<true>(open, fast, sh) : gcm_ragged_fn<false>(open, fast, sh);
-    worker_park_for_batch(blocks);
-    hipLaunchKernelGGL(fn, dim3(blocks), dim3(sh.wg), 0, s, a);
-    return hip_rc(hipGetLastError());
 }
 
 } // namespace na

@@ -1,104 +1,92 @@
 /*
- * launch_chacha.hip — launchers of the ChaChaPoly kernels (chachapoly.hip):
- * picks the instantiation for the lane count, layout, key sharing and open
- * order of a job and launches it.  Called by the C-ABI layer (aead_api.hip)
- * through launch.h.
+ * launch_chacha.hip — launcher of the ChaChaPoly kernels (chachapoly.hip,
+ * chachapoly_seg.hip): turns a Plan (dispatch.h) into the instantiation it
+ * names and launches it, and answers what the plans ask of the device.
+ * Called by the C-ABI layer (aead_api.hip) through launch.h.
  */
 #include "launch.h"
 #include "chachapoly.hip"
 #include "chachapoly_seg.hip"
 #include <atomic>
-#include <cstdlib>
-#include <cstring>
 
 namespace na {
 namespace {
 
-template <typename Args>
-using KernelFn = void (*)(Args);
+static_assert(PLAN_SEG_KMAX == SEG_KMAX, "dispatch.h counts the segmented grid with SEG_KMAX");
 
-template <typename Args>
-int launch(KernelFn<Args> fn, uint32_t n_records, int lanes, const Args &a, hipStream_t s)
-{
-    if (n_records == 0) return NOISE_ERROR_NONE;
-    const uint64_t threads = (uint64_t)n_records * lanes;
-    const uint32_t blocks = (uint32_t)((threads + 255) / 256);
-    worker_park_for_batch(blocks);
-    hipLaunchKernelGGL(fn, dim3(blocks), dim3(256), 0, s, a);
-    return hip_rc(hipGetLastError());
-}
+using AnyKernel = void (*)();
+template <typename... A>
+AnyKernel any(void (*fn)(A...)) { return (AnyKernel)fn; }
 
 template <int K>
-KernelFn<UniformArgs> chacha_staged_fn(bool open, bool ukey)
+AnyKernel staged_k(const Plan &p)
 {
-    if (ukey) return open ? chachapoly_open_staged<K, true> : chachapoly_seal_staged<K, true>;
-    return open ? chachapoly_open_staged<K, false> : chachapoly_seal_staged<K, false>;
+    if (p.kernel == K_CHACHA_DUPLEX_STAGED)
+        return any(p.ukey ? chachapoly_duplex_staged<K, true> : chachapoly_duplex_staged<K, false>);
+    if (p.kernel == K_CHACHA_STAGED_VF)
+        return any(p.ukey ? chachapoly_open_staged_vf<K, true> : chachapoly_open_staged_vf<K, false>);
+    if (p.ukey) return any(p.open ? chachapoly_open_staged<K, true> : chachapoly_seal_staged<K, true>);
+    return any(p.open ? chachapoly_open_staged<K, false> : chachapoly_seal_staged<K, false>);
 }
 
-/* vf: a VERIFY_FIRST open takes an AUTH + DEC kernel — the one-lane
-   open_solo_staged, the 4/8-lane open_il_staged_vf (FAST layouts) or the
-   two-pass chachapoly_open_uniform — never the one-pass staged kernels */
+template <int K, bool FAST>
+AnyKernel generic_k(const Plan &p)
+{
+    if (p.kernel == K_CHACHA_UNIFORM) {
+        /* no plan names these: a FAST job on 1, 4 or 8 lanes takes the one-lane
+           or a staged kernel (their device code stays instantiated, as it was) */
+        if (FAST && (K == 1 || K == 4 || K == 8)) return nullptr;
+        return any(p.open ? chachapoly_open_uniform<K, FAST> : chachapoly_seal_uniform<K, FAST>);
+    }
+    if (!p.open) return any(chachapoly_seal_ragged<K, FAST>);
+    if constexpr (K < 4) return any(chachapoly_open_ragged<K, FAST>);
+    else if constexpr (FAST) return any(p.vf_order ? chachapoly_open_ragged<K, true, true> : chachapoly_open_ragged<K, true, false>);
+    else return any(chachapoly_open_ragged<K, false, false>);
+}
+
+/* the generic-layout and wide-group kernels, uniform or ragged */
 template <bool FAST>
-KernelFn<UniformArgs> chacha_uniform_fn_t(int k, bool open, bool ukey, bool vf, bool runs)
+AnyKernel generic_fn(const Plan &p)
 {
-    switch (k) {
-    case 1:
-        /* one lane per record, LDS-staged (seal_solo_staged); runs: the key
-           stream issued in runs once the launch holds two waves per SIMD */
-        if (FAST) {
-            if (runs) {
-                if (ukey) return open ? chachapoly_open_solo<true, true> : chachapoly_seal_solo<true, true>;
-                return open ? chachapoly_open_solo<false, true> : chachapoly_seal_solo<false, true>;
-            }
-            if (ukey) return open ? chachapoly_open_solo<true, false> : chachapoly_seal_solo<true, false>;
-            return open ? chachapoly_open_solo<false, false> : chachapoly_seal_solo<false, false>;
+    switch (p.lanes) {
+    case 1: return generic_k<1, FAST>(p);
+    case 2: return generic_k<2, FAST>(p);
+    case 4: return generic_k<4, FAST>(p);
+    case 8: return generic_k<8, FAST>(p);
+    case 16: return generic_k<16, FAST>(p);
+    case 32: return generic_k<32, FAST>(p);
+    case 64: return generic_k<64, FAST>(p);
+    }
+    return nullptr;
+}
+
+/* The plan's kernel value and template arguments as the function pointer
+   (nullptr: no such instantiation). */
+AnyKernel chacha_kernel(const Plan &p)
+{
+    switch (p.kernel) {
+    case K_CHACHA_UNIFORM:
+    case K_CHACHA_RAGGED: return p.fast ? generic_fn<true>(p) : generic_fn<false>(p);
+    case K_CHACHA_STAGED:
+    case K_CHACHA_STAGED_VF:
+    case K_CHACHA_DUPLEX_STAGED: return p.lanes == 4 ? staged_k<4>(p) : (p.lanes == 8 ? staged_k<8>(p) : nullptr);
+    case K_CHACHA_SOLO:
+        if (p.runs) {
+            if (p.ukey) return any(p.open ? chachapoly_open_solo<true, true> : chachapoly_seal_solo<true, true>);
+            return any(p.open ? chachapoly_open_solo<false, true> : chachapoly_seal_solo<false, true>);
         }
-        return open ? chachapoly_open_uniform<1, FAST> : chachapoly_seal_uniform<1, FAST>;
-    case 2: return open ? chachapoly_open_uniform<2, FAST> : chachapoly_seal_uniform<2, FAST>;
-    case 4:
-        if (FAST && open && vf) return ukey ? chachapoly_open_staged_vf<4, true> : chachapoly_open_staged_vf<4, false>;
-        if (FAST) return chacha_staged_fn<4>(open, ukey);
-        return open ? chachapoly_open_uniform<4, FAST> : chachapoly_seal_uniform<4, FAST>;
-    case 8:
-        if (FAST && open && vf) return ukey ? chachapoly_open_staged_vf<8, true> : chachapoly_open_staged_vf<8, false>;
-        if (FAST) return chacha_staged_fn<8>(open, ukey);
-        return open ? chachapoly_open_uniform<8, FAST> : chachapoly_seal_uniform<8, FAST>;
-    case 16: return open ? chachapoly_open_uniform<16, FAST> : chachapoly_seal_uniform<16, FAST>;
-    case 32: return open ? chachapoly_open_uniform<32, FAST> : chachapoly_seal_uniform<32, FAST>;
-    case 64: return open ? chachapoly_open_uniform<64, FAST> : chachapoly_seal_uniform<64, FAST>;
+        if (p.ukey) return any(p.open ? chachapoly_open_solo<true, false> : chachapoly_seal_solo<true, false>);
+        return any(p.open ? chachapoly_open_solo<false, false> : chachapoly_seal_solo<false, false>);
+    case K_CHACHA_SEG2:
+        if (p.open) return any(p.ukey ? chachapoly_seg2_uniform<true, true> : chachapoly_seg2_uniform<true, false>);
+        return any(p.ukey ? chachapoly_seg2_uniform<false, true> : chachapoly_seg2_uniform<false, false>);
+    case K_CHACHA_DUPLEX_SOLO: return any(p.ukey ? chachapoly_duplex_solo<true> : chachapoly_duplex_solo<false>);
+    case K_CHACHA_SEG_RAGGED: return any(p.open ? chachapoly_seg_ragged<true> : chachapoly_seg_ragged<false>);
+    default: return nullptr;
     }
-    return nullptr;
 }
 
-/* ukey: every wave's 64/k records share one state (see u_key_nonce) */
-KernelFn<UniformArgs> chacha_uniform_fn(int k, bool open, bool fast, bool ukey, bool vf, bool runs)
-{
-    return fast ? chacha_uniform_fn_t<true>(k, open, ukey, vf, runs)
-                : chacha_uniform_fn_t<false>(k, open, ukey, vf, runs);
-}
-
-/* VF: the FAST opens' two-pass (verify-first) instantiation; the generic
-   layouts' opens are two-pass already */
-template <bool FAST, bool VF>
-KernelFn<RaggedArgs> chacha_ragged_fn_t(int k, bool open)
-{
-    switch (k) {
-    case 1: return open ? chachapoly_open_ragged<1, FAST> : chachapoly_seal_ragged<1, FAST>;
-    case 2: return open ? chachapoly_open_ragged<2, FAST> : chachapoly_seal_ragged<2, FAST>;
-    case 4: return open ? chachapoly_open_ragged<4, FAST, VF> : chachapoly_seal_ragged<4, FAST>;
-    case 8: return open ? chachapoly_open_ragged<8, FAST, VF> : chachapoly_seal_ragged<8, FAST>;
-    case 16: return open ? chachapoly_open_ragged<16, FAST, VF> : chachapoly_seal_ragged<16, FAST>;
-    case 32: return open ? chachapoly_open_ragged<32, FAST, VF> : chachapoly_seal_ragged<32, FAST>;
-    case 64: return open ? chachapoly_open_ragged<64, FAST, VF> : chachapoly_seal_ragged<64, FAST>;
-    }
-    return nullptr;
-}
-
-KernelFn<RaggedArgs> chacha_ragged_fn(int k, bool open, bool fast, bool vf)
-{
-    if (!fast) return chacha_ragged_fn_t<false, false>(k, open);
-    return vf ? chacha_ragged_fn_t<true, true>(k, open) : chacha_ragged_fn_t<true, false>(k, open);
-}
+} // namespace
 
 /* the current device's CU count, cached per device (a host may mix GPU
    models); 0: unknown */
@@ -117,111 +105,35 @@ uint32_t device_cus()
     return v;
 }
 
-/* Resident workgroups of a kernel on this device (CUs x occupancy). */
-template <typename F>
-uint32_t resident_blocks(F fn)
-{
-    int per = 0;
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per, fn, 256, 0) != hipSuccess || per < 1) return 0;
-    return device_cus() * (uint32_t)per;
-}
-
-} // namespace
-
-int chacha_uniform(const UniformArgs &a, int k, bool open, bool fast, bool ukey, hipStream_t s)
-{
-    if (k == 2 && fast) {
-        /* two segments per record, LDS-staged (chachapoly_seg.hip) */
-        const bool uk = a.rps % 32 == 0;
-        KernelFn<UniformArgs> fn = open ? (uk ? chachapoly_seg2_uniform<true, true> : chachapoly_seg2_uniform<true, false>)
-                                        : (uk ? chachapoly_seg2_uniform<false, true> : chachapoly_seg2_uniform<false, false>);
-        return launch(fn, a.n_records, 2, a, s);
-    }
-    /* one lane per record: runs once the launch is two waves per SIMD
-       (64 records per wave, four SIMDs per CU) */
-    const uint32_t cus = device_cus();
-    const bool runs = cus && (uint64_t)a.n_records >= 2ull * 4 * 64 * cus;
-    KernelFn<UniformArgs> fn = chacha_uniform_fn(k, open, fast, ukey, a.vf != 0, runs);
-    if (!fn) return NOISE_ERROR_INVALID_PARAM;
-    if (k == 1 && fast) {
-        /* one-lane kernels: balance = the launch is one generation (at most
-           two 64-record waves per SIMD; chachapoly.hip solo_blocks2) */
-        UniformArgs b = a;
-        b.balance = cus && (uint64_t)a.n_records <= 2ull * 4 * 64 * cus;
-        return launch(fn, a.n_records, k, b, s);
-    }
-    return launch(fn, a.n_records, k, a, s);
-}
-
-/* chachapoly_duplex_solo's run length: the current device's CU count (one
-   seal and one open block per CU); NOISE_AEAD_DUPLEX_RUNS=0, read once,
-   alternates block by block (A/B runs) */
-static uint32_t duplex_run_chunk()
-{
-    static const bool off = [] {
-        const char *e = getenv("NOISE_AEAD_DUPLEX_RUNS");
-        return e && e[0] == '0';
-    }();
-    return off ? 0u : device_cus();
-}
-
-int chacha_duplex(const UniformArgs &a, const UniformArgs &b, int k, bool ukey, hipStream_t s)
-{
-    const uint32_t sb = (uint32_t)(((uint64_t)a.n_records * k + 255) / 256);
-    const uint32_t ob = (uint32_t)(((uint64_t)b.n_records * k + 255) / 256);
-    if (k == 1) {
-        /* balance: the launch is one generation (two waves per SIMD at most,
-           256-thread blocks of four waves; chachapoly.hip solo_blocks2) */
-        const uint32_t cus = device_cus();
-        UniformArgs a1 = a, b1 = b;
-        a1.balance = b1.balance = cus && (uint64_t)(sb + ob) <= 2ull * cus;
-        worker_park_for_batch(sb + ob);
-        hipLaunchKernelGGL(ukey ? chachapoly_duplex_solo<true> : chachapoly_duplex_solo<false>, dim3(sb + ob),
-                           dim3(256), 0, s, a1, b1, sb, ob, duplex_run_chunk());
-        return hip_rc(hipGetLastError());
-    }
-    void (*fn)(UniformArgs, UniformArgs, uint32_t, uint32_t);
-    if (k == 4) fn = ukey ? chachapoly_duplex_staged<4, true> : chachapoly_duplex_staged<4, false>;
-    else if (k == 8) fn = ukey ? chachapoly_duplex_staged<8, true> : chachapoly_duplex_staged<8, false>;
-    else return NOISE_ERROR_INVALID_PARAM;
-    worker_park_for_batch(sb + ob);
-    hipLaunchKernelGGL(fn, dim3(sb + ob), dim3(256), 0, s, a, b, sb, ob);
-    return hip_rc(hipGetLastError());
-}
-
-int chacha_ragged(const RaggedArgs &a, int k, bool open, bool fast, hipStream_t s)
-{
-    KernelFn<RaggedArgs> fn = chacha_ragged_fn(k, open, fast, a.vf != 0);
-    if (!fn) return NOISE_ERROR_INVALID_PARAM;
-    return launch(fn, a.n_records, k, a, s);
-}
-
-/* Resident workgroups of chachapoly_seg_ragged<open> on the current device,
-   cached per device (a host may mix GPU models): the persistent
-   grid and worker_park_for_batch take this count. */
-template <typename F>
-uint32_t seg_resident(bool open, F fn)
+/* Resident workgroups of chachapoly_seg_ragged<open> on the current device
+   (CUs x occupancy), cached per device: the persistent grid and
+   worker_park_for_batch take this count. */
+uint32_t seg_resident(bool open)
 {
     constexpr int MAX_DEV = 64;
     static std::atomic<uint32_t> cache[MAX_DEV][2];
     int dev = 0;
     if (hipGetDevice(&dev) != hipSuccess || dev < 0) return 0;
-    if (dev >= MAX_DEV) return resident_blocks(fn);
-    std::atomic<uint32_t> &c = cache[dev][open ? 1 : 0];
-    uint32_t v = c.load(std::memory_order_relaxed);
+    std::atomic<uint32_t> *c = dev < MAX_DEV ? &cache[dev][open ? 1 : 0] : nullptr;
+    uint32_t v = c ? c->load(std::memory_order_relaxed) : 0;
     if (!v) {
-        v = resident_blocks(fn); /* idempotent: a racing thread stores the same value */
-        c.store(v, std::memory_order_relaxed);
+        int per = 0;
+        const hipError_t e = open ? hipOccupancyMaxActiveBlocksPerMultiprocessor(&per, chachapoly_seg_ragged<true>, 256, 0)
+                                  : hipOccupancyMaxActiveBlocksPerMultiprocessor(&per, chachapoly_seg_ragged<false>, 256, 0);
+        if (e != hipSuccess || per < 1) return 0;
+        v = device_cus() * (uint32_t)per; /* idempotent: a racing thread stores the same value */
+        if (c) c->store(v, std::memory_order_relaxed);
     }
     return v;
 }
 
+namespace {
+
 /* Ragged FAST batch through the segmented one-lane kernel: the plan (count,
    scan, place) in a stream-ordered scratch block, then the persistent
    kernel, then the scratch is freed (stream-ordered too). */
-int chacha_ragged_seg(const RaggedArgs &a, bool open, hipStream_t s)
+int chacha_ragged_seg(const Plan &plan, const RaggedArgs &a, hipStream_t s)
 {
-    if (a.n_records == 0) return NOISE_ERROR_NONE;
     const size_t bytes = SEG_MAP_OFF + (size_t)a.n_records * SEG_KMAX * sizeof(uint32_t);
     uint8_t *scratch = nullptr;
     if (hipMallocAsync((void **)&scratch, bytes, s) != hipSuccess) return NOISE_ERROR_NO_MEMORY;
@@ -243,19 +155,29 @@ int chacha_ragged_seg(const RaggedArgs &a, bool open, hipStream_t s)
         rc = hip_rc(hipGetLastError());
     }
     if (!rc) {
-        auto fn = open ? chachapoly_seg_ragged<true> : chachapoly_seg_ragged<false>;
-        const uint32_t res = seg_resident(open, fn);
-        const uint64_t most = ((uint64_t)a.n_records * SEG_KMAX + 255) / 256; /* jobs / 4, at most */
-        const uint32_t grid = (uint32_t)(res && most > res ? res : (most ? most : 1));
-        if (!res) rc = NOISE_ERROR_SYSTEM;
-        else {
-            worker_park_for_batch(grid);
-            hipLaunchKernelGGL(fn, dim3(grid), dim3(256), 0, s, a, p, (const uint32_t *)map);
-            rc = hip_rc(hipGetLastError());
-        }
+        using SegFn = void (*)(RaggedArgs, SegPlanHdr *, const uint32_t *);
+        rc = launch(plan, (SegFn)chacha_kernel(plan), s, a, p, (const uint32_t *)map);
     }
     (void)hipFreeAsync(scratch, s);
     return rc;
+}
+
+} // namespace
+
+int chacha_launch(const Plan &p, const PlanArgs &args, hipStream_t s)
+{
+    using UniformFn = void (*)(UniformArgs);
+    using RaggedFn = void (*)(RaggedArgs);
+    using DuplexFn = void (*)(UniformArgs, UniformArgs, uint32_t, uint32_t);
+    using DuplexRunFn = void (*)(UniformArgs, UniformArgs, uint32_t, uint32_t, uint32_t);
+    const AnyKernel fn = chacha_kernel(p);
+    switch (p.kernel) {
+    case K_CHACHA_DUPLEX_SOLO: return launch(p, (DuplexRunFn)fn, s, *args.a, *args.b, p.sb, p.ob, p.run);
+    case K_CHACHA_DUPLEX_STAGED: return launch(p, (DuplexFn)fn, s, *args.a, *args.b, p.sb, p.ob);
+    case K_CHACHA_RAGGED: return launch(p, (RaggedFn)fn, s, *args.r);
+    case K_CHACHA_SEG_RAGGED: return chacha_ragged_seg(p, *args.r, s);
+    default: return launch(p, (UniformFn)fn, s, *args.a);
+    }
 }
 
 } // namespace na

@@ -447,20 +447,8 @@ struct WorkerGroup {
 constexpr int kMaxDev = 64;
 constexpr int kMaxGroups = 8;
 
-/* The environment switches: each read once, by its getter's static.
-   env_flag: a switch that is on by default goes off with "0", one that is
-   off goes on with "1"; env_int: a positive number, else dflt. */
-bool env_flag(const char *name, bool on)
-{
-    const char *e = getenv(name);
-    return e ? (on ? e[0] != '0' : e[0] == '1') : on;
-}
-
-int env_int(const char *name, int dflt)
-{
-    const char *e = getenv(name);
-    return e && atoi(e) > 0 ? atoi(e) : dflt;
-}
+/* The environment switches: each read once, by its getter's static
+   (dispatch.h env_flag / env_int / env_choice). */
 
 /* A resident group never ends while calls keep coming (up to LIFETIME), so
    it must own its hardware queue: a kernel queued behind it on the same AQL
@@ -477,11 +465,7 @@ int env_int(const char *name, int dflt)
    NOISE_AEAD_WORKER_PRIO=normal / low: the A/B placements. */
 int worker_stream_prio()
 {
-    static const int v = [] {
-        const char *e = getenv("NOISE_AEAD_WORKER_PRIO");
-        if (!e) return 1;
-        return !strcmp(e, "normal") ? 0 : (!strcmp(e, "low") ? -1 : 1);
-    }();
+    static const int v = 1 - env_choice("NOISE_AEAD_WORKER_PRIO", {"normal", "low"}); /* high 1, normal 0, low -1 */
     return v;
 }
 
@@ -864,8 +848,7 @@ int current_dev()
 
 bool ct_env()
 {
-    static const bool v = env_flag("NOISE_AEAD_CT_GHASH", false);
-    return v;
+    return switches().ct_ghash;
 }
 
 /* host-side phase times of the last request (ns, CLOCK_MONOTONIC): packed,

@@ -150,6 +150,7 @@ def lib() -> C.CDLL:
         "noise_perror": (None, [C.c_char_p, i]),
         "noise_aead_debug_batch_stats": (None, [P(C.c_uint64), P(C.c_uint64)]),
         "noise_aead_debug_last_freed_ctx": (vp, [P(sz)]),
+        "noise_aead_debug_last_plan": (i, [C.c_char_p, sz]),
         "noise_aead_dev_fill_splitmix": (i, [vp, C.c_uint64, C.c_uint64, C.c_uint64, vp]),
     }
     for name, (res, args) in sigs.items():
@@ -423,6 +424,14 @@ def dev_split(hash_id: int, *, ck: int, n: int, k1: int, k2: int, stream: int = 
 
 def dev_fill_splitmix(d_out: int, nbytes: int, seed: int, word0: int = 0, stream: int = 0) -> int:
     return lib().noise_aead_dev_fill_splitmix(d_out, nbytes, seed, word0, stream or None)
+
+
+def last_plan() -> str:
+    """The batch kernel this thread launched last, with its template arguments,
+    grid and kernel arguments (noise_aead_debug_last_plan)."""
+    buf = C.create_string_buffer(256)
+    lib().noise_aead_debug_last_plan(buf, len(buf))
+    return buf.value.decode()
 
 
 def dev_default_lanes(cipher: int, n_records: int) -> int:

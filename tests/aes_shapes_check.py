@@ -1,9 +1,9 @@
 """Child process of test_gpu_aes_shapes.py (not collected by pytest): the
 AES-GCM kernels that only an environment switch reaches, against the oracle.
 NOISE_AEAD_GCM_SHAPE and NOISE_AEAD_GCM_DUPLEX are read once per process,
-hence the child; the parent sets them.  Nothing here can tell which kernel
-ran: the names and values are those of launch_aes.hip (gcm_ragged_shape,
-gcm_duplex_fused_on) and must follow them if they change there.
+hence the child; the parent sets them.  Each launch is asked which kernel it
+ran (noise_aead_debug_last_plan): gcm_ragged_staged in the forced shape,
+gcm_duplex_staged where the duplex switch asks for it.
 
   aes_shapes_check.py ragged   the windowed ragged kernel in the forced shape
   aes_shapes_check.py duplex   the same, then the duplex of two uniform jobs
@@ -31,6 +31,15 @@ REC_DT = [("in_off", "<u8"), ("out_off", "<u8"), ("nonce", "<u8"), ("ctx_off", "
           ("ad_off", "<u8"), ("len", "<u4"), ("ad_len", "<u4")]
 FIXED_LENS = [0, 15, 16, 17, 1400, 4096]
 AD_SLOT = 32
+# NOISE_AEAD_GCM_SHAPE: threads per workgroup, records per group, lanes per record
+SHAPES = {"w1024r1": "1024,%s,1,4", "w1024r2": "1024,%s,2,4", "w1024r2k8": "1024,%s,2,8"}
+
+
+def ran_forced_shape(open_, fast, ct):
+    tf = {False: "false", True: "true"}
+    shape = SHAPES[os.environ["NOISE_AEAD_GCM_SHAPE"]] % tf[bool(ct)]
+    want = "gcm_ragged_staged<%s,%s,%s>" % (tf[open_], tf[bool(fast)], shape)
+    assert aead.last_plan().split()[0] == want, (aead.last_plan(), want)
 
 
 def ragged(orc, fast, ct):
@@ -81,6 +90,7 @@ def ragged(orc, fast, ct):
     d_pt = dev(pt)
     d_ct = torch.full((total,), 0xA5, dtype=torch.uint8, device="cuda")
     assert aead.dev_ragged(False, AES, inp=d_pt.data_ptr(), out=d_ct.data_ptr(), **kw) == 0
+    ran_forced_shape(False, fast, ct)
     sync()
     sealed = d_ct.cpu().numpy()
     for i in range(count):
@@ -106,6 +116,7 @@ def ragged(orc, fast, ct):
         d_st = torch.full((count,), 9, dtype=torch.uint8, device="cuda")
         assert aead.dev_ragged(True, AES, inp=d_in.data_ptr(), out=d_out.data_ptr(),
                                status=d_st.data_ptr(), **kw) == 0
+        ran_forced_shape(True, fast, ct)
         sync()
         st, back = d_st.cpu().numpy(), d_out.cpu().numpy()
         assert np.array_equal(st, bad.astype(np.uint8)), (what, "status", in_place)

@@ -181,10 +181,10 @@ def test_batch_host_rules(aead_built):
 
 
 def test_default_lane_policy(aead_built):
-    """Lanes per record the library picks (aead_api.hip uniform_lanes /
+    """Lanes per record the library picks (dispatch.h chacha_uniform_lanes /
     auto_lanes): a standalone seal or open takes one lane per record from
     128 Ki records (two waves per SIMD), 4 lanes from 64 Ki (two segments per
-    record measured slower there, aead_api.hip seg_mode), 8 below, and wide
+    record measured slower there, dispatch.h Switches::seg), 8 below, and wide
     groups (up to a wave per record) only for batches of at most 512 records
     — the latency regime; the jobs of a duplex launch take one lane per
     record from 64 Ki records (the BASELINE sizes, FAST layouts)."""
@@ -201,7 +201,7 @@ def test_default_lane_policy(aead_built):
 
 def test_device_api_argument_rules(aead_built):
     """The device-resident entry points reject bad jobs before any HIP call
-    (aead_api.hip check_uniform / run_ragged), so these run without a GPU.
+    (dispatch.h check_uniform / check_ragged), so these run without a GPU.
     The pointers are never dereferenced: every case fails validation."""
     A = aead_built
     fake = 1 << 20  # aligned, non-null, never touched

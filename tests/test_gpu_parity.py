@@ -80,7 +80,7 @@ def gpu_uniform(aead, open_, cipher, keys, nonce_base, rps, inp, in_stride, leng
 def rejected_fill(cipher, out_init, flags=0):
     """What a rejected record's output holds after an out-of-place open:
     untouched (its prior fill) when the open verified first — every open by
-    default since round 6 (aead_api.hip open_vf; every AES-GCM open always)
+    default since round 6 (dispatch.h open_vf; every AES-GCM open always)
     — and zeroed after a ChaChaPoly open that opted into
     NOISE_AEAD_FLAG_ONE_PASS (VERIFY_FIRST overrides it)."""
     return 0 if (cipher == CHACHA and flags & FLAG_ONE_PASS and not flags & FLAG_VERIFY_FIRST) else out_init
@@ -261,14 +261,42 @@ SLOT_CASES = [((1400, 1024, 512), (1400, 768, 256)), ((1400, 512, 256), (1024, 2
               ((1, 256, 256), (1400, 300, 256)), ((1400, 1000, 256), (4096, 256, 256))]
 
 
+def duplex_kernel(aead, cipher, lanes, layout, flags, case):
+    """The one-launch kernel that include/noise_aead_hip.h promises the two
+    jobs of a duplex case, None where it promises two launches: an empty job,
+    a layout that is not FAST, AES-GCM without one state per 256 records;
+    ChaChaPoly jobs on different lane counts, on other than 1, 4 or 8 lanes,
+    on 4 or 8 with a verify-first open, or of which only one has a state per
+    wave."""
+    (_La, na, rpsa), (_Lb, nb_, rpsb) = case
+    tf = {False: "false", True: "true"}
+    if not na or not nb_ or layout == "packed":
+        return None
+    if cipher == AES:
+        if rpsa % 256 or rpsb % 256:
+            return None
+        staged = os.environ.get("NOISE_AEAD_GCM_DUPLEX") == "staged"
+        return "gcm_duplex_%s<%s>" % ("staged" if staged else "fused", tf[bool(flags & FLAG_CT_GHASH)])
+    ka, kb = (lanes or aead.dev_duplex_lanes(cipher, n) for n in (na, nb_))
+    vf = bool(flags & FLAG_VERIFY_FIRST) or not flags & FLAG_ONE_PASS
+    if ka != kb or ka not in (1, 4, 8) or (ka != 1 and vf):
+        return None
+    ua, ub = rpsa % (64 // ka) == 0, rpsb % (64 // ka) == 0
+    if ua != ub:
+        return None
+    return "chachapoly_duplex_solo<%s>" % tf[ua] if ka == 1 else "chachapoly_duplex_staged<%d,%s>" % (ka, tf[ua])
+
+
 def duplex_cases_check(aead, oracle, cipher, cases, layout, lanes, flags, rng):
     """One noise_aead_dev_duplex_uniform call per case, written ((len, records,
     records per state) of the seal job, the same of the open job), checked
     against the oracle (test_duplex_vs_oracle; tests/aes_shapes_check.py runs
-    it under the AES-GCM environment switches).  Returns the last case's
-    device buffers."""
+    it under the AES-GCM environment switches); the kernel that ran
+    (noise_aead_debug_last_plan) is the one duplex_kernel names.  Returns the
+    last case's device buffers."""
     torch = _torch()
-    for (La, na, rpsa), (Lb, nb_, rpsb) in cases:
+    for case in cases:
+        (La, na, rpsa), (Lb, nb_, rpsb) = case
         def strides(L):
             if layout == "packed":
                 return L, L + 16
@@ -305,6 +333,9 @@ def duplex_cases_check(aead, oracle, cipher, cases, layout, lanes, flags, rng):
                               n_records=nb_, recs_per_state=rpsb, status=d_st.data_ptr(),
                               lanes=lanes, flags=flags)
         assert aead.dev_duplex(cipher, sj, oj, stream()) == 0
+        want = duplex_kernel(aead, cipher, lanes, layout, flags, case)
+        ran = aead.last_plan().split()[0]
+        assert ran == want if want else "duplex" not in ran, (case, ran, want)
         sync()
         got_a, back, st = d_outa.cpu().numpy(), d_outb.cpu().numpy(), d_st.cpu().numpy()
         assert np.array_equal(got_a[:na * oa], exp_a[:na * oa]), f"duplex seal len={La}"
@@ -968,6 +999,9 @@ def test_duplex_solo_runs(aead, gpu, oracle, flags):
                           n_records=nb_, recs_per_state=rps, status=got_st.data_ptr(), lanes=1,
                           flags=flags)
     assert aead.dev_duplex(CHACHA, sj, oj, stream()) == 0
+    plan = aead.last_plan().split()
+    assert plan[0] == "chachapoly_duplex_solo<true>" and "sb=301" in plan and "ob=291" in plan, plan
+    assert plan[-1] == "run=%d" % torch.cuda.get_device_properties(0).multi_processor_count, plan
     sync()
     assert torch.equal(got_a, exp_a)
     assert torch.equal(got_b, exp_b)

@@ -81,6 +81,7 @@ def test_ragged_seg_vs_oracle(aead, gpu, oracle, vf, inplace):
                            inp=d_pt.data_ptr(), out=d_ct.data_ptr(), n_records=count,
                            ad=d_ad.data_ptr(), status=d_st.data_ptr(), flags=aead.FLAG_FAST,
                            stream=stream()) == 0
+    assert aead.last_plan().split()[0] == "chachapoly_seg_ragged<false>", aead.last_plan()
     sync()
     got = d_ct.cpu().numpy()
     refused = lens > 65519
@@ -117,6 +118,8 @@ def test_ragged_seg_vs_oracle(aead, gpu, oracle, vf, inplace):
                            inp=d_in.data_ptr(), out=d_out.data_ptr(), n_records=count,
                            ad=d_ad.data_ptr(), status=d_st.data_ptr(), flags=flags,
                            stream=stream()) == 0
+    plan = aead.last_plan().split()
+    assert plan[0] == "chachapoly_seg_ragged<true>" and plan[-1] == "vf=%d" % vf, plan
     sync()
     st = d_st.cpu().numpy()
     want = np.where(refused, 2, np.where(badm, 1, 0))
@@ -158,6 +161,8 @@ def test_uniform_seg2_vs_oracle(aead, gpu, oracle, vf, rps):
         pt = rng.integers(0, 256, count * ins + 64, dtype=np.uint8)
         exp = oracle_seal_records(oracle, CHACHA, keys, nb, rps, pt, ins, L, count, outs)
         got, _ = gpu_uniform(aead, False, CHACHA, keys, nb, rps, pt, ins, L, count, outs, lanes=2)
+        ukey = "true" if rps % 32 == 0 else "false"
+        assert aead.last_plan().split()[0] == "chachapoly_seg2_uniform<false,%s>" % ukey, aead.last_plan()
         assert np.array_equal(got[:count * outs], exp[:count * outs]), f"seal len={L}"
         ct = got.copy()
         bad = sorted(set(rng.integers(0, count, 4).tolist()))
@@ -166,6 +171,7 @@ def test_uniform_seg2_vs_oracle(aead, gpu, oracle, vf, rps):
         flags = aead.FLAG_VERIFY_FIRST if vf else aead.FLAG_ONE_PASS
         back, st = gpu_uniform(aead, True, CHACHA, keys, nb, rps, ct, outs, L, count, ins, lanes=2,
                                out_init=0x5A, flags=flags)
+        assert aead.last_plan().split()[0] == "chachapoly_seg2_uniform<true,%s>" % ukey, aead.last_plan()
         for i in range(count):
             seg = back[i * ins: i * ins + L]
             if i in bad:
@@ -184,6 +190,7 @@ def test_uniform_seg2_vs_oracle(aead, gpu, oracle, vf, rps):
                                 inp=buf.data_ptr(), out=buf.data_ptr(), in_stride=outs, out_stride=outs,
                                 length=L, n_records=count, recs_per_state=rps, status=d_st.data_ptr(),
                                 lanes=2, flags=flags, stream=stream()) == 0
+        assert aead.last_plan().split()[0] == "chachapoly_seg2_uniform<true,%s>" % ukey, aead.last_plan()
         sync()
         g = buf.cpu().numpy()
         for i in range(count):
@@ -212,6 +219,7 @@ def test_uniform_seg2_verify_first_partial_wave(aead, gpu, oracle, count):
         exp = oracle_seal_records(oracle, CHACHA, keys, nb, rps, pt, ins, L, count, outs)
         back, st = gpu_uniform(aead, True, CHACHA, keys, nb, rps, exp, outs, L, count, ins, lanes=2,
                                out_init=0x5A, flags=aead.FLAG_VERIFY_FIRST)
+        assert aead.last_plan().split()[0] == "chachapoly_seg2_uniform<true,false>", aead.last_plan()
         assert not st.any(), (L, np.nonzero(st)[0].tolist())
         for i in range(count):
             assert np.array_equal(back[i * ins: i * ins + L], pt[i * ins: i * ins + L]), (L, i)

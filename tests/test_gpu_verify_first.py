@@ -25,9 +25,18 @@ REC_DT = [("in_off", "<u8"), ("out_off", "<u8"), ("nonce", "<u8"), ("ctx_off", "
           ("ad_off", "<u8"), ("len", "<u4"), ("ad_len", "<u4")]
 
 
-@pytest.mark.parametrize("cipher,lanes,rps", [(CHACHA, 4, 256), (CHACHA, 8, 256), (CHACHA, 4, 13), (CHACHA, 8, 13),
-                                              (CHACHA, 1, 16), (CHACHA, 1, 64), (CHACHA, 64, 16), (AES, 0, 256),
-                                              (AES, 0, 13)])
+# the kernel of each uniform case (noise_aead_debug_last_plan): the 4/8-lane
+# verify-first staged kernel with and without a state per wave (ADVICE r6
+# item 5: K = 8 with a per-record key), the one-lane kernel, the generic
+# two-pass kernel, the staged and the generic AES-GCM kernel
+UNIFORM_KERNEL = {(CHACHA, 4, 256): "chachapoly_open_staged_vf<4,true>", (CHACHA, 8, 256): "chachapoly_open_staged_vf<8,true>",
+                  (CHACHA, 4, 13): "chachapoly_open_staged_vf<4,false>", (CHACHA, 8, 13): "chachapoly_open_staged_vf<8,false>",
+                  (CHACHA, 1, 16): "chachapoly_open_solo<false,false>", (CHACHA, 1, 64): "chachapoly_open_solo<true,false>",
+                  (CHACHA, 64, 16): "chachapoly_open_uniform<64,true>", (AES, 0, 256): "gcm_staged<true,false>",
+                  (AES, 0, 13): "gcm_uniform<true,false>"}
+
+
+@pytest.mark.parametrize("cipher,lanes,rps", list(UNIFORM_KERNEL))
 @pytest.mark.parametrize("in_place", [False, True])
 @pytest.mark.parametrize("vflag", [VF, 0])
 def test_uniform_verify_first(aead, gpu, oracle, cipher, lanes, rps, in_place, vflag):
@@ -62,6 +71,8 @@ def test_uniform_verify_first(aead, gpu, oracle, cipher, lanes, rps, in_place, v
                                 status=d_st.data_ptr(), lanes=lanes, flags=vflag, stream=stream(),
                                 ad=d_ad.data_ptr() if adl else 0, ad_stride=32 if adl else 0,
                                 ad_len=adl) == 0
+        assert aead.last_plan().split()[0] == UNIFORM_KERNEL[cipher, lanes, rps], aead.last_plan()
+        assert aead.last_plan().split()[-1] == "vf=1"
         sync()
         back, st = d_out.cpu().numpy(), d_st.cpu().numpy()
         for i in range(count):
@@ -74,6 +85,21 @@ def test_uniform_verify_first(aead, gpu, oracle, cipher, lanes, rps, in_place, v
                     assert np.all(back[o:o + L] == 0xC3), (L, i)  # never written
             else:
                 assert st[i] == 0 and np.array_equal(back[o:o + L], pt[i * ins:i * ins + L]), (L, i)
+
+
+def ragged_kernel(cipher, lanes, count, fast):
+    """The ragged cases' kernels: every ChaChaPoly lane width's two-pass
+    instantiation (64 lanes for the 300 records with automatic lanes), a
+    workgroup per AES-GCM record for those, and each windowed AES-GCM shape
+    (64-record windows, paired 8-lane groups from 65536 records, paired
+    4-lane groups from 131072)."""
+    tf = "true" if fast else "false"
+    if cipher == CHACHA:
+        return "chachapoly_open_ragged<%d,%s,%s>" % (lanes or 64, tf, tf)
+    if not lanes:
+        return "gcm_wide<true,false>"
+    wg, r, kl = (256, 1, 4) if count < 65536 else ((1024, 2, 8) if count < 131072 else (1024, 2, 4))
+    return "gcm_ragged_staged<true,%s,%d,false,%d,%d>" % (tf, wg, r, kl)
 
 
 @pytest.mark.parametrize("cipher,lanes,count,maxlen", [
@@ -125,6 +151,7 @@ def test_ragged_verify_first(aead, gpu, oracle, cipher, lanes, count, maxlen, fa
                            inp=d_ct.data_ptr(), out=d_out.data_ptr(), n_records=count,
                            status=d_st.data_ptr(), flags=flags | VF, lanes=lanes,
                            stream=stream()) == 0
+    assert aead.last_plan().split()[0] == ragged_kernel(cipher, lanes, count, fast), aead.last_plan()
     sync()
     st, back = d_st.cpu().numpy(), d_out.cpu().numpy()
     assert np.array_equal(st != 0, bad)
