@@ -325,6 +325,47 @@ typedef struct NoiseAeadRagged {
 int noise_aead_dev_seal_ragged(int cipher_id, const NoiseAeadRagged *job, void *stream);
 int noise_aead_dev_open_ragged(int cipher_id, const NoiseAeadRagged *job, void *stream);
 
+/* Ragged duplex: seal_job and open_job in one launch per call where the two
+ * can share a kernel — an echo server's or proxy's tick: a batch of received
+ * frames to open and a batch of outgoing frames to seal, across many
+ * sessions, in every length.  The result is exactly
+ * noise_aead_dev_seal_ragged(seal_job) followed by
+ * noise_aead_dev_open_ragged(open_job) on `stream`: every byte of both
+ * outputs, both status arrays (the seal job's optional one: 0 or 2) and
+ * every byte the separate calls leave untouched.
+ *
+ * Each job keeps its own flags and lanes_per_record with the meaning they
+ * have above: FAST is the caller's guarantee per job, the open verifies
+ * first unless NOISE_AEAD_FLAG_ONE_PASS is set (honoured for FAST ChaChaPoly
+ * opens exactly as noise_aead_dev_open_ragged honours it),
+ * NOISE_AEAD_FLAG_CT_GHASH works per job, and a record over 65519 bytes gets
+ * status 2 and nothing written.  Each job must be a valid ragged job (else
+ * NOISE_ERROR_INVALID_PARAM); a job with n_records == 0 is valid and leaves
+ * the call equal to the other job's standalone call.  An unknown cipher
+ * gives NOISE_ERROR_UNKNOWN_ID.
+ *
+ * The jobs must be independent: nothing one job writes (its output records,
+ * its statuses) may meet anything the other job reads (records, AD) or
+ * writes.  The descriptors live in device memory, so for the record and AD
+ * ranges this is the caller's guarantee (not checked, as for the ragged
+ * calls above); the two status arrays are checked: if both are given and
+ * [status, status + n_records) of the two meet, the call is refused with
+ * NOISE_ERROR_INVALID_PARAM and nothing is written.
+ *
+ * The launch is shared when both jobs, each planned alone, take the same
+ * kernel family with the same template arguments: two segmented ChaChaPoly
+ * jobs (FAST, automatic lanes, 16384 records or more each), two windowed
+ * ChaChaPoly jobs on the same lanes per record and the same FAST, two
+ * windowed AES-GCM jobs of the same launch shape, FAST and CT_GHASH.
+ * Otherwise (a small AES-GCM job with automatic lanes, different lane
+ * counts or shapes, one segmented and one windowed job, FAST on one AES-GCM
+ * job only) the library issues the two launches on `stream`, seal first.
+ * NOISE_AEAD_RAGGED_DUPLEX=0 in the environment (read once) makes every
+ * ragged duplex two launches, =1 shares wherever the jobs agree; unset, a
+ * family shares by default where that was measured faster. */
+int noise_aead_dev_duplex_ragged(int cipher_id, const NoiseAeadRagged *seal_job,
+                                 const NoiseAeadRagged *open_job, void *stream);
+
 /* ------------------------------------------------ 5. session key fan-out
  *
  * SURVEY.md §8f rank 2.  For n sessions at once, the HKDF of

@@ -15,6 +15,13 @@
  *                            tests/golden/dispatch_plans.txt.gz
  *   dispatch_check --table G only environment group G of the table
  *   dispatch_check --groups  the groups' environment settings
+ *   dispatch_check --duplex-ragged
+ *                            plan_duplex_ragged against plan_ragged over both
+ *                            ciphers, record counts, lanes and flags per job,
+ *                            the NOISE_AEAD_RAGGED_DUPLEX switch and the
+ *                            segmented kernel's occupancy, and
+ *                            check_duplex_ragged at the span edges
+ *                            (tests/test_dispatch_duplex_ragged_host.py)
  *
  * The golden table was recorded from the selection code as it stood before
  * dispatch.h existed, compiled with its launches replaced by prints: this
@@ -464,8 +471,156 @@ static void check_arithmetic_edges()
                     }
 }
 
+/* ------------------------------------------------- the ragged duplex plan
+   plan_duplex_ragged's promises, stated against plan_ragged (each job's
+   plan alone): a shared launch runs, for each job, the family and template
+   arguments the job would run alone. */
+static int g_shared; /* shared plans seen */
+
+static bool same_ragged_kernel(const Plan &a, const Plan &b)
+{
+    if (a.kernel != b.kernel) return false;
+    switch (a.kernel) {
+    case K_CHACHA_SEG_RAGGED: return true;
+    case K_CHACHA_RAGGED: return a.lanes == b.lanes && a.fast == b.fast;
+    case K_GCM_RAGGED: return a.wg == b.wg && a.r == b.r && a.lanes == b.lanes && a.fast == b.fast && a.ct == b.ct;
+    default: return false; /* gcm_wide shares nothing */
+    }
+}
+
+static void check_duplex_ragged_plan(int cipher, const NoiseAeadRagged &sj, const NoiseAeadRagged &oj, int sw_value,
+                                     uint32_t resident)
+{
+    Switches sw;
+    sw.ragged_duplex = sw_value;
+    const Plan ps = plan_ragged(cipher, &sj, false, sw, resident), po = plan_ragged(cipher, &oj, true, sw, resident);
+    const Plan p = plan_duplex_ragged(cipher, &sj, &oj, sw, resident);
+#define WHERE "cipher %x n %u/%u k %u/%u f %u/%u sw %d resident %u", cipher, sj.n_records, oj.n_records, \
+              sj.lanes_per_record, oj.lanes_per_record, sj.flags, oj.flags, sw_value, resident
+    /* a refused standalone plan is refused here with the same rc */
+    const int want_rc = ps.rc ? ps.rc : po.rc;
+    CHECK(p.rc == want_rc, WHERE);
+    if (want_rc) return;
+    bool want = sw_value != 0 && sj.n_records && oj.n_records && same_ragged_kernel(ps, po);
+    if (want && sw_value < 0) {
+        Switches on;
+        on.ragged_duplex = 1;
+        const Plan forced = plan_duplex_ragged(cipher, &sj, &oj, on, resident);
+        want = ragged_duplex_default(forced.kernel, forced.vf);
+    }
+    CHECK(p.shared == want, WHERE);
+    g_shared += p.shared;
+    if (!p.shared) {
+        CHECK(p.kernel == K_NONE && !p.grid, WHERE);
+        return;
+    }
+    /* shared implies: both standalone plans exist and name one family with
+       the same template arguments */
+    CHECK(!ps.rc && !po.rc && ps.grid && po.grid && same_ragged_kernel(ps, po), WHERE);
+    CHECK(plan_is_gcm(p) == (cipher == AES), WHERE);
+    CHECK(p.vf == po.vf && p.fast == ps.fast && p.fast == po.fast && p.park == p.grid, WHERE);
+    char line[256];
+    plan_print(p, line, sizeof line);
+    CHECK(strstr(line, " sb=") && strstr(line, " ob="), "%s", line);
+    switch (ps.kernel) {
+    case K_CHACHA_SEG_RAGGED: {
+        const uint64_t most = (uint64_t)blocks_for((uint64_t)sj.n_records * PLAN_SEG_KMAX, PLAN_BLOCK) +
+                              blocks_for((uint64_t)oj.n_records * PLAN_SEG_KMAX, PLAN_BLOCK);
+        CHECK(p.kernel == K_CHACHA_SEG_DUPLEX && p.grid == (most < resident ? most : resident) && p.block == PLAN_BLOCK, WHERE);
+        CHECK(!strncmp(line, "chachapoly_seg_duplex ", 22), "%s", line);
+        break;
+    }
+    case K_CHACHA_RAGGED:
+        CHECK(p.kernel == K_CHACHA_DUPLEX_RAGGED && p.lanes == ps.lanes && p.vf_order == po.vf_order, WHERE);
+        CHECK(p.sb == ps.grid && p.ob == po.grid && p.grid == p.sb + p.ob && p.block == PLAN_BLOCK, WHERE);
+        CHECK(!strncmp(line, "chachapoly_duplex_ragged<", 25), "%s", line);
+        break;
+    case K_GCM_RAGGED:
+        CHECK(p.kernel == K_GCM_DUPLEX_RAGGED && p.wg == ps.wg && p.r == ps.r && p.lanes == ps.lanes && p.ct == ps.ct, WHERE);
+        CHECK(p.sb == ps.grid && p.ob == po.grid && p.grid == (p.sb > p.ob ? p.sb : p.ob) && p.block == ps.block, WHERE);
+        CHECK(!strncmp(line, "gcm_duplex_ragged<", 18), "%s", line);
+        break;
+    default: CHECK(false, WHERE);
+    }
+#undef WHERE
+}
+
+static void check_duplex_ragged_plans()
+{
+    const uint32_t counts[] = {0, 1, 63, 64, 300, 512, 513, 16383, 16384, 65535, 65536, 131071, 131072, 1u << 26};
+    const uint32_t lanes[] = {0, 1, 4, 8, 64};
+    const uint32_t F = NOISE_AEAD_FLAG_FAST;
+    const uint32_t flags[] = {0, F, F | NOISE_AEAD_FLAG_CT_GHASH, F | NOISE_AEAD_FLAG_ONE_PASS};
+    for (int cipher : {CHACHA, AES})
+        for (uint32_t ns : counts)
+            for (uint32_t no : counts)
+                for (uint32_t ks : lanes)
+                    for (uint32_t ko : lanes)
+                        for (uint32_t fs : flags)
+                            for (uint32_t fo : flags)
+                                for (int sw : {1, 0, -1})
+                                    for (uint32_t resident : {0u, 512u})
+                                        check_duplex_ragged_plan(cipher, ragged_job(ns, ks, fs), ragged_job(no, ko, fo), sw,
+                                                                 resident);
+    /* lanes no kernel is built for, and an unknown cipher */
+    const NoiseAeadRagged ok = ragged_job(300, 8, F), bad = ragged_job(300, 3, F);
+    Switches on;
+    on.ragged_duplex = 1;
+    CHECK(plan_duplex_ragged(CHACHA, &bad, &ok, on, 512).rc == PARAM, "3 lanes on the seal job");
+    CHECK(plan_duplex_ragged(CHACHA, &ok, &bad, on, 512).rc == PARAM, "3 lanes on the open job");
+    CHECK(plan_duplex_ragged(0x4303, &ok, &ok, on, 512).rc == NOISE_ERROR_UNKNOWN_ID, "unknown cipher");
+}
+
+/* check_duplex_ragged: the jobs' own checks, then the two status arrays */
+static void check_duplex_ragged_spans()
+{
+    const NoiseAeadRagged ok = ragged_job(300, 0, 0);
+    auto with = [&](uint64_t status, uint32_t n) {
+        NoiseAeadRagged j = ok;
+        j.status = (uint8_t *)status, j.n_records = n;
+        return j;
+    };
+    auto rc = [](NoiseAeadRagged s, NoiseAeadRagged o) { return check_duplex_ragged(&s, &o); };
+    CHECK(check_duplex_ragged(nullptr, &ok) == PARAM && check_duplex_ragged(&ok, nullptr) == PARAM, "a NULL job");
+    for (int side = 0; side < 2; ++side) {
+        NoiseAeadRagged j = ok;
+        j.recs = nullptr;
+        CHECK((side ? rc(ok, j) : rc(j, ok)) == PARAM, "no descriptors, side %d", side);
+        j = ok, j.in = nullptr;
+        CHECK((side ? rc(ok, j) : rc(j, ok)) == PARAM, "no input, side %d", side);
+        j = ok, j.out = nullptr;
+        CHECK((side ? rc(ok, j) : rc(j, ok)) == PARAM, "no output, side %d", side);
+    }
+    CHECK(rc(ok, ok) == OK, "no status arrays");
+    for (uint64_t base : {4096ull, (1ull << 32) - 150, (1ull << 63) - 150, ~0ull - 1000}) {
+        for (uint32_t n : {1u, 2u, 300u}) {
+            CHECK(rc(with(base, n), with(base + n, n)) == OK, "arrays that touch: base %" PRIx64 " n %u", base, n);
+            CHECK(rc(with(base + n, n), with(base, n)) == OK, "arrays that touch, swapped: base %" PRIx64 " n %u", base, n);
+            CHECK(rc(with(base, n), with(base + n - 1, n)) == PARAM, "arrays that meet by a byte: base %" PRIx64 " n %u", base, n);
+            CHECK(rc(with(base + n - 1, n), with(base, n)) == PARAM, "meet by a byte, swapped: base %" PRIx64 " n %u", base, n);
+            CHECK(rc(with(base, n), with(base, n)) == PARAM, "one array for both: base %" PRIx64 " n %u", base, n);
+            CHECK(rc(with(base, n), with(0, n)) == OK && rc(with(0, n), with(base, n)) == OK, "one array only");
+            CHECK(rc(with(base, 0), with(base, n)) == OK && rc(with(base, n), with(base, 0)) == OK, "an empty job writes no status");
+        }
+    }
+    /* the widest arrays: 2^32 - 1 statuses ending at the top of the address
+       space (the span's end, 2^64 - 1, does not wrap in 128 bits) */
+    const uint32_t N = 0xFFFFFFFFu;
+    const uint64_t top = ~0ull - N;
+    CHECK(rc(with(top, N), with(top - N, N)) == OK, "touch below the top");
+    CHECK(rc(with(top, N), with(top - N + 1, N)) == PARAM, "meet by a byte below the top");
+    CHECK(rc(with(top, N), with(16, N)) == OK, "a wrapped end would meet the bottom");
+    CHECK(rc(with(~0ull, 1), with(16, 300)) == OK && rc(with(~0ull, 1), with(~0ull, 1)) == PARAM, "the last byte");
+}
+
 int main(int argc, char **argv)
 {
+    if (argc > 1 && !strcmp(argv[1], "--duplex-ragged")) {
+        check_duplex_ragged_plans();
+        check_duplex_ragged_spans();
+        printf("dispatch_check: %d cases, %d failures, %d shared plans\n", g_cases, g_fail, g_shared);
+        return g_fail ? 1 : 0;
+    }
     if (argc > 1 && !strcmp(argv[1], "--groups")) {
         for (const EnvGroup &g : GROUPS) printf("%s=%s\n", g.name ? g.name : "", g.name ? g.value : "");
         return 0;

@@ -75,12 +75,8 @@ int run_duplex(int cipher_id, const NoiseAeadUniform *sj, const NoiseAeadUniform
     return rc;
 }
 
-int run_ragged(int cipher_id, const NoiseAeadRagged *job, void *stream, bool open)
+RaggedArgs to_args(const NoiseAeadRagged *job, uint32_t vf)
 {
-    const int rc = check_ragged(job);
-    if (rc) return rc;
-    const uint32_t resident = ragged_takes_seg(cipher_id, job, switches()) ? seg_resident(open) : 0;
-    const Plan p = plan_ragged(cipher_id, job, open, switches(), resident);
     RaggedArgs a;
     a.keys = (const uint8_t *)job->ctx_base;
     a.recs = (const RecDesc *)job->recs;
@@ -89,8 +85,37 @@ int run_ragged(int cipher_id, const NoiseAeadRagged *job, void *stream, bool ope
     a.ad = job->ad;
     a.status = job->status;
     a.n_records = job->n_records;
-    a.vf = p.vf;
-    return launch_plan(p, {nullptr, nullptr, &a}, stream);
+    a.vf = vf;
+    return a;
+}
+
+int run_ragged(int cipher_id, const NoiseAeadRagged *job, void *stream, bool open)
+{
+    const int rc = check_ragged(job);
+    if (rc) return rc;
+    const uint32_t resident = ragged_takes_seg(cipher_id, job, switches()) ? seg_resident(open ? SEG_OPEN : SEG_SEAL) : 0;
+    const Plan p = plan_ragged(cipher_id, job, open, switches(), resident);
+    const RaggedArgs a = to_args(job, p.vf);
+    return launch_plan(p, {nullptr, nullptr, &a, nullptr}, stream);
+}
+
+int run_duplex_ragged(int cipher_id, const NoiseAeadRagged *sj, const NoiseAeadRagged *oj, void *stream)
+{
+    int rc = check_duplex_ragged(sj, oj);
+    if (rc) return rc;
+    /* the occupancy of the kernel the segmented jobs would take */
+    const bool seg_s = ragged_takes_seg(cipher_id, sj, switches()), seg_o = ragged_takes_seg(cipher_id, oj, switches());
+    const uint32_t resident =
+        seg_s && seg_o ? seg_resident(SEG_DUPLEX) : (seg_s ? seg_resident(SEG_SEAL) : (seg_o ? seg_resident(SEG_OPEN) : 0));
+    const Plan p = plan_duplex_ragged(cipher_id, sj, oj, switches(), resident);
+    if (p.rc) return p.rc;
+    if (p.shared) {
+        const RaggedArgs sa = to_args(sj, 0), oa = to_args(oj, p.vf);
+        return launch_plan(p, {nullptr, nullptr, &sa, &oa}, stream);
+    }
+    rc = run_ragged(cipher_id, sj, stream, false);
+    if (!rc) rc = run_ragged(cipher_id, oj, stream, true);
+    return rc;
 }
 
 __global__ void splitmix_fill(uint8_t *out, uint64_t nbytes, uint64_t seed, uint64_t word0)
@@ -166,6 +191,12 @@ int noise_aead_dev_seal_ragged(int cipher_id, const NoiseAeadRagged *job, void *
 int noise_aead_dev_open_ragged(int cipher_id, const NoiseAeadRagged *job, void *stream)
 {
     return run_ragged(cipher_id, job, stream, true);
+}
+
+int noise_aead_dev_duplex_ragged(int cipher_id, const NoiseAeadRagged *seal_job,
+                                 const NoiseAeadRagged *open_job, void *stream)
+{
+    return run_duplex_ragged(cipher_id, seal_job, open_job, stream);
 }
 
 int noise_aead_dev_fill_splitmix(uint8_t *d_out, uint64_t nbytes, uint64_t seed,

@@ -1067,34 +1067,24 @@ NA_DEV RkS rk_scalar(const uint32_t *p)
  * longest records finishes; R = 2 pairs long with short records so every
  * wave carries about the window's mean (KL = 8 keeps that at 256 records
  * per window). */
-template <bool OPEN, bool FAST, int WG, bool CT, int R = 1, int KL = GCM_LANES>
-__global__ __launch_bounds__(WG) void gcm_ragged_staged(RaggedArgs a)
+/* One window of a ragged job: the records [base, base + NREC) in the length
+   order `order` holds (window_rec), each group's R records one after another.
+   key: two staged state slots, slot_off their contexts' offsets (GCM_NO_SLOT:
+   the slot holds no state). */
+constexpr uint64_t GCM_NO_SLOT = ~0ull; /* no context lies at this offset (contexts are 16-byte aligned) */
+
+template <bool OPEN, bool FAST, int WG, bool CT, int R, int KL>
+NA_DEV void gcm_ragged_window(const RaggedArgs &a, const uint8_t *TE, const GcmKey *key, const uint64_t (&slot_off)[2],
+                              const uint32_t *order, uint32_t base)
 {
     constexpr int K = KL, NG = WG / KL, NREC = NG * R;
-    __shared__ GcmLds<2> L;
-    __shared__ uint32_t order[NREC];
-    const uint8_t *TE = (const uint8_t *)&L.te[0][0][0];
-    const uint32_t base = blockIdx.x * (uint32_t)NREC;
-    const uint32_t last = min(base + (uint32_t)NREC, a.n_records) - 1;
-    const uint64_t slot_off[2] = {a.recs[base].ctx_off, a.recs[last].ctx_off};
-    te_fill<WG>(L.te);
-#pragma unroll
-    for (int sl = 0; sl < 2; ++sl) key_fill<WG, KL>(L.key[sl], (const AesCtx *)(a.keys + slot_off[sl]), !CT);
     const uint32_t g = threadIdx.x / K;
-    if constexpr (R > 1) { /* sort the whole window; groups take ranks by snake_rank */
-        window_rec<NREC>(a.recs, a.n_records, base, 0, order);
-    }
     const int l = (int)(threadIdx.x % K);
     const uint32_t tpl = te_lane_tpl();
 #pragma unroll 1
     for (int p = 0; p < R; ++p) {
-        uint32_t rec;
-        if constexpr (R == 1) {
-            rec = window_rec<NREC>(a.recs, a.n_records, base, g, order);
-        } else {
-            const uint32_t key = order[snake_rank<NG>(g, p)];
-            rec = key != 0xFFFFFFFFu ? base + (key & (NREC <= 256 ? 0xFFu : 0x1FFu)) : 0xFFFFFFFFu;
-        }
+        const uint32_t okey = order[snake_rank<NG>(g, p)];
+        const uint32_t rec = okey != 0xFFFFFFFFu ? base + (okey & (NREC <= 256 ? 0xFFu : 0x1FFu)) : 0xFFFFFFFFu;
         if (rec >= a.n_records) continue;
         const RecDesc d = a.recs[rec];
         if (reject_len(a, rec, d.len, l == K - 1)) continue;
@@ -1113,17 +1103,80 @@ __global__ __launch_bounds__(WG) void gcm_ragged_staged(RaggedArgs a)
             const int s0 = __builtin_amdgcn_readfirstlane(sl);
             if (s0 >= 0 && __all(sl == s0)) { /* the wave's records share an LDS slot */
                 ok = gcm_record_staged<OPEN, FAST, CT, KL>(
-                    rv, l, TE, tpl, rk_scalar(((const AesCtx *)(a.keys + slot_off[s0]))->rk), L.key[s0].h4);
+                    rv, l, TE, tpl, rk_scalar(((const AesCtx *)(a.keys + slot_off[s0]))->rk), key[s0].h4);
                 done = true;
             }
         }
         if (done) {
         } else if (sl >= 0)
-            ok = gcm_record_staged<OPEN, FAST, CT, KL>(rv, l, TE, tpl, L.key[sl].rk, L.key[sl].h4);
-        else /* a third state in the window: its own context, from global memory */
+            ok = gcm_record_staged<OPEN, FAST, CT, KL>(rv, l, TE, tpl, key[sl].rk, key[sl].h4);
+        else /* another state in the window: its own context, from global memory */
             ok = gcm_record_staged<OPEN, FAST, CT, KL>(rv, l, TE, tpl, rv.ctx->rk, horner_tab<KL>(rv.ctx));
         if (l == K - 1 && a.status) a.status[rec] = ok ? 0 : 1;
     }
+}
+
+template <bool OPEN, bool FAST, int WG, bool CT, int R = 1, int KL = GCM_LANES>
+__global__ __launch_bounds__(WG) void gcm_ragged_staged(RaggedArgs a)
+{
+    constexpr int NREC = WG / KL * R;
+    __shared__ GcmLds<2> L;
+    __shared__ uint32_t order[NREC];
+    const uint32_t base = blockIdx.x * (uint32_t)NREC;
+    const uint32_t last = min(base + (uint32_t)NREC, a.n_records) - 1;
+    const uint64_t slot_off[2] = {a.recs[base].ctx_off, a.recs[last].ctx_off};
+    te_fill<WG>(L.te);
+#pragma unroll
+    for (int sl = 0; sl < 2; ++sl) key_fill<WG, KL>(L.key[sl], (const AesCtx *)(a.keys + slot_off[sl]), !CT);
+    window_rec<NREC>(a.recs, a.n_records, base, 0, order); /* sorts the window; its barriers cover the fills */
+    gcm_ragged_window<OPEN, FAST, WG, CT, R, KL>(a, (const uint8_t *)&L.te[0][0][0], L.key, slot_off, order, base);
+}
+
+/* Ragged duplex (noise_aead_dev_duplex_ragged), the ragged counterpart of
+   gcm_duplex_fused: workgroup b fills the replicated T-tables ONCE, seals
+   window b of job s (b < s_blocks), then opens window b of job o
+   (b < o_blocks), every wave going on to its open records as soon as its
+   seal records are done — no barrier between the halves.
+   LDS: four state slots (the first and last state of both windows) would be
+   131072 + 4 x 8432 = 164800 B, over a workgroup's 163840.  This kernel
+   takes THREE slots and two order arrays: 131072 + 3 x 8432 + 2 x 2048 =
+   160464 B.  The seal window keeps its two slots (first and last state, and
+   rk_scalar for the waves that share one), the open window stages its first
+   record's state; an open record of any other state takes the
+   global-context path, as a third state does in gcm_ragged_staged.  The
+   open half still runs the two-slot lookup, its second slot empty
+   (GCM_NO_SLOT): compiled with a one-slot lookup the open half's register
+   allocation went from 109 VGPRs and no scratch to 128 VGPRs and 148-244
+   bytes of scratch per lane.  Both
+   windows are sorted up front (each into its own order array), so the sort's
+   barriers are behind every wave before its first record. */
+template <bool FAST, int WG, bool CT, int R = 1, int KL = GCM_LANES>
+__global__ __launch_bounds__(WG) void gcm_duplex_ragged(RaggedArgs s, RaggedArgs o, uint32_t s_blocks,
+                                                        uint32_t o_blocks)
+{
+    constexpr int NREC = WG / KL * R;
+    __shared__ GcmLds<3> L;
+    __shared__ uint32_t order[2][NREC];
+    static_assert(sizeof(GcmLds<3>) + sizeof(uint32_t) * 2 * NREC <= 160 * 1024, "a workgroup's LDS");
+    const uint32_t base = blockIdx.x * (uint32_t)NREC;
+    const bool has_s = blockIdx.x < s_blocks, has_o = blockIdx.x < o_blocks; /* workgroup-uniform */
+    uint64_t off_s[2] = {0, 0}, off_o[2] = {0, GCM_NO_SLOT};
+    te_fill<WG>(L.te);
+    if (has_s) {
+        off_s[0] = s.recs[base].ctx_off;
+        off_s[1] = s.recs[min(base + (uint32_t)NREC, s.n_records) - 1].ctx_off;
+#pragma unroll
+        for (int sl = 0; sl < 2; ++sl) key_fill<WG, KL>(L.key[sl], (const AesCtx *)(s.keys + off_s[sl]), !CT);
+    }
+    if (has_o) {
+        off_o[0] = o.recs[base].ctx_off;
+        key_fill<WG, KL>(L.key[2], (const AesCtx *)(o.keys + off_o[0]), !CT);
+    }
+    if (has_s) window_rec<NREC>(s.recs, s.n_records, base, 0, order[0]);
+    if (has_o) window_rec<NREC>(o.recs, o.n_records, base, 0, order[1]);
+    const uint8_t *TE = (const uint8_t *)&L.te[0][0][0];
+    if (has_s) gcm_ragged_window<false, FAST, WG, CT, R, KL>(s, TE, &L.key[0], off_s, order[0], base);
+    if (has_o) gcm_ragged_window<true, FAST, WG, CT, R, KL>(o, TE, &L.key[2], off_o, order[1], base);
 }
 
 /* ------------------------------------ row-collaborative GHASH multiply

@@ -2034,12 +2034,11 @@ __global__ __launch_bounds__(256) void chachapoly_open_uniform(UniformArgs a)
    authenticate, then decrypt only a verified record, nothing written for a
    rejected one (cipher-chachapoly.c:135-141) — instead of the one-pass
    open_il_1p, whose plaintext exists before the verdict. */
+/* one workgroup of a ragged seal: window `blk` of the job */
 template <int K, bool FAST>
-__global__ __launch_bounds__(256) void chachapoly_seal_ragged(RaggedArgs a)
+NA_DEV void seal_ragged_wg(const RaggedArgs &a, uint32_t blk, uint32_t *order)
 {
-    __shared__ uint32_t order[256 / K];
-    const uint32_t rec = window_rec<256 / K>(a.recs, a.n_records, blockIdx.x * (256u / K),
-                                             threadIdx.x / K, order);
+    const uint32_t rec = window_rec<256 / K>(a.recs, a.n_records, blk * (256u / K), threadIdx.x / K, order);
     if (rec >= a.n_records) return;
     const RecView rv = ragged_view(a, rec);
     if (reject_len(a, rec, rv.len, threadIdx.x % K == K - 1)) return;
@@ -2047,12 +2046,11 @@ __global__ __launch_bounds__(256) void chachapoly_seal_ragged(RaggedArgs a)
     if (threadIdx.x % K == K - 1 && a.status) a.status[rec] = 0;
 }
 
-template <int K, bool FAST, bool VF = false>
-__global__ __launch_bounds__(256) void chachapoly_open_ragged(RaggedArgs a)
+/* one workgroup of a ragged open */
+template <int K, bool FAST, bool VF>
+NA_DEV void open_ragged_wg(const RaggedArgs &a, uint32_t blk, uint32_t *order)
 {
-    __shared__ uint32_t order[256 / K];
-    const uint32_t rec = window_rec<256 / K>(a.recs, a.n_records, blockIdx.x * (256u / K),
-                                             threadIdx.x / K, order);
+    const uint32_t rec = window_rec<256 / K>(a.recs, a.n_records, blk * (256u / K), threadIdx.x / K, order);
     if (rec >= a.n_records) return;
     const int k = (int)(threadIdx.x % K);
     const RecView rv = ragged_view(a, rec);
@@ -2065,6 +2063,46 @@ __global__ __launch_bounds__(256) void chachapoly_open_ragged(RaggedArgs a)
     }
     if (k == K - 1 && a.status) a.status[rec] = ok ? 0 : 1;
     if (!ok && !a.vf) scrub_rejected(rv.dst, rv.src, rv.len, (uint32_t)k, K);
+}
+
+template <int K, bool FAST>
+__global__ __launch_bounds__(256) void chachapoly_seal_ragged(RaggedArgs a)
+{
+    __shared__ uint32_t order[256 / K];
+    seal_ragged_wg<K, FAST>(a, blockIdx.x, order);
+}
+
+template <int K, bool FAST, bool VF = false>
+__global__ __launch_bounds__(256) void chachapoly_open_ragged(RaggedArgs a)
+{
+    __shared__ uint32_t order[256 / K];
+    open_ragged_wg<K, FAST, VF>(a, blockIdx.x, order);
+}
+
+/* Ragged duplex: one launch sealing ragged job `s` and opening ragged job
+   `o` (noise_aead_dev_duplex_ragged; both jobs on K lanes with the same
+   layout guarantee).  chachapoly_duplex_staged's index arithmetic:
+   workgroups alternate between the jobs while both have windows left, then
+   the longer job's remainder follows.  Each workgroup runs the body of the
+   standalone kernel on its own job, so the results are those of the two
+   separate launches. */
+template <int K, bool FAST, bool VF>
+__global__ __launch_bounds__(256) void chachapoly_duplex_ragged(RaggedArgs s, RaggedArgs o, uint32_t s_blocks,
+                                                                uint32_t o_blocks)
+{
+    __shared__ uint32_t order[256 / K];
+    const uint32_t n = min(s_blocks, o_blocks);
+    uint32_t b = blockIdx.x;
+    bool open;
+    if (b < 2 * n) {
+        open = b & 1;
+        b >>= 1;
+    } else {
+        open = o_blocks > s_blocks;
+        b -= n;
+    }
+    if (open) open_ragged_wg<K, FAST, VF>(o, b, order);
+    else seal_ragged_wg<K, FAST>(s, b, order);
 }
 
 } // namespace na

@@ -958,4 +958,73 @@ __global__ __launch_bounds__(256) NA_SOLO_OCC void chachapoly_seg_ragged(RaggedA
     tl.flush();
 }
 
+/* Ragged duplex (noise_aead_dev_duplex_ragged): ONE persistent grid over the
+   plans of a seal job `s` and an open job `o`, each built by the three plan
+   kernels above.  The waves draw from one ticket (ps->ticket) over
+   n_jobs_seal + n_jobs_open, dealt so that both lists keep their
+   longest-first order: tickets alternate seal, open while both plans have
+   jobs left, then the longer plan's remainder follows.  A wave's job is a
+   seal or an open on a wave-uniform branch, each chachapoly_seg_ragged's
+   own job body: the next-ticket prefetch as the data pass ends, the store
+   drain before the tile is reused, seg_repair's in-place rule. */
+__global__ __launch_bounds__(256) NA_SOLO_OCC void chachapoly_seg_duplex(RaggedArgs s, RaggedArgs o, SegPlanHdr *ps,
+                                                                         const uint32_t *map_s, SegPlanHdr *po,
+                                                                         const uint32_t *map_o)
+{
+    __shared__ struct {
+        uint4 tiles[4][2 * SOLO_TILE];
+        SegOwner owners[4][64];
+    } sh;
+    auto &tiles = sh.tiles;
+    auto &owners = sh.owners;
+    const uint32_t lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+    const uint32_t jobs_s = ps->n_jobs, total_s = ps->total_lanes;
+    const uint32_t jobs_o = po->n_jobs, total_o = po->total_lanes;
+    const uint32_t paired = min(jobs_s, jobs_o), n_jobs = jobs_s + jobs_o;
+    SegTL tl;
+    const uint64_t born = SegTL::now();
+    uint32_t t = 0, e_nx = 0, e0_nx = 0;
+    bool open_nx = false; /* wave-uniform: the ticket's job is the open plan's */
+    const auto next = [&]() {
+        uint32_t tn = 0;
+        if (lane == 0) tn = atomicAdd(&ps->ticket, 1u);
+        t = __builtin_amdgcn_readfirstlane((uint32_t)__shfl((int)tn, 0, 64));
+        uint32_t job;
+        if (t < 2 * paired) {
+            open_nx = t & 1;
+            job = t >> 1;
+        } else {
+            open_nx = jobs_o > jobs_s;
+            job = t - paired;
+        }
+        if (t >= n_jobs) job = 0xFFFFFFFFu; /* past the end: reads nothing */
+        if (open_nx) seg_map_entries(map_o, total_o, jobs_o, job, lane, e_nx, e0_nx);
+        else seg_map_entries(map_s, total_s, jobs_s, job, lane, e_nx, e0_nx);
+    };
+    next();
+    for (;;) {
+        const uint64_t t0 = SegTL::now();
+        if (t >= n_jobs) break; /* every wave draws one ticket past the end */
+        const uint32_t e = e_nx, e0 = e0_nx;
+        const bool open = open_nx;
+        uint32_t key[8];
+        SegLane q = seg_ragged_lane(open ? o : s, e, e0, key);
+        seg_blocks(q);
+        SegIOL io;
+        io.tab = owners[w];
+        io.init(q, lane);
+        const bool inplace = q.src == q.dst;
+        tl.add(1, SegTL::now() - t0);
+        if (open) seg_job<true, false>(q, key, io, lane, tiles[w], o.status, o.vf != 0, inplace, tl, next);
+        else seg_job<false, false>(q, key, io, lane, tiles[w], s.status, false, inplace, tl, next);
+        const uint64_t td = SegTL::now();
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); /* the job's stores left before the tile is reused */
+        __builtin_amdgcn_wave_barrier();
+        tl.add(6, SegTL::now() - td);
+        tl.add(7, 1);
+    }
+    tl.add(0, SegTL::now() - born);
+    tl.flush();
+}
+
 } // namespace na

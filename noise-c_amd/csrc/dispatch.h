@@ -86,6 +86,11 @@ struct Switches {
        duplex kernel (one LDS fill, seal then open per workgroup: C3
        +0.7-0.9 % in three interleaved rounds, profiles/r03/gcm_fused_ab.jsonl) */
     bool gcm_duplex_fused = true;
+    /* NOISE_AEAD_RAGGED_DUPLEX: noise_aead_dev_duplex_ragged's shared
+       launches.  0: every ragged duplex is two launches (seal, then open);
+       1: every family that can share a launch does; unset (-1): each family's
+       measured default (ragged_duplex_default) */
+    int ragged_duplex = -1;
 };
 
 inline Switches switches_from_env()
@@ -99,6 +104,8 @@ inline Switches switches_from_env()
     s.duplex_runs = env_flag("NOISE_AEAD_DUPLEX_RUNS", true);
     s.gcm_shape = env_choice("NOISE_AEAD_GCM_SHAPE", {"w1024r1", "w1024r2", "w1024r2k8"});
     s.gcm_duplex_fused = env_choice("NOISE_AEAD_GCM_DUPLEX", {"staged"}) != 1;
+    const char *rd = getenv("NOISE_AEAD_RAGGED_DUPLEX");
+    s.ragged_duplex = rd ? (rd[0] == '0' ? 0 : (rd[0] == '1' ? 1 : -1)) : -1;
     return s;
 }
 
@@ -211,6 +218,26 @@ inline int check_duplex(const NoiseAeadUniform *sj, const NoiseAeadUniform *oj)
 inline int check_ragged(const NoiseAeadRagged *job)
 {
     return (!job || !job->recs || !job->in || !job->out) ? NOISE_ERROR_INVALID_PARAM : NOISE_ERROR_NONE;
+}
+
+/* The jobs of a ragged duplex launch are independent too, but their
+   descriptors live in device memory: that no record or AD range of one job
+   meets anything the other writes is the caller's guarantee (stated in the
+   header, not checked, as for the ragged calls).  The host sees the two
+   status arrays: they may not meet. */
+inline Span ragged_status_span(const NoiseAeadRagged *j)
+{
+    const u128 lo = (uintptr_t)j->status;
+    return {lo, j->status ? lo + j->n_records : lo};
+}
+
+inline int check_duplex_ragged(const NoiseAeadRagged *sj, const NoiseAeadRagged *oj)
+{
+    int rc = check_ragged(sj);
+    if (!rc) rc = check_ragged(oj);
+    if (rc) return rc;
+    const Span s = ragged_status_span(sj), o = ragged_status_span(oj);
+    return s.lo != s.hi && o.lo != o.hi && meet(s, o) ? NOISE_ERROR_INVALID_PARAM : NOISE_ERROR_NONE;
 }
 
 /* ------------------------------------------------------ the facts of a job
@@ -368,18 +395,21 @@ enum Kernel : uint8_t {
     K_CHACHA_DUPLEX_STAGED, /* chachapoly_duplex_staged<K, UKEY> */
     K_CHACHA_RAGGED,        /* chachapoly_seal_ragged<K, FAST>, chachapoly_open_ragged<K, FAST[, VF]> */
     K_CHACHA_SEG_RAGGED,    /* chachapoly_seg_ragged<OPEN> */
+    K_CHACHA_DUPLEX_RAGGED, /* chachapoly_duplex_ragged<K, FAST, VF> */
+    K_CHACHA_SEG_DUPLEX,    /* chachapoly_seg_duplex */
     K_GCM_UNIFORM,          /* gcm_uniform<OPEN, CT> */
     K_GCM_STAGED,           /* gcm_staged<OPEN, CT> */
     K_GCM_DUPLEX_FUSED,     /* gcm_duplex_fused<CT> */
     K_GCM_DUPLEX_STAGED,    /* gcm_duplex_staged<CT> */
     K_GCM_WIDE,             /* gcm_wide<OPEN, CT> */
     K_GCM_RAGGED,           /* gcm_ragged_staged<OPEN, FAST, WG, CT, R, KL> */
+    K_GCM_DUPLEX_RAGGED,    /* gcm_duplex_ragged<FAST, WG, CT, R, KL> */
 };
 
 struct Plan {
     int rc = NOISE_ERROR_NONE; /* not NONE: the job is refused, nothing else is set */
     Kernel kernel = K_NONE;
-    bool shared = false;       /* plan_duplex: the two jobs share this launch; else plan each alone */
+    bool shared = false;       /* plan_duplex, plan_duplex_ragged: the two jobs share this launch; else plan each alone */
     /* template arguments */
     bool open = false, fast = false, ukey = false, runs = false, vf_order = false, ct = false;
     int wg = 0, r = 0;         /* gcm_ragged_staged: threads per workgroup, records per group */
@@ -587,6 +617,80 @@ inline Plan plan_ragged(int cipher_id, const NoiseAeadRagged *j, bool open, cons
     return refused(NOISE_ERROR_UNKNOWN_ID);
 }
 
+/* Which families' shared ragged launch noise_aead_dev_duplex_ragged takes
+   when NOISE_AEAD_RAGGED_DUPLEX is unset: the ones measured faster than the
+   better of the two separate launches (one stream, two streams) by more
+   than the spread between repeats of one arm, on C5's data with two sets
+   (tools/duplex_ragged_ab.py, profiles/duplex_ragged_ab.jsonl, DESIGN.md
+   4.9).  A family that is off stays built, tested and reachable with
+   NOISE_AEAD_RAGGED_DUPLEX=1.  vf: the open job verifies first.
+   - chachapoly_seg_duplex: 700.6 vs 753.4 us per step (-7.0 %, spread
+     <= 2.9 %) with a one-pass open: on; with a verify-first open 803.7 vs
+     809.9 us (-0.8 %, spread <= 1.4 %): off;
+   - gcm_duplex_ragged<.., 2, 8>: 1544.1 vs 1439.9 us (+7.2 %): off;
+   - chachapoly_duplex_ragged<8, true, true> (the same data under
+     NOISE_AEAD_SEG=0): 985.3 vs 890.4 us (+10.7 %): off. */
+inline bool ragged_duplex_default(Kernel k, bool vf)
+{
+    switch (k) {
+    case K_CHACHA_SEG_DUPLEX: return !vf;
+    case K_CHACHA_DUPLEX_RAGGED:
+    case K_GCM_DUPLEX_RAGGED:
+    default: return false;
+    }
+}
+
+/* A ragged duplex of two checked jobs: one launch (shared) when both jobs
+   take, each planned alone (plan_ragged), the same kernel family with the
+   same template arguments — a job in a shared launch runs exactly what it
+   would run alone.  Else (shared = false) each job is planned and launched
+   alone, seal first.  A job that plan_ragged refuses is refused here with
+   the same rc (the seal job's first).  seg_resident: resident workgroups of
+   the kernel the segmented jobs would run (chachapoly_seg_duplex when both
+   are segmented). */
+inline Plan plan_duplex_ragged(int cipher_id, const NoiseAeadRagged *sj, const NoiseAeadRagged *oj,
+                               const Switches &sw, uint32_t seg_resident)
+{
+    const Plan ps = plan_ragged(cipher_id, sj, false, sw, seg_resident);
+    if (ps.rc) return refused(ps.rc);
+    const Plan po = plan_ragged(cipher_id, oj, true, sw, seg_resident);
+    if (po.rc) return refused(po.rc);
+    Plan p;
+    if (!sj->n_records || !oj->n_records || sw.ragged_duplex == 0 || ps.kernel != po.kernel) return p;
+    if (ps.kernel == K_CHACHA_SEG_RAGGED) {
+        /* one ticket over both plans' jobs on the persistent grid */
+        const uint64_t most = (uint64_t)blocks_for((uint64_t)sj->n_records * PLAN_SEG_KMAX, PLAN_BLOCK) +
+                              blocks_for((uint64_t)oj->n_records * PLAN_SEG_KMAX, PLAN_BLOCK);
+        p.kernel = K_CHACHA_SEG_DUPLEX;
+        p.lanes = 1;
+        p.grid = p.park = most > seg_resident ? seg_resident : (uint32_t)most;
+        p.sb = ps.grid, p.ob = po.grid;
+    } else if (ps.kernel == K_CHACHA_RAGGED) {
+        if (ps.lanes != po.lanes || ps.fast != po.fast) return p;
+        if ((uint64_t)ps.grid + po.grid > 0xFFFFFFFFull) return p;
+        p.kernel = K_CHACHA_DUPLEX_RAGGED;
+        p.lanes = ps.lanes;
+        p.vf_order = po.vf_order;
+        p.sb = ps.grid, p.ob = po.grid;
+        p.grid = p.park = p.sb + p.ob;
+    } else if (ps.kernel == K_GCM_RAGGED) {
+        if (ps.wg != po.wg || ps.r != po.r || ps.lanes != po.lanes || ps.fast != po.fast || ps.ct != po.ct) return p;
+        p.kernel = K_GCM_DUPLEX_RAGGED;
+        p.wg = ps.wg, p.r = ps.r, p.lanes = ps.lanes;
+        p.ct = ps.ct;
+        p.block = ps.block;
+        p.sb = ps.grid, p.ob = po.grid;
+        p.grid = p.park = p.sb > p.ob ? p.sb : p.ob;
+    } else {
+        return p; /* gcm_wide: a workgroup per record, nothing to share */
+    }
+    if (sw.ragged_duplex < 0 && !ragged_duplex_default(p.kernel, po.vf)) return Plan();
+    p.shared = true;
+    p.fast = ps.fast;
+    p.vf = po.vf;
+    return p;
+}
+
 /* The printed form of a plan: the kernel as its symbol demangles (without
    namespace and arguments), then the launch and the kernel arguments.  The
    golden plan table and noise_aead_debug_last_plan share it. */
@@ -609,6 +713,10 @@ inline int plan_print(const Plan &p, char *buf, size_t size)
         else snprintf(name, sizeof name, "chachapoly_seal_ragged<%d,%s>", p.lanes, b[p.fast]);
         break;
     case K_CHACHA_SEG_RAGGED: snprintf(name, sizeof name, "chachapoly_seg_ragged<%s>", b[p.open]); break;
+    case K_CHACHA_DUPLEX_RAGGED:
+        snprintf(name, sizeof name, "chachapoly_duplex_ragged<%d,%s,%s>", p.lanes, b[p.fast], b[p.vf_order]);
+        break;
+    case K_CHACHA_SEG_DUPLEX: snprintf(name, sizeof name, "chachapoly_seg_duplex"); break;
     case K_GCM_UNIFORM: snprintf(name, sizeof name, "gcm_uniform<%s,%s>", b[p.open], b[p.ct]); break;
     case K_GCM_STAGED: snprintf(name, sizeof name, "gcm_staged<%s,%s>", b[p.open], b[p.ct]); break;
     case K_GCM_DUPLEX_FUSED: snprintf(name, sizeof name, "gcm_duplex_fused<%s>", b[p.ct]); break;
@@ -617,6 +725,9 @@ inline int plan_print(const Plan &p, char *buf, size_t size)
     case K_GCM_RAGGED:
         snprintf(name, sizeof name, "gcm_ragged_staged<%s,%s,%d,%s,%d,%d>", b[p.open], b[p.fast], p.wg, b[p.ct], p.r,
                  p.lanes);
+        break;
+    case K_GCM_DUPLEX_RAGGED:
+        snprintf(name, sizeof name, "gcm_duplex_ragged<%s,%d,%s,%d,%d>", b[p.fast], p.wg, b[p.ct], p.r, p.lanes);
         break;
     }
     if (p.sb || p.ob)

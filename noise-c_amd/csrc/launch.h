@@ -34,18 +34,21 @@ int launch(const Plan &p, void (*fn)(A...), hipStream_t s, const A &...args)
 }
 
 /* The arguments of a plan's kernel: a and b the (seal and open) jobs of a
-   uniform or duplex plan, r the job of a ragged one; the others are null. */
+   uniform or duplex plan, r the job of a ragged one, r and ro the seal and
+   the open job of a ragged duplex; the others are null. */
 struct PlanArgs {
     const UniformArgs *a, *b;
-    const RaggedArgs *r;
+    const RaggedArgs *r, *ro;
 };
 
 /* ---- launch_chacha.hip */
 NA_HIDDEN int chacha_launch(const Plan &p, const PlanArgs &args, hipStream_t s);
 /* the current device's CU count (0: unknown), and its resident workgroups of
-   chachapoly_seg_ragged<open>: what the plans ask of the device */
+   a segmented ragged kernel — SEG_SEAL, SEG_OPEN: chachapoly_seg_ragged<open>,
+   SEG_DUPLEX: chachapoly_seg_duplex: what the plans ask of the device */
+enum SegKernel { SEG_SEAL, SEG_OPEN, SEG_DUPLEX };
 NA_HIDDEN uint32_t device_cus();
-NA_HIDDEN uint32_t seg_resident(bool open);
+NA_HIDDEN uint32_t seg_resident(SegKernel which);
 
 /* ---- launch_aes.hip */
 NA_HIDDEN int aes_launch(const Plan &p, const PlanArgs &args, hipStream_t s);

@@ -82,6 +82,16 @@ AnyKernel gcm_ragged_kernel(const Plan &p)
     return gcm_ragged_pick<CT, 256, 1>(p.open, p.fast);
 }
 
+/* gcm_duplex_ragged in the shapes gcm_ragged_kernel picks */
+template <bool CT, bool FAST>
+AnyKernel gcm_duplex_ragged_kernel(const Plan &p)
+{
+    if (p.lanes == 8) return any(gcm_duplex_ragged<FAST, 1024, CT, 2, 8>);
+    if (p.wg == 1024 && p.r == 2) return any(gcm_duplex_ragged<FAST, 1024, CT, 2>);
+    if (p.wg == 1024) return any(gcm_duplex_ragged<FAST, 1024, CT, 1>);
+    return any(gcm_duplex_ragged<FAST, 256, CT, 1>);
+}
+
 AnyKernel aes_kernel(const Plan &p)
 {
     switch (p.kernel) {
@@ -91,6 +101,9 @@ AnyKernel aes_kernel(const Plan &p)
     case K_GCM_DUPLEX_FUSED: return any(p.ct ? gcm_duplex_fused<true> : gcm_duplex_fused<false>);
     case K_GCM_DUPLEX_STAGED: return any(p.ct ? gcm_duplex_staged<true> : gcm_duplex_staged<false>);
     case K_GCM_RAGGED: return p.ct ? gcm_ragged_kernel<true>(p) : gcm_ragged_kernel<false>(p);
+    case K_GCM_DUPLEX_RAGGED:
+        if (p.ct) return p.fast ? gcm_duplex_ragged_kernel<true, true>(p) : gcm_duplex_ragged_kernel<true, false>(p);
+        return p.fast ? gcm_duplex_ragged_kernel<false, true>(p) : gcm_duplex_ragged_kernel<false, false>(p);
     default: return nullptr;
     }
 }
@@ -109,12 +122,14 @@ int aes_launch(const Plan &p, const PlanArgs &args, hipStream_t s)
     using UniformFn = void (*)(UniformArgs);
     using RaggedFn = void (*)(RaggedArgs);
     using DuplexFn = void (*)(UniformArgs, UniformArgs, uint32_t, uint32_t);
+    using DuplexRaggedFn = void (*)(RaggedArgs, RaggedArgs, uint32_t, uint32_t);
     const AnyKernel fn = aes_kernel(p);
     switch (p.kernel) {
     case K_GCM_DUPLEX_FUSED:
     case K_GCM_DUPLEX_STAGED: return launch(p, (DuplexFn)fn, s, *args.a, *args.b, p.sb, p.ob);
     case K_GCM_WIDE:
     case K_GCM_RAGGED: return launch(p, (RaggedFn)fn, s, *args.r);
+    case K_GCM_DUPLEX_RAGGED: return launch(p, (DuplexRaggedFn)fn, s, *args.r, *args.ro, p.sb, p.ob);
     default: return launch(p, (UniformFn)fn, s, *args.a);
     }
 }

@@ -44,6 +44,30 @@ AnyKernel generic_k(const Plan &p)
     else return any(chachapoly_open_ragged<K, false, false>);
 }
 
+/* chachapoly_duplex_ragged<K, FAST, VF>: VF only where the standalone open
+   has the two instantiations (FAST, K >= 4) */
+template <int K, bool FAST>
+AnyKernel duplex_ragged_k(const Plan &p)
+{
+    if constexpr (FAST && K >= 4) return any(p.vf_order ? chachapoly_duplex_ragged<K, true, true> : chachapoly_duplex_ragged<K, true, false>);
+    else return any(chachapoly_duplex_ragged<K, FAST, false>);
+}
+
+template <bool FAST>
+AnyKernel duplex_ragged_fn(const Plan &p)
+{
+    switch (p.lanes) {
+    case 1: return duplex_ragged_k<1, FAST>(p);
+    case 2: return duplex_ragged_k<2, FAST>(p);
+    case 4: return duplex_ragged_k<4, FAST>(p);
+    case 8: return duplex_ragged_k<8, FAST>(p);
+    case 16: return duplex_ragged_k<16, FAST>(p);
+    case 32: return duplex_ragged_k<32, FAST>(p);
+    case 64: return duplex_ragged_k<64, FAST>(p);
+    }
+    return nullptr;
+}
+
 /* the generic-layout and wide-group kernels, uniform or ragged */
 template <bool FAST>
 AnyKernel generic_fn(const Plan &p)
@@ -82,6 +106,8 @@ AnyKernel chacha_kernel(const Plan &p)
         return any(p.ukey ? chachapoly_seg2_uniform<false, true> : chachapoly_seg2_uniform<false, false>);
     case K_CHACHA_DUPLEX_SOLO: return any(p.ukey ? chachapoly_duplex_solo<true> : chachapoly_duplex_solo<false>);
     case K_CHACHA_SEG_RAGGED: return any(p.open ? chachapoly_seg_ragged<true> : chachapoly_seg_ragged<false>);
+    case K_CHACHA_DUPLEX_RAGGED: return p.fast ? duplex_ragged_fn<true>(p) : duplex_ragged_fn<false>(p);
+    case K_CHACHA_SEG_DUPLEX: return any(chachapoly_seg_duplex);
     default: return nullptr;
     }
 }
@@ -105,21 +131,23 @@ uint32_t device_cus()
     return v;
 }
 
-/* Resident workgroups of chachapoly_seg_ragged<open> on the current device
-   (CUs x occupancy), cached per device: the persistent grid and
+/* Resident workgroups of a segmented ragged kernel on the current device
+   (CUs x occupancy), cached per device and kernel: the persistent grid and
    worker_park_for_batch take this count. */
-uint32_t seg_resident(bool open)
+uint32_t seg_resident(SegKernel which)
 {
     constexpr int MAX_DEV = 64;
-    static std::atomic<uint32_t> cache[MAX_DEV][2];
+    static std::atomic<uint32_t> cache[MAX_DEV][3];
     int dev = 0;
     if (hipGetDevice(&dev) != hipSuccess || dev < 0) return 0;
-    std::atomic<uint32_t> *c = dev < MAX_DEV ? &cache[dev][open ? 1 : 0] : nullptr;
+    std::atomic<uint32_t> *c = dev < MAX_DEV ? &cache[dev][which] : nullptr;
     uint32_t v = c ? c->load(std::memory_order_relaxed) : 0;
     if (!v) {
         int per = 0;
-        const hipError_t e = open ? hipOccupancyMaxActiveBlocksPerMultiprocessor(&per, chachapoly_seg_ragged<true>, 256, 0)
-                                  : hipOccupancyMaxActiveBlocksPerMultiprocessor(&per, chachapoly_seg_ragged<false>, 256, 0);
+        const hipError_t e =
+            which == SEG_DUPLEX ? hipOccupancyMaxActiveBlocksPerMultiprocessor(&per, chachapoly_seg_duplex, 256, 0)
+            : which == SEG_OPEN ? hipOccupancyMaxActiveBlocksPerMultiprocessor(&per, chachapoly_seg_ragged<true>, 256, 0)
+                                : hipOccupancyMaxActiveBlocksPerMultiprocessor(&per, chachapoly_seg_ragged<false>, 256, 0);
         if (e != hipSuccess || per < 1) return 0;
         v = device_cus() * (uint32_t)per; /* idempotent: a racing thread stores the same value */
         if (c) c->store(v, std::memory_order_relaxed);
@@ -162,6 +190,45 @@ int chacha_ragged_seg(const Plan &plan, const RaggedArgs &a, hipStream_t s)
     return rc;
 }
 
+/* A ragged duplex of two segmented jobs: both plans in one stream-ordered
+   scratch block (header and map of the seal job, then of the open job),
+   built by the same three plan kernels, then ONE persistent kernel over both
+   (chachapoly_seg_duplex). */
+int chacha_seg_duplex(const Plan &plan, const RaggedArgs &sa, const RaggedArgs &oa, hipStream_t s)
+{
+    const auto round256 = [](size_t v) { return (v + 255) & ~(size_t)255; };
+    const size_t open_off = round256(SEG_MAP_OFF + (size_t)sa.n_records * SEG_KMAX * sizeof(uint32_t));
+    const size_t bytes = open_off + SEG_MAP_OFF + (size_t)oa.n_records * SEG_KMAX * sizeof(uint32_t);
+    uint8_t *scratch = nullptr;
+    if (hipMallocAsync((void **)&scratch, bytes, s) != hipSuccess) return NOISE_ERROR_NO_MEMORY;
+#ifdef NA_SEG_DEBUG
+    {
+        uint64_t r[2] = {(uint64_t)(uintptr_t)scratch, (uint64_t)(uintptr_t)scratch + bytes};
+        (void)hipMemcpyToSymbolAsync(HIP_SYMBOL(g_seg_arena), r, sizeof(r), 2 * sizeof(uint64_t),
+                                     hipMemcpyHostToDevice, s);
+    }
+#endif
+    SegPlanHdr *hdr[2] = {(SegPlanHdr *)scratch, (SegPlanHdr *)(scratch + open_off)};
+    uint32_t *map[2] = {(uint32_t *)(scratch + SEG_MAP_OFF), (uint32_t *)(scratch + open_off + SEG_MAP_OFF)};
+    const RaggedArgs *job[2] = {&sa, &oa};
+    int rc = NOISE_ERROR_NONE;
+    for (int i = 0; i < 2 && !rc; ++i) {
+        const RaggedArgs &a = *job[i];
+        rc = hip_rc(hipMemsetAsync(hdr[i], 0, sizeof(SegPlanHdr), s));
+        if (rc) break;
+        const uint32_t pb = (a.n_records + 1023) / 1024;
+        hipLaunchKernelGGL(seg_plan_count, dim3(pb), dim3(1024), 0, s, a.recs, a.n_records, hdr[i]);
+        hipLaunchKernelGGL(seg_plan_scan, dim3(1), dim3(64), 0, s, hdr[i]);
+        hipLaunchKernelGGL(seg_plan_place, dim3(pb), dim3(1024), 0, s, a.recs, a.n_records, hdr[i], map[i], a.status);
+        rc = hip_rc(hipGetLastError());
+    }
+    if (!rc)
+        rc = launch(plan, chachapoly_seg_duplex, s, sa, oa, hdr[0], (const uint32_t *)map[0], hdr[1],
+                    (const uint32_t *)map[1]);
+    (void)hipFreeAsync(scratch, s);
+    return rc;
+}
+
 } // namespace
 
 int chacha_launch(const Plan &p, const PlanArgs &args, hipStream_t s)
@@ -170,12 +237,15 @@ int chacha_launch(const Plan &p, const PlanArgs &args, hipStream_t s)
     using RaggedFn = void (*)(RaggedArgs);
     using DuplexFn = void (*)(UniformArgs, UniformArgs, uint32_t, uint32_t);
     using DuplexRunFn = void (*)(UniformArgs, UniformArgs, uint32_t, uint32_t, uint32_t);
+    using DuplexRaggedFn = void (*)(RaggedArgs, RaggedArgs, uint32_t, uint32_t);
     const AnyKernel fn = chacha_kernel(p);
     switch (p.kernel) {
     case K_CHACHA_DUPLEX_SOLO: return launch(p, (DuplexRunFn)fn, s, *args.a, *args.b, p.sb, p.ob, p.run);
     case K_CHACHA_DUPLEX_STAGED: return launch(p, (DuplexFn)fn, s, *args.a, *args.b, p.sb, p.ob);
     case K_CHACHA_RAGGED: return launch(p, (RaggedFn)fn, s, *args.r);
     case K_CHACHA_SEG_RAGGED: return chacha_ragged_seg(p, *args.r, s);
+    case K_CHACHA_DUPLEX_RAGGED: return launch(p, (DuplexRaggedFn)fn, s, *args.r, *args.ro, p.sb, p.ob);
+    case K_CHACHA_SEG_DUPLEX: return chacha_seg_duplex(p, *args.r, *args.ro, s);
     default: return launch(p, (UniformFn)fn, s, *args.a);
     }
 }

@@ -143,6 +143,7 @@ def lib() -> C.CDLL:
         "noise_aead_dev_duplex_uniform": (i, [i, P(NoiseAeadUniform), P(NoiseAeadUniform), vp]),
         "noise_aead_dev_seal_ragged": (i, [i, P(NoiseAeadRagged), vp]),
         "noise_aead_dev_open_ragged": (i, [i, P(NoiseAeadRagged), vp]),
+        "noise_aead_dev_duplex_ragged": (i, [i, P(NoiseAeadRagged), P(NoiseAeadRagged), vp]),
         "noise_aead_dev_default_lanes": (i, [i, C.c_uint32]),
         "noise_aead_dev_duplex_lanes": (i, [i, C.c_uint32]),
         "noise_aead_dev_pad": (i, [vp, vp, C.c_uint64, vp, C.c_uint32, C.c_uint32, i, vp, vp]),
@@ -398,6 +399,21 @@ def dev_ragged(open_: bool, cipher: int, *, ctx_base: int, recs: int, inp: int, 
                         n_records, lanes, flags, 0)
     f = lib().noise_aead_dev_open_ragged if open_ else lib().noise_aead_dev_seal_ragged
     return f(cipher, C.byref(j), stream or None)
+
+
+def ragged_job(*, ctx_base: int, recs: int, inp: int, out: int, n_records: int, status: int = 0,
+               ad: int = 0, lanes: int = 0, flags: int = 0) -> NoiseAeadRagged:
+    return NoiseAeadRagged(ctx_base or None, recs or None, inp or None, out or None, ad or None,
+                           status or None, n_records, lanes, flags, 0)
+
+
+def dev_duplex_ragged(cipher: int, seal_job: NoiseAeadRagged, open_job: NoiseAeadRagged,
+                      stream: int = 0) -> int:
+    """noise_aead_dev_duplex_ragged: seal_job and open_job in one launch where
+    they can share a kernel (a job may be None: the NULL job)."""
+    return lib().noise_aead_dev_duplex_ragged(cipher, C.byref(seal_job) if seal_job is not None else None,
+                                              C.byref(open_job) if open_job is not None else None,
+                                              stream or None)
 
 
 def dev_hkdf(hash_id: int, *, keys: int, key_len: int, data: int = 0, data_len: int = 0,
