@@ -62,6 +62,7 @@ typedef struct {
 #define NOISE_HASH_BLAKE2b NOISE_ID('H', 2)
 #define NOISE_HASH_SHA256 NOISE_ID('H', 3)
 #define NOISE_HASH_SHA512 NOISE_ID('H', 4)
+#define NOISE_DH_CURVE25519 NOISE_ID('D', 1) /* constants.h:51 */
 #define NOISE_ERROR_NONE 0
 #define NOISE_ERROR_NO_MEMORY NOISE_ID('E', 1)
 #define NOISE_ERROR_UNKNOWN_ID NOISE_ID('E', 2)
@@ -429,6 +430,48 @@ typedef struct NoiseRandSnapshot {
 int noise_aead_dev_pad(NoiseRandSnapshot *d_rand, uint8_t *d_payloads, uint64_t stride,
                        const uint32_t *d_orig_lens, uint32_t padded_len, uint32_t n,
                        int padding_mode, uint32_t *d_done, void *stream);
+
+/* ------------------------------------------------ 7. batched X25519
+ *
+ * n calls of noise_dhstate_calculate for Curve25519 (src/protocol/dhstate.c
+ * :685-717, which runs curve25519_donna, src/backend/ref/dh-curve25519.c
+ * :94-103) in one launch, so that DH -> mix_key (noise_aead_dev_hkdf) ->
+ * split -> prepare -> seal runs for n sessions without a host round trip.
+ * Session i multiplies the 32-byte private key at d_priv + i*priv_stride by
+ * the 32-byte public value at d_pub + i*pub_stride and writes the 32-byte
+ * shared key at d_shared + 32*i: packed, directly the d_data of
+ * noise_aead_dev_hkdf(..., data_len = 32, ...).  A stride of 0 is one key for
+ * all n sessions (a server's static key against n client ephemerals, the
+ * es / se tokens); any other stride must be at least 32.  No pointer or
+ * stride needs any alignment.
+ *
+ * Byte for byte what the reference computes: the private key is clamped
+ * inside the call (the keys in memory are never written), bit 255 of the
+ * public value is ignored, a public value of 2^255 - 19 or more is accepted
+ * and reduced, the result is fully reduced.  The all-zero public value gives
+ * the all-zero shared key (the reference's null rule, dhstate.c:702-715, which
+ * the arithmetic satisfies by itself), and so does every other point of small
+ * order, without an error (dh-curve25519.c:99-102).
+ * noise_aead_dev_dh_public is curved25519_scalarmult_basepoint
+ * (dh-curve25519.c:49,73) for n private keys: the same ladder on u = 9, which
+ * also clamps; public key i goes to d_pub_out + 32*i.
+ *
+ * Constant time: 255 ladder steps whatever the key, swaps by mask, no branch,
+ * address or table index that depends on a key bit or an intermediate value
+ * (the base point takes the ladder too), and no scratch memory: no limb of a
+ * key or of an intermediate is spilled to device memory.
+ *
+ * Checked on the host before any launch: dh_id other than NOISE_DH_CURVE25519
+ * gives NOISE_ERROR_UNKNOWN_ID; n == 0 gives NOISE_ERROR_NONE and touches
+ * nothing; otherwise a NULL pointer, a stride in 1..31, or an output range
+ * [d_shared, + 32 n) that meets an input span ([ptr, + (n - 1)*stride + 32))
+ * gives NOISE_ERROR_INVALID_PARAM, with nothing written.
+ * Device pointers, asynchronous on `stream`. */
+int noise_aead_dev_dh_calculate(int dh_id, const uint8_t *d_priv, uint64_t priv_stride,
+                                const uint8_t *d_pub, uint64_t pub_stride, uint32_t n,
+                                uint8_t *d_shared, void *stream);
+int noise_aead_dev_dh_public(int dh_id, const uint8_t *d_priv, uint64_t priv_stride, uint32_t n,
+                             uint8_t *d_pub_out, void *stream);
 
 /* ------------------------------------------------ error reports
  * include/noise/protocol/errors.h; src/protocol/errors.c:92-127. */

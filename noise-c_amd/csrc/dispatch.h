@@ -240,6 +240,30 @@ inline int check_duplex_ragged(const NoiseAeadRagged *sj, const NoiseAeadRagged 
     return s.lo != s.hi && o.lo != o.hi && meet(s, o) ? NOISE_ERROR_INVALID_PARAM : NOISE_ERROR_NONE;
 }
 
+/* Batched X25519 (noise_aead_dev_dh_calculate / _dh_public; launch_dh.hip).
+   The span of n 32-byte keys a stride apart; stride 0 is one key for all. */
+inline Span dh_key_span(const void *p, uint64_t stride, uint32_t n)
+{
+    const u128 lo = (uintptr_t)p;
+    return {lo, lo + (u128)(n - 1) * stride + 32};
+}
+
+/* pub == nullptr with has_pub false: the base point (noise_aead_dev_dh_public).
+   NOISE_ERROR_NONE with n == 0 means "nothing to do". */
+inline int check_dh(int dh_id, const void *priv, uint64_t priv_stride, bool has_pub, const void *pub,
+                    uint64_t pub_stride, uint32_t n, const void *out)
+{
+    if (dh_id != NOISE_DH_CURVE25519) return NOISE_ERROR_UNKNOWN_ID;
+    if (!n) return NOISE_ERROR_NONE;
+    if (!priv || !out || (has_pub && !pub)) return NOISE_ERROR_INVALID_PARAM;
+    if ((priv_stride && priv_stride < 32) || (has_pub && pub_stride && pub_stride < 32))
+        return NOISE_ERROR_INVALID_PARAM;
+    const Span o = dh_key_span(out, 32, n);
+    if (meet(o, dh_key_span(priv, priv_stride, n)) || (has_pub && meet(o, dh_key_span(pub, pub_stride, n))))
+        return NOISE_ERROR_INVALID_PARAM;
+    return NOISE_ERROR_NONE;
+}
+
 /* ------------------------------------------------------ the facts of a job
    FAST layout (chachapoly.hip): 16-B aligned record slots whose input may be
    read up to roundup64(len) — and, for open, holds CT || tag. */

@@ -42,6 +42,7 @@ HASH_BLAKE2s = NOISE_ID("H", 1)  # constants.h:43-46
 HASH_BLAKE2b = NOISE_ID("H", 2)
 HASH_SHA256 = NOISE_ID("H", 3)
 HASH_SHA512 = NOISE_ID("H", 4)
+DH_CURVE25519 = NOISE_ID("D", 1)  # constants.h:51
 HASH_LEN = {HASH_BLAKE2s: 32, HASH_BLAKE2b: 64, HASH_SHA256: 32, HASH_SHA512: 64}
 
 
@@ -147,6 +148,8 @@ def lib() -> C.CDLL:
         "noise_aead_dev_default_lanes": (i, [i, C.c_uint32]),
         "noise_aead_dev_duplex_lanes": (i, [i, C.c_uint32]),
         "noise_aead_dev_pad": (i, [vp, vp, C.c_uint64, vp, C.c_uint32, C.c_uint32, i, vp, vp]),
+        "noise_aead_dev_dh_calculate": (i, [i, vp, C.c_uint64, vp, C.c_uint64, C.c_uint32, vp, vp]),
+        "noise_aead_dev_dh_public": (i, [i, vp, C.c_uint64, C.c_uint32, vp, vp]),
         "noise_strerror": (i, [i, C.c_char_p, sz]),
         "noise_perror": (None, [C.c_char_p, i]),
         "noise_aead_debug_batch_stats": (None, [P(C.c_uint64), P(C.c_uint64)]),
@@ -436,6 +439,21 @@ def dev_and_hash(open_: bool, cipher: int, hash_id: int, *, ctx_base: int, h: in
 
 def dev_split(hash_id: int, *, ck: int, n: int, k1: int, k2: int, stream: int = 0) -> int:
     return lib().noise_aead_dev_split(hash_id, ck, n, k1, k2, stream or None)
+
+
+def dev_dh_calculate(dh_id: int, *, priv: int, priv_stride: int = 32, pub: int, pub_stride: int = 32,
+                     n: int, shared: int, stream: int = 0) -> int:
+    """noise_aead_dev_dh_calculate: n shared keys, packed 32 bytes apart at
+    `shared` (a stride of 0: one key for all n sessions)."""
+    return lib().noise_aead_dev_dh_calculate(dh_id, priv or None, priv_stride, pub or None, pub_stride,
+                                             n, shared or None, stream or None)
+
+
+def dev_dh_public(dh_id: int, *, priv: int, priv_stride: int = 32, n: int, pub_out: int,
+                  stream: int = 0) -> int:
+    """noise_aead_dev_dh_public: the public key of each of n private keys."""
+    return lib().noise_aead_dev_dh_public(dh_id, priv or None, priv_stride, n, pub_out or None,
+                                          stream or None)
 
 
 def dev_fill_splitmix(d_out: int, nbytes: int, seed: int, word0: int = 0, stream: int = 0) -> int:

@@ -1,0 +1,131 @@
+"""Batched X25519 without a GPU: noise_aead_dev_dh_calculate / _dh_public.
+
+(a) The big-integer ladder of tests/x25519_ref.py — the checker the GPU tests
+    use — equals the reference's curve25519_donna and
+    curved25519_scalarmult_basepoint on every case of tests/golden/x25519.json
+    (gen_x25519.py): the RFC 7748 vectors, the edge public values, the small
+    order points, the scalars that clamping changes, 64 random pairs.
+(b) noise-c_amd/asan/dh_check.cpp, a stand-alone program (`make -C noise-c_amd
+    dh_check`: g++ -fsanitize=address,undefined -fno-sanitize-recover=all)
+    over csrc/fe25519.h — the one source of the field arithmetic, ladder,
+    inversion and freeze, which the kernels compile too — computes every
+    fixture case on the CPU and checks the entry points' argument rules
+    (csrc/dispatch.h check_dh) against a byte-by-byte reading of the header.
+    It runs here as a plain child process.
+(c) The argument rules through the library itself; no launch happens.
+(d) The DH translation unit compiled for gfx950 reports no scratch memory for
+    any kernel: no limb of a private key is spilled to device memory.
+"""
+import os
+import re
+import subprocess
+
+import x25519_ref as X
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+LIB = os.path.join(ROOT, "noise-c_amd")
+CHECK = os.path.join(LIB, "asan", "dh_check")
+ROCM = os.environ.get("ROCM", "/opt/rocm")
+
+
+def test_checker_equals_the_reference_fixture():
+    cases = X.fixture_cases()
+    names = [c["name"] for c in cases]
+    assert len(cases) >= 2 + 2 + 10 + 8 + 64 and len(set(names)) == len(names)
+    assert cases[0]["shared"] == "c3da55379de9c6908e94ea4df28d084f32eccf03491c71f754b4075577a28552"
+    for c in cases:
+        priv, pub = bytes.fromhex(c["priv"]), bytes.fromhex(c["pub"])
+        assert X.x25519(priv, pub).hex() == c["shared"], c["name"]
+        assert X.x25519_base(priv).hex() == c["public"], c["name"]
+    by = {c["name"]: c for c in cases}
+    # what the header promises about the edge values
+    for n in ("u=0", "u=1", "u=p-1", "u=p", "u=p+1", "u=order8a", "u=order8b"):
+        assert by[n]["shared"] == "00" * 32, n
+    assert by["u=9"]["shared"] == by["u=9"]["public"]
+    assert by["u=0xff..ff"]["shared"] == X.x25519(bytes.fromhex(by["u=0xff..ff"]["priv"]),
+                                                  (18).to_bytes(32, "little")).hex()
+
+
+def test_shared_ladder_and_argument_rules_under_sanitizers():
+    subprocess.run(["make", "-s", "-C", LIB, "dh_check"], check=True)
+    cases = X.fixture_cases()
+    feed = "".join(f"{c['priv']} {c['pub']} {c['shared']} {c['public']}\n" for c in cases)
+    r = subprocess.run([CHECK], input=feed, capture_output=True, text=True, timeout=120)
+    out = r.stdout[-4000:] + r.stderr[-4000:]
+    assert r.returncode == 0, out
+    assert "AddressSanitizer" not in out and "runtime error" not in out, out
+    line = [l for l in r.stdout.splitlines() if l.startswith("dh_check:")][-1].split()
+    assert int(line[1]) == len(cases) and int(line[3]) > 50000 and line[5] == "0", line
+    # a wrong expected value is noticed: the program does compare
+    bad = cases[0]["shared"][:-1] + ("0" if cases[0]["shared"][-1] != "0" else "1")
+    r = subprocess.run([CHECK], input=f"{cases[0]['priv']} {cases[0]['pub']} {bad} {cases[0]['public']}\n",
+                       capture_output=True, text=True, timeout=120)
+    assert r.returncode == 1 and "FAIL calculate" in r.stderr, r.stdout + r.stderr
+
+
+def test_dev_dh_argument_rules(aead):
+    """Validation before any launch (no GPU work), on never-dereferenced pointers."""
+    A = aead
+    ID = A.DH_CURVE25519
+    assert ID == 0x4401
+    ok = dict(priv=0x10000, priv_stride=32, pub=0x20000, pub_stride=32, n=4, shared=0x30000)
+
+    def calc(**kw):
+        return A.dev_dh_calculate(kw.pop("dh_id", ID), **{**ok, **kw})
+
+    def public(**kw):
+        a = {"priv": 0x10000, "priv_stride": 32, "n": 4, "pub_out": 0x30000, **kw}
+        return A.dev_dh_public(a.pop("dh_id", ID), **a)
+
+    assert calc(dh_id=0x4402) == A.ERROR_UNKNOWN_ID      # Curve448: not yet
+    assert calc(dh_id=0x4801, n=0) == A.ERROR_UNKNOWN_ID
+    assert public(dh_id=0) == A.ERROR_UNKNOWN_ID
+    assert calc(n=0, priv=0, pub=0, shared=0, priv_stride=5) == A.ERROR_NONE
+    assert public(n=0, priv=0, pub_out=0) == A.ERROR_NONE
+    for k in ("priv", "pub", "shared"):
+        assert calc(**{k: 0}) == A.ERROR_INVALID_PARAM, k
+    for k in ("priv", "pub_out"):
+        assert public(**{k: 0}) == A.ERROR_INVALID_PARAM, k
+    for s in (1, 31):
+        assert calc(priv_stride=s) == A.ERROR_INVALID_PARAM
+        assert calc(pub_stride=s) == A.ERROR_INVALID_PARAM
+        assert public(priv_stride=s) == A.ERROR_INVALID_PARAM
+    # the output may touch an input span but not meet it
+    assert calc(shared=0x10000) == A.ERROR_INVALID_PARAM
+    assert calc(shared=0x10000 + 4 * 32 - 1) == A.ERROR_INVALID_PARAM
+    assert calc(shared=0x20000 - 4 * 32 + 1) == A.ERROR_INVALID_PARAM
+    assert calc(priv_stride=0, shared=0x10000 + 31) == A.ERROR_INVALID_PARAM
+    assert calc(pub_stride=40, shared=0x20000 + 3 * 40 + 31) == A.ERROR_INVALID_PARAM
+    assert public(pub_out=0x10000 + 4 * 32 - 1) == A.ERROR_INVALID_PARAM
+    assert public(pub_out=0x10000 - 4 * 32 + 1) == A.ERROR_INVALID_PARAM
+    assert public(n=1, pub_out=0x10000 + 31) == A.ERROR_INVALID_PARAM
+
+
+def test_dh_kernels_use_no_scratch():
+    """The compiler's own report for the DH unit (as tools/kres.py reads it)."""
+    cmd = [f"{ROCM}/bin/hipcc", "-O3", "-std=c++17", "--offload-arch=gfx950", "-fPIC", "-I../include", "-Icsrc",
+           "--cuda-device-only", "-c", "csrc/launch_dh.hip", "-o", "/dev/null",
+           "-Rpass-analysis=kernel-resource-usage"]
+    r = subprocess.run(cmd, cwd=LIB, capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0, r.stderr[-3000:]
+    cur, rows = None, {}
+    for line in r.stderr.splitlines():
+        m = re.search(r"remark:\s+(.*)", line)
+        if not m:
+            continue
+        t = m.group(1)
+        if t.startswith("Function Name:"):
+            cur = t.split(":", 1)[1].split(" [")[0].strip()
+            rows[cur] = {}
+        elif cur and ":" in t:
+            k, v = t.split(":", 1)
+            rows[cur][k.strip()] = v.split("[-R")[0].strip()
+    kernels = {k: v for k, v in rows.items() if "x25519_batch" in k}
+    assert len(kernels) == 2, list(rows)  # the base point and the per-session point
+    for name, row in rows.items():
+        report = (f"{name}: VGPRs {row.get('VGPRs')}, occupancy {row.get('Occupancy [waves/SIMD]')} waves/SIMD, "
+                  f"scratch {row.get('ScratchSize [bytes/lane]')} bytes/lane, "
+                  f"spilled VGPRs {row.get('VGPRs Spill')}")
+        print(report)
+        assert row.get("ScratchSize [bytes/lane]") == "0", report
+        assert row.get("VGPRs Spill") == "0" and row.get("SGPRs Spill") == "0", report

@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Register / scratch / occupancy / LDS report of the library's kernels,
-from hipcc's kernel-resource-usage remarks (no GPU needed): the four device
+from hipcc's kernel-resource-usage remarks (no GPU needed): the five device
 translation units of `make asm`, compiled side by side, one line per kernel
 sorted by unit and name, so that two runs compare with diff(1).
 usage: python tools/kres.py [name-filter-regex] > report.txt   (takes minutes)"""
@@ -13,7 +13,7 @@ from concurrent.futures import ThreadPoolExecutor
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 ROCM = os.environ.get("ROCM", "/opt/rocm")
-UNITS = ["aead_api", "launch_chacha", "launch_aes", "worker"]
+UNITS = ["aead_api", "launch_chacha", "launch_aes", "worker", "launch_dh"]
 
 
 def remarks(unit):
