@@ -526,6 +526,28 @@ void noise_aead_debug_worker_leave_info(int group, int slot, unsigned *out);
  *   "kernel<template arguments> grid=.. block=.. ..." (dispatch.h plan_print);
  *   "none ..." before the first.  Returns the length it has (snprintf's). */
 int noise_aead_debug_last_plan(char *buf, size_t n);
+/* noise_aead_debug_f25_op: one operation of the X25519 field arithmetic
+ *   (csrc/fe25519.h) on each of n elements, one lane each, so that a test can
+ *   put a single carry chain of the device build on its rare paths.  Element
+ *   i is the 32 little-endian bytes at d_a + 32*i (and d_b + 32*i for add,
+ *   sub and mul; d_b may be NULL for the others); any 256-bit value is an
+ *   operand.  The result at d_out + 32*i is the operation's raw output: some
+ *   256-bit value congruent to the answer mod 2^255 - 19, canonical only for
+ *   FREEZE.  INVERT gives 0 for an operand that is 0 mod 2^255 - 19.
+ *   An op outside the list gives NOISE_ERROR_UNKNOWN_ID; n == 0 gives
+ *   NOISE_ERROR_NONE and no launch; a NULL pointer, or a d_out range that
+ *   meets an operand range, gives NOISE_ERROR_INVALID_PARAM.
+ *   Device pointers, asynchronous on `stream`. */
+#define NOISE_AEAD_F25_ADD        0
+#define NOISE_AEAD_F25_SUB        1
+#define NOISE_AEAD_F25_MUL        2
+#define NOISE_AEAD_F25_SQ         3
+#define NOISE_AEAD_F25_MUL_121665 4
+#define NOISE_AEAD_F25_MUL_9      5
+#define NOISE_AEAD_F25_FREEZE     6
+#define NOISE_AEAD_F25_INVERT     7
+int noise_aead_debug_f25_op(int op, const uint8_t *d_a, const uint8_t *d_b, uint32_t n,
+                            uint8_t *d_out, void *stream);
 
 /* Default lanes per record the library picks for a standalone uniform seal
  * or open of n records (noise_aead_dev_{seal,open}_uniform, lanes 0) in a

@@ -10,23 +10,34 @@
  *             private  public-value  shared  public-key
  *           shared must be X25519(private, public-value) and public-key
  *           X25519(private, 9); the test feeds tests/golden/x25519.json.
+ *           A line "f25 <op> <a> <b> <result>" is one field operation instead:
+ *           op is add, sub, mul, sq, freeze, invert or mul_small_<k> (decimal
+ *           k < 2^26), a and b any 256-bit values (b is read by add, sub and
+ *           mul only), result the canonical residue, each the hex of 32
+ *           little-endian bytes.  The operation's raw output is frozen and
+ *           compared; freeze's own output is compared as it is.  The test
+ *           feeds every vector of tests/f25_cases.py.
  *   then    the argument rules against a byte-by-byte reading of the header:
  *           every small layout (pointers, strides, counts), the spans that
  *           touch without meeting, stride 0, n = 1, and values at the edges
  *           of 64-bit arithmetic, over never-dereferenced pointers.
  *
- * Last line: "dh_check: <cases> cases <checks> checks <failures> failures".
+ * Output: "dh_check f25: <vectors> vectors <failures> failures", then the last
+ * line "dh_check: <cases> cases <checks> checks <failures> failures" (cases
+ * counts the X25519 lines, failures everything).
  */
 #include "../csrc/dispatch.h"
 #include "../csrc/fe25519.h"
 
 #include <cinttypes>
+#include <cstdlib>
+#include <cstring>
 #include <string>
 #include <vector>
 
 using namespace na;
 
-static long g_checks, g_failures;
+static long g_checks, g_failures, g_f25, g_f25_failures;
 
 static void fail(const char *what, const std::string &detail)
 {
@@ -65,11 +76,70 @@ static std::vector<uint8_t> lane(const std::vector<uint8_t> &priv, const std::ve
     return out;
 }
 
+/* one "f25" line (after the word): what one lane of f25_op_batch does, then
+   the freeze, again on heap buffers of exactly 32 bytes */
+static void run_f25(const char *p)
+{
+    const char *const line = p;
+    char op[32];
+    std::vector<uint8_t> f[3];
+    size_t len = 0;
+    while (p[len] && p[len] != ' ' && p[len] != '\n') ++len;
+    bool ok = len > 0 && len < sizeof op;
+    if (ok) {
+        memcpy(op, p, len);
+        op[len] = 0;
+        p += len;
+    }
+    for (int k = 0; k < 3 && ok; ++k) {
+        while (*p == ' ') ++p;
+        len = 0;
+        while (p[len] && p[len] != ' ' && p[len] != '\n') ++len;
+        ok = unhex(p, len, f[k]);
+        p += len;
+    }
+    F25 r;
+    bool frozen = false;
+    if (ok) {
+        const F25 a = f25_load(f[0].data()), b = f25_load(f[1].data());
+        if (!strcmp(op, "add")) r = f25_add(a, b);
+        else if (!strcmp(op, "sub")) r = f25_sub(a, b);
+        else if (!strcmp(op, "mul")) r = f25_mul(a, b);
+        else if (!strcmp(op, "sq")) r = f25_sq(a);
+        else if (!strcmp(op, "invert")) r = f25_invert(a);
+        else if (!strcmp(op, "freeze")) {
+            r = f25_freeze(a);
+            frozen = true;
+        } else if (!strncmp(op, "mul_small_", 10)) {
+            char *end;
+            const unsigned long k = strtoul(op + 10, &end, 10);
+            ok = end != op + 10 && !*end && k < (1ul << 26);
+            if (ok) r = f25_mul_small(a, (uint32_t)k);
+        } else
+            ok = false;
+    }
+    if (!ok) {
+        fail("input", std::string("f25 ") + line);
+        return;
+    }
+    ++g_f25;
+    std::vector<uint8_t> out(32, 0xA5);
+    f25_store(out.data(), frozen ? r : f25_freeze(r));
+    if (out != f[2]) {
+        ++g_f25_failures;
+        fail((std::string("f25 ") + op).c_str(), hex(f[0].data()) + " " + hex(f[1].data()) + " -> " + hex(out.data()));
+    }
+}
+
 static long run_cases()
 {
     long cases = 0;
     char line[512];
     while (fgets(line, sizeof line, stdin)) {
+        if (!strncmp(line, "f25 ", 4)) {
+            run_f25(line + 4);
+            continue;
+        }
         std::vector<uint8_t> f[4];
         const char *p = line;
         bool ok = true;
@@ -199,6 +269,7 @@ int main()
 {
     const long cases = run_cases();
     run_rules();
+    printf("dh_check f25: %ld vectors %ld failures\n", g_f25, g_f25_failures);
     printf("dh_check: %ld cases %ld checks %ld failures\n", cases, g_checks, g_failures);
     return g_failures ? 1 : 0;
 }

@@ -5,7 +5,9 @@
  * launch_dh.hip from it, plain g++ builds asan/dh_check.cpp from it, so the
  * CPU check under ASan/UBSan runs the code the GPU runs.  The only
  * device-only builtins are the 32-bit add-with-carry / subtract-with-borrow
- * (f25_addc / f25_subb), each with a plain C++ form beside it.
+ * (f25_addc / f25_subb), each with a plain C++ form beside it; the builtin
+ * forms are checked on the device, one operation at a time and at the carry
+ * edges, by tests/test_gpu_f25.py (noise_aead_debug_f25_op, debug_f25.hip).
  *
  * Layout: eight 32-bit limbs, radix 2^32, little endian — the 32 key bytes as
  * they lie in memory.  A value is any 256-bit number; it stands for its

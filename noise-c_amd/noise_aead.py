@@ -155,6 +155,7 @@ def lib() -> C.CDLL:
         "noise_aead_debug_batch_stats": (None, [P(C.c_uint64), P(C.c_uint64)]),
         "noise_aead_debug_last_freed_ctx": (vp, [P(sz)]),
         "noise_aead_debug_last_plan": (i, [C.c_char_p, sz]),
+        "noise_aead_debug_f25_op": (i, [i, vp, vp, C.c_uint32, vp, vp]),
         "noise_aead_dev_fill_splitmix": (i, [vp, C.c_uint64, C.c_uint64, C.c_uint64, vp]),
     }
     for name, (res, args) in sigs.items():
@@ -466,6 +467,16 @@ def last_plan() -> str:
     buf = C.create_string_buffer(256)
     lib().noise_aead_debug_last_plan(buf, len(buf))
     return buf.value.decode()
+
+
+# the operations of noise_aead_debug_f25_op (NOISE_AEAD_F25_*)
+F25_ADD, F25_SUB, F25_MUL, F25_SQ, F25_MUL_121665, F25_MUL_9, F25_FREEZE, F25_INVERT = range(8)
+
+
+def debug_f25_op(op: int, *, a: int, b: int = 0, n: int, out: int, stream: int = 0) -> int:
+    """noise_aead_debug_f25_op: one field operation of csrc/fe25519.h on each
+    of n packed 32-byte elements; the raw result, 32 bytes each, at `out`."""
+    return lib().noise_aead_debug_f25_op(op, a or None, b or None, n, out or None, stream or None)
 
 
 def dev_default_lanes(cipher: int, n_records: int) -> int:

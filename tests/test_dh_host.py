@@ -15,11 +15,18 @@
 (c) The argument rules through the library itself; no launch happens.
 (d) The DH translation unit compiled for gfx950 reports no scratch memory for
     any kernel: no limb of a private key is spilled to device memory.
+(e) The field operations one at a time, on the operands of tests/f25_cases.py:
+    the coverage condition (the edge set alone takes every named carry path
+    of every operation, the random operands none of the rare ones), every
+    vector through csrc/fe25519.h in dh_check under ASan/UBSan, and the
+    argument rules of noise_aead_debug_f25_op, which tests/test_gpu_f25.py
+    runs the same vectors through.
 """
 import os
 import re
 import subprocess
 
+import f25_cases as F
 import x25519_ref as X
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -61,6 +68,88 @@ def test_shared_ladder_and_argument_rules_under_sanitizers():
     r = subprocess.run([CHECK], input=f"{cases[0]['priv']} {cases[0]['pub']} {bad} {cases[0]['public']}\n",
                        capture_output=True, text=True, timeout=120)
     assert r.returncode == 1 and "FAIL calculate" in r.stderr, r.stdout + r.stderr
+
+
+def test_f25_edge_set_takes_every_named_path():
+    """The coverage condition of tests/f25_cases.py.  The restated steps must
+    also give the right residue for every vector, or the path names mean
+    nothing."""
+    assert len(set(F.E)) == len(F.E) and all(0 <= v < F.M for v in F.E)
+    assert set(F.PATHS) == set(F.OPS)
+    for op in F.OPS:
+        taken = {}
+        for a, b in F.edge_vectors(op):
+            raw, names = F.paths(op, a, b)
+            assert raw % F.P == F.expected(op, a, b), (op, hex(a), hex(b))
+            assert names <= set(F.PATHS[op]), (op, names)
+            for name in names:
+                taken[name] = taken.get(name, 0) + 1
+        print(op, taken)
+        assert all(taken.get(name, 0) >= 1 for name in F.PATHS[op]), (op, taken)
+        assert len(F.random_vectors(op)) == F.RANDOM_PAIRS
+        for a, b in F.random_vectors(op):
+            raw, names = F.paths(op, a, b)
+            assert raw % F.P == F.expected(op, a, b), (op, hex(a), hex(b))
+            assert not names & set(F.RARE), (op, hex(a), hex(b), names)
+        assert len(F.vectors(op)) % 64 != 0  # a launch ends inside a workgroup
+    # freeze restated gives the canonical value itself, and the expectations
+    # are what they say: in [0, p), a * a^-1 = 1
+    for a in F.E:
+        assert F.paths("freeze", a)[0] == a % F.P
+        inv = F.expected("invert", a)
+        assert 0 <= inv < F.P and a * inv % F.P == (0 if a % F.P == 0 else 1)
+
+
+def test_f25_field_operations_under_sanitizers():
+    """Every vector of every operation through the header on the CPU."""
+    subprocess.run(["make", "-s", "-C", LIB, "dh_check"], check=True)
+    feed = "".join(F.check_lines(op) for op in F.OPS)
+    total = sum(len(F.vectors(op)) for op in F.OPS)
+    r = subprocess.run([CHECK], input=feed, capture_output=True, text=True, timeout=120)
+    out = r.stdout[-4000:] + r.stderr[-4000:]
+    assert r.returncode == 0, out
+    assert "AddressSanitizer" not in out and "runtime error" not in out, out
+    lines = r.stdout.splitlines()
+    f25 = [l for l in lines if l.startswith("dh_check f25:")][-1].split()
+    assert int(f25[2]) == total and f25[4] == "0", f25
+    last = [l for l in lines if l.startswith("dh_check:")][-1].split()
+    assert last[1] == "0" and int(last[3]) > 50000 and last[5] == "0", last
+    # a wrong expected value is noticed, for the operation that is frozen
+    # here and for the one that freezes itself
+    for op in ("sub", "freeze"):
+        a, b = F.vectors(op)[5]
+        wrong = (F.expected(op, a, b) + 1) % F.P
+        r = subprocess.run([CHECK], input=f"f25 {op} {F.le32(a).hex()} {F.le32(b).hex()} {F.le32(wrong).hex()}\n",
+                           capture_output=True, text=True, timeout=120)
+        assert r.returncode == 1 and f"FAIL f25 {op}" in r.stderr, r.stdout + r.stderr
+        assert "dh_check f25: 1 vectors 1 failures" in r.stdout
+    # and a line it cannot read is a failure, not a skipped vector
+    r = subprocess.run([CHECK], input="f25 cube 00 00 00\n", capture_output=True, text=True, timeout=120)
+    assert r.returncode == 1 and "FAIL input" in r.stderr, r.stdout + r.stderr
+
+
+def test_debug_f25_op_argument_rules(aead):
+    """Validation before any launch (no GPU work), on never-dereferenced pointers."""
+    A = aead
+    assert [A.F25_ADD, A.F25_SUB, A.F25_MUL, A.F25_SQ, A.F25_MUL_121665, A.F25_MUL_9, A.F25_FREEZE,
+            A.F25_INVERT] == [F.OPS[op][0] for op in F.DEVICE_OPS] == list(range(8))
+    ok = dict(a=0x10000, b=0x20000, n=4, out=0x30000)
+    for op in (-1, 8, 0x4401):
+        assert A.debug_f25_op(op, **ok) == A.ERROR_UNKNOWN_ID
+        assert A.debug_f25_op(op, **{**ok, "n": 0}) == A.ERROR_UNKNOWN_ID
+    for op in range(8):
+        binary = op <= A.F25_MUL
+        assert A.debug_f25_op(op, a=0, b=0, n=0, out=0) == A.ERROR_NONE
+        assert A.debug_f25_op(op, **{**ok, "a": 0}) == A.ERROR_INVALID_PARAM
+        assert A.debug_f25_op(op, **{**ok, "out": 0}) == A.ERROR_INVALID_PARAM
+        if binary:
+            assert A.debug_f25_op(op, **{**ok, "b": 0}) == A.ERROR_INVALID_PARAM
+        # the output may touch an operand range but not meet it
+        assert A.debug_f25_op(op, **{**ok, "out": 0x10000}) == A.ERROR_INVALID_PARAM
+        assert A.debug_f25_op(op, **{**ok, "out": 0x10000 + 4 * 32 - 1}) == A.ERROR_INVALID_PARAM
+        assert A.debug_f25_op(op, **{**ok, "out": 0x10000 - 4 * 32 + 1}) == A.ERROR_INVALID_PARAM
+        if binary:
+            assert A.debug_f25_op(op, **{**ok, "out": 0x20000 + 4 * 32 - 1}) == A.ERROR_INVALID_PARAM
 
 
 def test_dev_dh_argument_rules(aead):
