@@ -7,6 +7,8 @@ gcm_duplex_staged where the duplex switch asks for it.
 
   aes_shapes_check.py ragged   the windowed ragged kernel in the forced shape
   aes_shapes_check.py duplex   the same, then the duplex of two uniform jobs
+  aes_shapes_check.py classes  the ragged kernel over the (len, ad_len) list of
+                               tests/length_classes.py for its lanes per record
 
 Prints "ok N" (N records checked) and exits non-zero on the first mismatch.
 """
@@ -42,13 +44,26 @@ def ran_forced_shape(open_, fast, ct):
     assert aead.last_plan().split()[0] == want, (aead.last_plan(), want)
 
 
-def ragged(orc, fast, ct):
-    """1100 records, lanes_per_record = 4 (off gcm_wide): 256-record windows
-    with a partial last one (512 at w1024r2); per-state runs of 1..300 records
+def drawn_lengths(rng, count):
+    """lengths 0..600 with each of FIXED_LENS at 11 places (all window
+    positions), AD of 1, 16, 21 or 32 bytes on every third record"""
+    lens = rng.integers(0, 601, count)
+    for j, L in enumerate(FIXED_LENS):
+        lens[7 * j + 5::101] = L
+    adls = np.where(np.arange(count) % 3 == 0, rng.choice([1, 16, 21, 32], count), 0)
+    return lens, adls
+
+
+def ragged(orc, fast, ct, pairs=None):
+    """lanes_per_record = 4 (off gcm_wide; the forced shape decides the lanes
+    that run).  Without pairs: 1100 records of drawn_lengths(): 256-record
+    windows with a partial last one (512 at w1024r2).  With pairs: one record
+    per (len, ad_len), AD slots of 64 bytes.  Per-state runs of 1..300 records,
     so windows hold one, two and three or more states (both LDS slots and the
     global-context path)."""
     rng = np.random.default_rng(9001 + 2 * fast + ct)
-    count = 1100
+    count = len(pairs) if pairs else 1100
+    ad_slot = 64 if pairs else AD_SLOT
     runs = []
     while sum(runs) < count:
         runs.append(int(rng.choice([1, 3, 40, 130, 300])))
@@ -56,22 +71,22 @@ def ragged(orc, fast, ct):
     keys = rng.integers(0, 256, (len(runs), 32), dtype=np.uint8)
     ctx, _k = prepare(aead, AES, keys)
     cb = aead.dev_ctx_bytes(AES)
-    lens = rng.integers(0, 601, count)
-    for j, L in enumerate(FIXED_LENS):  # each fixed length at 11 places, all window positions
-        lens[7 * j + 5::101] = L
-    adls = np.where(np.arange(count) % 3 == 0, rng.choice([1, 16, 21, 32], count), 0)
+    if pairs:
+        lens, adls = (np.array([p[i] for p in pairs], dtype=np.int64) for i in (0, 1))
+    else:
+        lens, adls = drawn_lengths(rng, count)
     slot = (lens + 16 + 63) // 64 * 64 if fast else lens + 16 + 5
     offs = np.zeros(count, dtype=np.int64)
     offs[1:] = np.cumsum(slot)[:-1]
     total = int(offs[-1] + slot[-1]) + 64
     pt = rng.integers(0, 256, total, dtype=np.uint8)
-    ad = rng.integers(0, 256, count * AD_SLOT, dtype=np.uint8)
+    ad = rng.integers(0, 256, count * ad_slot, dtype=np.uint8)
     nonces = rng.integers(0, 2**62, count, dtype=np.int64).astype(np.uint64)
     recs = np.zeros(count, dtype=REC_DT)
     recs["in_off"] = recs["out_off"] = offs
     recs["nonce"] = nonces
     recs["ctx_off"] = state_of.astype(np.uint64) * cb
-    recs["ad_off"] = np.arange(count) * AD_SLOT
+    recs["ad_off"] = np.arange(count) * ad_slot
     recs["len"] = lens
     recs["ad_len"] = adls
     flags = (aead.FLAG_FAST if fast else 0) | (FLAG_CT_GHASH if ct else 0)
@@ -84,7 +99,7 @@ def ragged(orc, fast, ct):
     exp = np.full(total, 0xA5, dtype=np.uint8)
     for i in range(count):
         o, L = int(offs[i]), int(lens[i])
-        a = bytes(ad[AD_SLOT * i: AD_SLOT * i + int(adls[i])])
+        a = bytes(ad[ad_slot * i: ad_slot * i + int(adls[i])])
         c = orc.encrypt(AES, bytes(keys[state_of[i]]), int(nonces[i]), bytes(pt[o:o + L]), a)
         exp[o:o + L + 16] = np.frombuffer(c, dtype=np.uint8)
     d_pt = dev(pt)
@@ -145,9 +160,14 @@ def main():
     orc = O.Oracle()
     aead.lib()
     n = 0
+    pairs = None
+    if sys.argv[1:] == ["classes"]:
+        import length_classes
+        lanes = int(SHAPES[os.environ["NOISE_AEAD_GCM_SHAPE"]].rsplit(",", 1)[1])
+        pairs = length_classes.full("gcm", lanes)
     for fast in (True, False):
         for ct in (False, True):
-            n += ragged(orc, fast, ct)
+            n += ragged(orc, fast, ct, pairs)
     if sys.argv[1:] == ["duplex"]:
         for flags in (0, FLAG_CT_GHASH):
             n += duplex(orc, flags)
