@@ -5,7 +5,11 @@ the resident worker, not a kernel launch.  ChaChaPoly records of up to 63
 units whose Poly1305 input is at most 256 blocks run the latency-first path
 (four lanes per ChaCha block, a Poly1305 tree over one block per lane);
 longer ones the multi-pass path (P ChaCha passes, G Poly1305 blocks per lane);
-AES-GCM gcm_wide_record.  Every case is checked
+AES-GCM gcm_wide_record in place in LDS.  The record lengths come from two
+sources: the hand-picked LENS x ADS below, and the cases that
+tests/length_classes.py derives from the worker's own arithmetic (tree width,
+Horner depth G, ChaCha passes P, the worker_fast_fits border, the transport's
+chunks and raw tail), run by the test_worker_length_classes_* tests.  Every case is checked
 byte for byte against the oracle (the restatement of
 src/backend/ref/cipher-chachapoly.c:107-143 and cipher-aesgcm.c:156-188),
 then opened back, then opened tampered: MAC failure, buffer and nonce left
@@ -22,9 +26,12 @@ pytestmark = pytest.mark.gpu
 
 CHACHA, AES = 0x4301, 0x4302
 
-# the fast path's edges: one unit, unit boundaries, 63 units (4032 B), and
-# the 256-block Poly limit with a 256-byte AD (3824 B), then the multi-pass
-# path (worker_chacha_multi) up to the 65519-byte maximum
+# hand-picked lengths: one unit, unit boundaries, 63 units (4032 B), the
+# 256-block Poly limit with a 256-byte AD (3824 B), then some of the multi-pass
+# path (worker_chacha_multi) up to the 65519-byte maximum.  They are a sample,
+# not the paths' cases: tests/length_classes.py derives those (wfast, wmulti,
+# wtransport) and test_worker_length_classes_* below run them;
+# tests/test_length_classes_host.py counts what this list reaches of them
 LENS = [0, 1, 15, 16, 17, 63, 64, 65, 100, 127, 128, 129, 1023, 1024, 1025, 1400,
         2047, 2048, 3823, 3824, 3825, 4031, 4032, 4033, 4096, 8000, 16384, 16385, 20000,
         40001, 65519]
@@ -53,8 +60,6 @@ def test_worker_single_records_vs_oracle(aead, gpu, oracle, cipher):
     assert tx.set_nonce(n0) == 0 and rx.set_nonce(n0) == 0
     n = n0
     for L, A in _cases():
-        if cipher == AES and L > 4096:
-            continue  # gcm_wide_record: covered elsewhere, slow on one workgroup
         pt = bytes(rnd.randrange(256) for _ in range(L))
         ad = bytes(rnd.randrange(256) for _ in range(A))
         ct = tx.seal(pt, ad)
@@ -121,6 +126,71 @@ def test_worker_in_place_buffer_semantics(aead, gpu, oracle):
     assert bytes(mem)[:L + 16] == oracle.encrypt(CHACHA, key, 0, pt)
     assert bytes(mem)[L + 16:] == bytes([0xAB]) * 48
     st.free()
+
+
+def _mode(args, env_extra):
+    env = dict(os.environ, **env_extra)
+    r = subprocess.run([sys.executable, "-u", os.path.join(os.path.dirname(__file__), "worker_mode_check.py")] + args,
+                       env=env, timeout=110, capture_output=True, text=True)
+    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
+    return r.stdout
+
+
+def _after(out, word):
+    return int(out.split(word)[-1].split()[0])
+
+
+@pytest.mark.parametrize("vram", ["0", "1"])
+def test_worker_length_classes_chacha(gpu, vram):
+    """Every case of the worker's own geometry (tests/length_classes.py):
+    the 312 cases of worker_chacha_fast's tree and tail, both sides of
+    worker_fast_fits's border for every AD length, the 160 records that reach
+    worker_chacha_multi's 165 marginals (every G and P in 1..17) and the
+    transport's cases for the placement in use, each sealed against the
+    oracle, opened tampered and opened back, in either placement
+    (tests/worker_mode_check.py --classes chacha)."""
+    import length_classes as LC
+    out = _mode(["--classes", "chacha"], {"NOISE_AEAD_WORKER_VRAM": vram})
+    placement = _after(out, "placement")
+    assert placement == 1 if vram == "0" else placement in (1, 2)
+    transport = len({x[1:] for x in LC.full("wtransport", placement - 1)})
+    assert _after(out, "classes") == 312 + 19 + 160 + transport
+
+
+@pytest.mark.parametrize("vram,ct", [("0", "0"), ("1", "0"), ("1", "1")])
+def test_worker_length_classes_aes(gpu, vram, ct):
+    """gcm_wide_record in place in the worker's LDS over full("gcm_wide",
+    ct): every case of the 8-chain deal, the lengths around EARLY and the
+    seal's second round (M = 255, 256, 257: records over 4096 bytes, which
+    test_worker_single_records_vs_oracle leaves out), with the tables in both
+    placements and with the constant-time GHASH (NOISE_AEAD_CT_GHASH=1) in
+    device memory where the device has it (tests/worker_mode_check.py
+    --classes aes)."""
+    import length_classes as LC
+    out = _mode(["--classes", "aes"], {"NOISE_AEAD_WORKER_VRAM": vram, "NOISE_AEAD_CT_GHASH": ct})
+    placement = _after(out, "placement")
+    assert placement == 1 if vram == "0" else placement in (1, 2)
+    assert _after(out, "classes") == len(LC.full("gcm_wide", 0, ct == "1"))
+
+
+def test_worker_slot_serves_states_in_turn(gpu):
+    """One slot serving three AES-GCM and two ChaChaPoly states in turn
+    (tests/worker_mode_check.py --sequence): the two-entry cache of AES-GCM
+    contexts evicts, a state is keyed again and one freed and replaced, short
+    records follow long ones and seals follow rejected opens; calls with more
+    AD than the worker takes go to the launch path with the same result."""
+    out = _mode(["--sequence"], {})
+    assert _after(out, "sequence") == 200 and _after(out, "big_ad") == 4
+    assert min(_after(out, w) for w in ("evictions", "long_short", "reject_seal")) >= 1, out
+
+
+def test_worker_calls_from_four_threads(gpu):
+    """Four threads, each on its own states, 150 seal-then-open calls each
+    over both ChaChaPoly paths and AES-GCM, every record against the oracle
+    (tests/worker_mode_check.py --threads)."""
+    out = _mode(["--threads"], {})
+    assert _after(out, "calls") == 600 and _after(out, "mismatches") == 0
+    assert _after(out, "served") == 4 and _after(out, "resident") >= 1, out
 
 
 def _child(script, env_extra, timeout=110):

@@ -160,3 +160,149 @@ def test_oracle_round_trips_every_fixture(oracle, name):
         lst = {"solo": C.full("solo"), "seg2": C.full("seg", 2), "seg_ragged": C.full("seg_ragged")}[name]
         pairs, cipher = C.with_ad(lst), CHACHA
     _round_trip(oracle, cipher, pairs, len(pairs))
+
+
+# ------------------------------------------------ the resident worker's lists
+
+WMULTI_MARGINALS = {"chunk": 93, "pass": 48, "tail": 24}
+WTRANSPORT = {0: 24, 1: 17}  # host memory (12-byte chunks, head 3072), device memory (8, 2048)
+
+
+def _old_worker_records():
+    """the hand-written (len, ad_len) of the worker's older ChaChaPoly tests,
+    imported from where they are used"""
+    import edge_records as E
+    import test_gpu_worker as W
+    import worker_mode_check as M
+    old = set(W._cases())
+    old |= {(L, A) for L in M.MAIN_LENS for A in M.MAIN_ADS}
+    old |= {(L, A) for A in M.HEAD_EDGE_ADS for L in M.head_edge_lens(A)}
+    for name, (cipher, _seed, lens, ads) in E.RAGGED_SHAPES.items():
+        if name.startswith("worker") and cipher == E.CHACHA:
+            old |= set(zip(lens, ads))
+    return old
+
+
+def test_worker_fast_fits_restates_the_kernel():
+    """worker_fast_fits: at most 63 units and at most 256 Poly1305 blocks"""
+    assert C.worker_fast_fits(4032, 48) and not C.worker_fast_fits(4033, 0)
+    assert not C.worker_fast_fits(4032, 49) and C.worker_fast_fits(4016, 49)
+    assert C.worker_fast_fits(3824, 256) and not C.worker_fast_fits(3825, 256)
+    for L, a in ((0, 0), (4032, 0), (4032, 48), (3824, 256), (65519, 256)):
+        _a, _m, n = C._poly_blocks(L, a)
+        assert C.worker_fast_fits(L, a) == (L <= 4032 and n <= 256)
+    assert [C._pow2(n) for n in (1, 2, 3, 4, 5, 33, 64, 65, 256)] == [1, 2, 4, 4, 8, 64, 64, 128, 256]
+
+
+def test_wfast_universe_and_list():
+    items = [(L, a) for L in range(C.WFAST_MAX_LEN + 1) for a in C.WORKER_ADS if C.worker_fast_fits(L, a)]
+    uni = C.universe(lambda x: C.wfast(*x), items)
+    full = C.full("wfast")
+    assert len(uni) == len(full) == 312 and C.universe(lambda x: C.wfast(*x), full) == uni == C.cases("wfast")
+    assert max(L for L, _a in full) == 4032 and all(C.worker_fast_fits(*x) for x in full)
+    # every tree width, N = 64 (n = 33 .. 64: the level-32 shuffle is the last) by name
+    assert {c[0] for c in uni} == set(range(9))
+    assert any(C.wfast(*x)[0] == 6 for x in full)
+    # each width above 2 full, one block past the half, and between (N = 4: n = 3 or 4 only)
+    for lg in range(2, 9):
+        assert {c[1] for c in uni if c[0] == lg} == ({0, 1} if lg == 2 else {0, 1, 2})
+    assert {c[3] for c in uni} == {0, 1, 2, 3, 4} and {c[2] for c in uni} == {0, 1, 2}
+
+
+def test_wfast_border_keeps_both_sides_and_the_corner():
+    border = C.wfast_border()
+    assert len(border) == 19 and len(set(border)) == 19
+    for a in C.WORKER_ADS:
+        fit = [L for L, x in border if x == a and C.worker_fast_fits(L, a)]
+        over = [L for L, x in border if x == a and not C.worker_fast_fits(L, a)]
+        assert len(fit) == 1 and fit[0] + 1 in over
+        assert not C.worker_fast_fits(fit[0] + 1, a)
+    # where both limits meet: 63 units with n = 256 against n = 257 (G = 2, pad = 1)
+    assert (4032, 48) in border and C.worker_fast_fits(4032, 48) and C._poly_blocks(4032, 48)[2] == 256
+    assert (4032, 49) in border and not C.worker_fast_fits(4032, 49)
+    assert C.wmulti_geometry(4032, 49)[2:] == (257, 2, 129, 1)
+
+
+def test_wmulti_universe_and_list():
+    items = [(L, a) for L in range(C.MAX_LEN + 1) for a in C.WORKER_ADS if not C.worker_fast_fits(L, a)]
+    uni = set()
+    for x in items:
+        uni.update(C.wmulti(*x))
+    full = C.full("wmulti")
+    assert {k: sum(1 for m in uni if m[0] == k) for k in WMULTI_MARGINALS} == WMULTI_MARGINALS
+    assert len(uni) == 165 and C.cases("wmulti") == uni
+    assert len(full) == 160 and list(full) == sorted(full) and not any(C.worker_fast_fits(*x) for x in full)
+    assert 4.9e6 < sum(L for L, _a in full) < 5.1e6
+    # every Horner depth (12 .. 15: bit 2 set below the top bit of the r^G
+    # ladder) and every number of ChaCha passes (3: a pair alone, 4: the
+    # smallest pair and a single)
+    assert {m[1] for m in uni if m[0] == "chunk"} == set(range(1, 18))
+    assert {m[1] for m in uni if m[0] == "pass"} == set(range(1, 18))
+    assert {C.wmulti_geometry(*x)[3] for x in full} == set(range(1, 18))
+    assert {C.wmulti_geometry(*x)[1] for x in full} == set(range(1, 18))
+    # P = 1 has no one-block last pass (J = 0 fits), P = 17 only that (J = 1024)
+    assert {m[2] for m in uni if m[:2] == ("pass", 1)} == {1, 2}
+    assert {m[2] for m in uni if m[:2] == ("pass", 17)} == {0}
+    # the tampered bit's three places lie inside the record and its AD
+    for L, a in full:
+        for field, lo, hi in C.wmulti_flips(L, a):
+            assert 0 <= lo < hi <= {"ad": a, "ct": L, "tag": 16}[field], (L, a, field)
+        J, P, n, G, NL, pad = C.wmulti_geometry(L, a)
+        assert 1 <= G <= 17 and 1 <= P <= 17 and NL <= 256 and 0 <= pad < G and NL * G - pad == n
+
+
+@pytest.mark.parametrize("vram", [0, 1])
+def test_wtransport_universe_and_list(vram):
+    items = [(op, L, a) for L in range(8193) for a in (0, 17) for op in (0, 1)]
+    uni = C.universe(lambda x: C.wtransport(vram, *x), items)
+    full = C.full("wtransport", vram)
+    assert len(uni) == len(full) == WTRANSPORT[vram] and C.cases("wtransport", vram) == uni
+    chunk, head = C.WORKER_CHUNK[vram], C.WORKER_HEAD[vram]
+    assert (chunk, head) == ((8, 2048) if vram else (12, 3072)) and head == 256 * chunk
+    assert {c[1] for c in uni if c[0] < 0} == set(range(chunk)) and {c[1] for c in uni if c[0] >= 0} == {None}
+    assert {c[0] for c in uni} == {-1, 0, 1}
+    for k in (2, 4):  # the raw tail's pieces, the result's
+        assert {c[k:k + 2] for c in uni} == {(0, False), (1, False), (1, True), (2, False), (2, True)}
+    # closed: the longest record adds nothing
+    assert {C.wtransport(vram, op, C.MAX_LEN, a) for op in (0, 1) for a in (0, 17)} <= uni
+
+
+def test_the_workers_hand_written_lists_were_thin():
+    """What LENS x ADS (sampled), worker_mode_check.py's lengths and the
+    worker shapes of edge_records.py reach of the above."""
+    old = _old_worker_records()
+    fast = {x for x in old if C.worker_fast_fits(*x)}
+    multi = old - fast
+    reached = C.universe(lambda x: C.wfast(*x), fast)
+    assert sorted({1 << c[0] for c in reached}) == [1, 2, 4, 8, 16, 32, 128, 256]  # no N = 64
+    assert not any(33 <= C._poly_blocks(*x)[2] <= 64 for x in fast)
+    # 93 cases, 88 of them among the 312 (the others come with the old lists' 13 and 32 bytes of AD)
+    assert len(reached) == 93 and len(reached & C.cases("wfast")) == 88
+    m = set()
+    for x in multi:
+        m.update(C.wmulti(*x))
+    assert m <= C.cases("wmulti")
+    assert sorted({c[1] for c in m if c[0] == "chunk"}) == [1, 2, 3, 5, 10, 16, 17]
+    assert sorted({c[1] for c in m if c[0] == "pass"}) == [1, 2, 5, 10, 17]
+    assert {k: sum(1 for c in m if c[0] == k) for k in WMULTI_MARGINALS} == {"chunk": 13, "pass": 8, "tail": 13}
+    # the border: 4032 bytes was never run with 48 or 49 bytes of AD
+    assert not {(4032, 48), (4032, 49), (4016, 49), (4017, 49)} & old
+    # the transport: the head edges were there; not every residue of the last
+    # chunk, nor a short last piece in both of a two-round record's loops
+    for vram, reached, missing in ((0, 20, {2, 6, 10}), (1, 12, {2, 3, 5, 6})):
+        gap = C.cases("wtransport", vram) - {C.wtransport(vram, op, L, a) for (L, a) in old for op in (0, 1)}
+        assert len(C.cases("wtransport", vram)) - len(gap) == reached
+        assert {c[1] for c in gap if c[0] < 0} == missing
+        assert {c for c in gap if c[0] >= 0} == {(1, None, 1, True, 2, True)}
+
+
+@pytest.mark.parametrize("name", ["wfast", "wmulti", "wtransport0", "wtransport1"])
+def test_oracle_round_trips_every_worker_fixture(oracle, name):
+    """as test_oracle_round_trips_every_fixture, for the worker's records"""
+    if name == "wfast":
+        pairs = list(C.full("wfast")) + C.wfast_border()
+    elif name == "wmulti":
+        pairs = list(C.full("wmulti"))
+    else:
+        pairs = sorted({x[1:] for x in C.full("wtransport", int(name[-1]))})
+    _round_trip(oracle, CHACHA, pairs, len(pairs))

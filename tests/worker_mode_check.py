@@ -3,7 +3,8 @@ pytest): single-record seal/open through the resident worker, checked
 against the oracle, under whatever NOISE_AEAD_WORKER_VRAM the parent set.
 The worker picks its request placement once per process, hence the child.
 Prints "placement N" (noise_aead_debug_worker_placement) and exits non-zero
-on the first mismatch."""
+on the first mismatch.  The other modes (--classes, --sequence, --threads,
+--head-edges, ...) say what they run in their functions' docstrings."""
 import os
 import random
 import sys
@@ -14,6 +15,18 @@ for p in (ROOT, os.path.join(ROOT, "oracle"), os.path.join(ROOT, "noise-c_amd"))
 
 import noise_aead as aead  # noqa: E402
 import oracle as O  # noqa: E402
+
+# the hand-written lists of the placement test and of --head-edges
+# (tests/test_length_classes_host.py counts what they reach)
+MAIN_LENS = (0, 1, 17, 1024, 1400, 2100, 3100, 4033, 8000, 16384)
+MAIN_ADS = (0, 32)
+HEAD_EDGE_ADS = (0, 17)
+
+
+def head_edge_lens(A):
+    ad_pad = (A + 15) & ~15
+    return sorted({head + d - 32 - ad_pad - tag
+                   for head in (2048, 3072) for tag in (0, 16) for d in (-1, 0, 1, 15, 16, 17)})
 
 
 def main():
@@ -28,10 +41,10 @@ def main():
         _, rx = aead.CipherState.new_by_id(cipher)
         assert tx.init_key(key) == 0 and rx.init_key(key) == 0
         n = 0
-        for L in (0, 1, 17, 1024, 1400, 2100, 3100, 4033, 8000, 16384):
+        for L in MAIN_LENS:
             if cipher == 0x4302 and L > 4096:
                 continue
-            for A in (0, 32):
+            for A in MAIN_ADS:
                 pt = bytes(rnd.randrange(256) for _ in range(L))
                 ad = bytes(rnd.randrange(256) for _ in range(A))
                 ct = tx.seal(pt, ad)
@@ -260,10 +273,8 @@ def head_edges():
         _, rx = aead.CipherState.new_by_id(cipher)
         assert tx.init_key(key) == 0 and rx.init_key(key) == 0
         n = 0
-        for A in (0, 17):
-            ad_pad = (A + 15) & ~15
-            lens = sorted({head + d - 32 - ad_pad - tag
-                           for head in (2048, 3072) for tag in (0, 16) for d in (-1, 0, 1, 15, 16, 17)})
+        for A in HEAD_EDGE_ADS:
+            lens = head_edge_lens(A)
             assert len(lens) == 18 and max(lens) + 16 <= 3100
             ad = bytes(rnd.randrange(256) for _ in range(A))
             for L in lens:
@@ -291,7 +302,265 @@ def head_edges():
     return 0
 
 
+CHACHA, AES = 0x4301, 0x4302
+NONCE0 = (1 << 32) - 3  # both nonce words live: the counter crosses 2^32 inside every run
+
+
+def _oracle():
+    if not os.path.exists(O.ORACLE_SO):
+        O.build(ref=False)
+    return O.Oracle()
+
+
+def _flip(rnd, ct, ad, where):
+    """(ct, ad) with one random bit flipped in bytes [lo, hi) of `where` =
+    (field, lo, hi), field "ct", "tag" or "ad"; an empty range falls to the
+    tag."""
+    field, lo, hi = where
+    if hi <= lo:
+        field, lo, hi = "tag", 0, 16
+    ct, ad = bytearray(ct), bytearray(ad)
+    pos, bit = rnd.randrange(lo, hi), 1 << rnd.randrange(8)
+    if field == "ad":
+        ad[pos] ^= bit
+    else:
+        ct[pos + (len(ct) - 16 if field == "tag" else 0)] ^= bit
+    return bytes(ct), bytes(ad)
+
+
+class _Pair:
+    """a sealing and an opening state under one key, nonces from NONCE0"""
+
+    def __init__(self, cipher, key):
+        self.cipher, self.key, self.n = cipher, key, NONCE0
+        _, self.tx = aead.CipherState.new_by_id(cipher)
+        _, self.rx = aead.CipherState.new_by_id(cipher)
+        for st in (self.tx, self.rx):
+            assert st.init_key(key) == 0 and st.set_nonce(NONCE0) == 0
+
+    def record(self, orc, rnd, seed, L, A, where):
+        """Seal against the oracle, a tampered open rejected with buffer and
+        nonce as given, open back: None, or what went wrong."""
+        pt, ad = orc.fill(seed, L), orc.fill(seed ^ 0xAD, A)
+        ct = self.tx.seal(pt, ad)
+        if ct != orc.encrypt(self.cipher, self.key, self.n, pt, ad):
+            return "seal mismatch"
+        bad, bad_ad = _flip(rnd, ct, ad, where)
+        rc, back = self.rx.open(bad, bad_ad)
+        if rc != aead.ERROR_MAC_FAILURE or back != bad or self.rx.nonce != self.n:
+            return "tamper in %s not rejected" % (where,)
+        rc, back = self.rx.open(ct, ad)
+        if rc != 0 or back != pt:
+            return "open mismatch"
+        self.n += 1
+        if self.tx.nonce != self.n or self.rx.nonce != self.n:
+            return "nonce"
+        return None
+
+    def free(self):
+        self.tx.free()
+        self.rx.free()
+
+
+def classes(which):
+    """--classes chacha | aes: every record length tests/length_classes.py
+    derives for the resident worker, under the placement
+    (NOISE_AEAD_WORKER_VRAM) and GHASH (NOISE_AEAD_CT_GHASH) the parent set.
+    chacha: full("wfast"), wfast_border(), full("wmulti") and
+    full("wtransport", placement in use); the tampered bit of case i lands in
+    the ciphertext, the tag or the AD (i % 3), for the multi-path records in
+    chunk 0, the last chunk or a block of the last ChaCha pass
+    (wmulti_flips).  aes: full("gcm_wide", ct), lengths over 4096 included
+    (gcm_wide_record in place in LDS).  Stops at the first mismatch, naming
+    cipher, len, ad_len and the case.  Prints "classes N" and "placement P"."""
+    import length_classes as LC
+    orc = _oracle()
+    lib = aead.lib()
+    ct_ghash = os.environ.get("NOISE_AEAD_CT_GHASH", "0") == "1"
+    rnd = random.Random(0xC1A55 + ct_ghash)
+    cipher = CHACHA if which == "chacha" else AES
+    pair = _Pair(cipher, orc.fill(0x1234 + cipher, 32))
+    pair.tx.seal(b"")  # the first call sets the worker up: the placement is known
+    pair.rx.set_nonce(NONCE0 + 1)
+    pair.n += 1
+    placement = lib.noise_aead_debug_worker_placement()
+    vram = 1 if placement == 2 else 0
+    simple = lambda i, L, A: (("ct", 0, L), ("tag", 0, 16), ("ad", 0, A))[i % 3]
+    if which == "chacha":
+        lists = [("wfast", LC.full("wfast"), lambda x: LC.wfast(*x), simple),
+                 ("border", LC.wfast_border(), lambda x: (LC.worker_fast_fits(*x),), simple),
+                 ("wmulti", LC.full("wmulti"), lambda x: LC.wmulti(*x), lambda i, L, A: LC.wmulti_flips(L, A)[i % 3]),
+                 ("wtransport", sorted({x[1:] for x in LC.full("wtransport", vram)}),
+                  lambda x: (LC.wtransport(vram, 0, *x), LC.wtransport(vram, 1, *x)), simple)]
+    else:
+        lists = [("gcm_wide", LC.full("gcm_wide", 0, ct_ghash), lambda x: LC.gcm_wide(x[0], x[1], ct_ghash), simple)]
+    done = 0
+    for name, items, case, where in lists:
+        for i, (L, A) in enumerate(items):
+            err = pair.record(orc, rnd, (done << 8) ^ cipher, L, A, where(i, L, A))
+            if err:
+                print(err, hex(cipher), "list", name, "len", L, "ad_len", A, "case", case((L, A)))
+                return 1
+            done += 1
+    pair.free()
+    print("classes", done)
+    print("placement", placement)
+    return 0
+
+
+SEQ_LENS = (0, 16, 100, 1400, 3100, 4033, 20000)  # head only, head + tail, fast / multi
+SEQ_ADS = (0, 17)
+
+
+def sequence():
+    """--sequence: one thread, so one slot, serving three AES-GCM and two
+    ChaChaPoly states in a fixed pseudo-random order, every result against
+    the oracle: a seal, an open of the oracle's record, or a tampered open
+    (rejected, buffer and nonce as given).  The third AES-GCM state evicts
+    the least recently used of the two contexts cached in LDS, long records
+    are followed by short ones, rejected opens by seals (each counted, none
+    may be 0).  Midway one AES-GCM state is keyed again (same state and
+    context address, next generation) and one is freed and a new one made
+    (ctx_take may hand it the freed address).  Last, per cipher, one call
+    with 257 and one with 1000 bytes of AD (over WORKER_MAX_AD): the launch
+    path serves them with the same nonce and result, and no worker kernel is
+    launched for them.  Prints "sequence N evictions E long_short S
+    reject_seal R big_ad B"."""
+    orc = _oracle()
+    lib = aead.lib()
+    lib.noise_aead_debug_worker_launches.restype = int
+    rnd = random.Random(0x5E9)
+    states = {}
+
+    def make(name, cipher, salt):
+        key = orc.fill(salt, 32)
+        _, st = aead.CipherState.new_by_id(cipher)
+        assert st.init_key(key) == 0 and st.set_nonce(NONCE0) == 0
+        states[name] = [cipher, key, st]
+
+    for k, name in enumerate(("A0", "A1", "A2", "C0", "C1")):
+        make(name, AES if name[0] == "A" else CHACHA, 100 + k)
+
+    def call(name, kind, L, A, seed):
+        cipher, key, st = states[name]
+        n = st.nonce
+        pt, ad = orc.fill(seed, L), orc.fill(seed ^ 0xAD, A)
+        exp = orc.encrypt(cipher, key, n, pt, ad)
+        if kind == "seal":
+            ok = st.seal(pt, ad) == exp and st.nonce == n + 1
+        elif kind == "open":
+            rc, back = st.open(exp, ad)
+            ok = rc == 0 and back == pt and st.nonce == n + 1
+        else:
+            bad, bad_ad = _flip(rnd, exp, ad, (("ct", 0, L), ("tag", 0, 16), ("ad", 0, A))[seed % 3])
+            rc, back = st.open(bad, bad_ad)
+            ok = rc == aead.ERROR_MAC_FAILURE and back == bad and st.nonce == n
+        if not ok:
+            print(kind, "mismatch", hex(cipher), "state", name, "len", L, "ad_len", A, "call", seed)
+        return ok
+
+    evictions = long_short = reject_seal = 0
+    lru, prev = [], None  # the two AES-GCM states used last; the call before
+    for i in range(200):
+        if i == 100:
+            # A0 keyed again in place, A1 freed and made anew: both under new keys
+            key = orc.fill(777, 32)
+            assert states["A0"][2].init_key(key) == 0 and states["A0"][2].set_nonce(NONCE0) == 0
+            states["A0"][1] = key
+            states["A1"][2].free()
+            make("A1", AES, 778)
+        name = rnd.choice(sorted(states))
+        kind = rnd.choice(("seal", "seal", "open", "tamper"))
+        L, A = rnd.choice(SEQ_LENS), rnd.choice(SEQ_ADS)
+        if not call(name, kind, L, A, i):
+            return 1
+        if name[0] == "A":
+            evictions += len(lru) == 2 and name not in lru
+            lru = ([x for x in lru if x != name] + [name])[-2:]
+        if prev:
+            long_short += prev[1] >= 4033 and L <= 100
+            reject_seal += prev[0] == "tamper" and kind == "seal"
+        prev = (kind, L)
+    big_ad = 0
+    for name in ("C0", "A2"):
+        for kind, A in (("seal", 257), ("open", 1000)):
+            before = lib.noise_aead_debug_worker_launches()
+            if not call(name, kind, 1400, A, 1000 + A):
+                return 1
+            if lib.noise_aead_debug_worker_launches() != before:
+                print("a worker kernel was launched for ad_len", A)
+                return 1
+            big_ad += 1
+    for _cipher, _key, st in states.values():
+        st.free()
+    print("sequence", 200, "evictions", evictions, "long_short", long_short, "reject_seal", reject_seal,
+          "big_ad", big_ad)
+    return 0 if evictions and long_short and reject_seal else 1
+
+
+THREAD_LENS = (0, 100, 1400, 4032, 4033, 9000)  # both ChaChaPoly paths, head only and head + tail
+
+
+def threads():
+    """--threads: four threads at once (ctypes releases the GIL), each with a
+    ChaChaPoly and an AES-GCM pair of states of its own, 150 seal-then-open
+    calls each over THREAD_LENS and both ciphers, compared with what the
+    oracle gave before the loops started.  Prints "mismatches M" (0),
+    "served S" (threads whose last call a worker served) and "resident R"
+    (request slots of the resident groups)."""
+    import threading
+    orc = _oracle()
+    lib = aead.lib()
+    lib.noise_aead_debug_workers_resident.restype = int
+    T, CALLS = 4, 150
+    plans = []
+    for t in range(T):
+        pairs = {c: _Pair(c, orc.fill(31 * t + c, 32)) for c in (CHACHA, AES)}
+        plan, n = [], {CHACHA: NONCE0, AES: NONCE0}
+        for i in range(CALLS):
+            c = (CHACHA, AES)[(i + t) % 2]
+            L, A = THREAD_LENS[(i // 2 + t) % len(THREAD_LENS)], (0, 17)[(i // 12) % 2]
+            pt, ad = orc.fill((t << 16) | i, L), orc.fill((t << 16) | i | 0x8000, A)
+            plan.append((c, pt, ad, orc.encrypt(c, pairs[c].key, n[c], pt, ad)))
+            n[c] += 1
+        plans.append((pairs, plan))
+    bad = [[] for _ in range(T)]
+    served = [0] * T
+    go = threading.Barrier(T)
+
+    def run(t):
+        pairs, plan = plans[t]
+        go.wait()
+        for i, (c, pt, ad, exp) in enumerate(plan):
+            ct = pairs[c].tx.seal(pt, ad)
+            rc, back = pairs[c].rx.open(ct, ad)
+            if ct != exp or rc != 0 or back != pt:
+                bad[t].append((hex(c), i, len(pt), len(ad)))
+        served[t] = 1 if lib.noise_aead_debug_worker_placement() else 0
+
+    ths = [threading.Thread(target=run, args=(t,)) for t in range(T)]
+    for th in ths:
+        th.start()
+    for th in ths:
+        th.join()
+    resident = lib.noise_aead_debug_workers_resident()
+    for pairs, _plan in plans:
+        for pr in pairs.values():
+            pr.free()
+    wrong = [x for b in bad for x in b]
+    if wrong:
+        print("first mismatches (cipher, call, len, ad_len)", wrong[:5])
+    print("calls", T * CALLS, "mismatches", len(wrong), "served", sum(served), "resident", resident)
+    return 0 if not wrong and sum(served) == T else 1
+
+
 if __name__ == "__main__":
+    if "--classes" in sys.argv:
+        sys.exit(classes(sys.argv[sys.argv.index("--classes") + 1]))
+    if "--sequence" in sys.argv:
+        sys.exit(sequence())
+    if "--threads" in sys.argv:
+        sys.exit(threads())
     if "--head-edges" in sys.argv:
         sys.exit(head_edges())
     if "--group-idle" in sys.argv:
