@@ -75,6 +75,18 @@ typedef struct {
 #define NOISE_ERROR_INVALID_STATE NOISE_ID('E', 12)
 #define NOISE_ERROR_INVALID_NONCE NOISE_ID('E', 13)
 #define NOISE_MAX_PAYLOAD_LEN 65535
+#define NOISE_ROLE_INITIATOR NOISE_ID('R', 1) /* constants.h:111-112 */
+#define NOISE_ROLE_RESPONDER NOISE_ID('R', 2)
+#define NOISE_ACTION_NONE 0 /* constants.h:115-120 */
+#define NOISE_ACTION_WRITE_MESSAGE NOISE_ID('A', 1)
+#define NOISE_ACTION_READ_MESSAGE NOISE_ID('A', 2)
+#define NOISE_ACTION_FAILED NOISE_ID('A', 3)
+#define NOISE_ACTION_SPLIT NOISE_ID('A', 4)
+#define NOISE_ACTION_COMPLETE NOISE_ID('A', 5)
+#define NOISE_ERROR_REMOTE_KEY_REQUIRED NOISE_ID('E', 7) /* constants.h:138-140, 146 */
+#define NOISE_ERROR_LOCAL_KEY_REQUIRED NOISE_ID('E', 8)
+#define NOISE_ERROR_PSK_REQUIRED NOISE_ID('E', 9)
+#define NOISE_ERROR_INVALID_PUBLIC_KEY NOISE_ID('E', 15)
 #endif
 
 /* ------------------------------------------------ 1. CipherState API
@@ -472,6 +484,120 @@ int noise_aead_dev_dh_calculate(int dh_id, const uint8_t *d_priv, uint64_t priv_
                                 uint8_t *d_shared, void *stream);
 int noise_aead_dev_dh_public(int dh_id, const uint8_t *d_priv, uint64_t priv_stride, uint32_t n,
                              uint8_t *d_pub_out, void *stream);
+
+/* ------------------------------------------------ 8. batched handshakes
+ *
+ * n Noise handshakes of one protocol and one role, run message by message
+ * without a host round trip: what noise_handshakestate_start / _write_message
+ * / _read_message / _split (src/protocol/handshakestate.c:800-885, 1151-1340,
+ * 1419-1600; symmetricstate.c:97-108, 514-573) do for one session, done for
+ * session i of the batch alone.  An opaque host object owns the device state
+ * (ck, h, k, key contexts, descriptors, a DH arena, statuses, local public
+ * keys, remote e and s: all allocated by _new; a message call allocates
+ * nothing).  Every data pointer is a device pointer; every call is
+ * asynchronous on `stream`, and none synchronises or copies to the host.  The
+ * calls of one object must be issued in stream order (one stream, or streams
+ * the caller orders).
+ *
+ * In scope: the patterns N K X NN NK NX XN XK XX KN KK KX IN IK IX over
+ * Curve25519, ChaChaPoly or AESGCM, the four hashes, the prefixes "Noise" and
+ * "NoisePSK" (the reference's old-style PSK: after the prologue ck, temp =
+ * HKDF(ck, psk) and MixHash(temp), handshakestate.c:833-842; every `e` token
+ * also MixKey(e.public), :1214-1217, :1477-1481).  A name that parses but
+ * needs Curve448, NewHope, a hybrid ("hfs") pattern or XXfallback gives
+ * NOISE_ERROR_NOT_APPLICABLE; anything else that is not a protocol name gives
+ * NOISE_ERROR_UNKNOWN_NAME.
+ *
+ * Strides: session i's value is at pointer + i * stride.  A stride of 0 is one
+ * value for all sessions (a server's static key, a shared prologue, one
+ * payload for all); any other key stride must be at least 32, any other
+ * prologue, payload or message stride at least the length; an output stride
+ * must be at least the bytes written (never 0).  Nothing needs alignment.
+ * Payload and message lengths are uniform over the batch.
+ *
+ * _new consumes the prologue, the PSK and the remote static public keys; the
+ * private keys (d_local_static_priv, d_local_ephemeral_priv) are read by
+ * later calls and must stay valid and unchanged until the split.  The
+ * ephemeral private keys are the caller's entropy, fresh per session, as the
+ * reseed of noise_aead_dev_pad is.  Start-up is the reference's: h = the name
+ * zero-padded to the hash length, or HASH(name) when longer; ck = h; then
+ * MixHash(prologue) (the empty one too, :826-829), the PSK step, and MixHash
+ * of the initiator's pre-message static key, then of the responder's
+ * (:844-877).
+ *
+ * Messages: _get_action says which call is next (an initiator starts with
+ * NOISE_ACTION_WRITE_MESSAGE, a responder with _READ_MESSAGE; after the last
+ * message — for a one-way pattern its only one — NOISE_ACTION_SPLIT, after
+ * the split _COMPLETE).  _overhead is what the next message adds to its
+ * payload: 32 per `e`, 32 per `s` plus 16 once a key is set (:1487-1488), 16
+ * for the payload once a key is set.  write_message builds
+ * d_msg + i * msg_stride from d_payload + i * payload_stride (payload_len
+ * bytes; d_payload may be NULL when 0) and writes payload_len + overhead
+ * bytes; read_message takes msg_len bytes and writes msg_len - overhead
+ * payload bytes to d_payload + i * payload_stride.  Before the first MixKey
+ * encrypt_and_hash / decrypt_and_hash pass the bytes through and MixHash them;
+ * the nonce restarts at 0 on every MixKey and counts one per AEAD.
+ * _split writes k1[i], k2[i] = HKDF(ck_i, "") truncated to 32 bytes, packed 32
+ * bytes apart in the order of noise_aead_dev_split (the initiator sends under
+ * k1), ready for noise_aead_dev_prepare, and h_i (hash-length bytes apart) to
+ * d_handshake_hash when it is not NULL.
+ *
+ * Checked on the host before any launch, in this order:
+ *   - the wrong call for _get_action: NOISE_ERROR_INVALID_STATE;
+ *   - _new without a key the pattern needs of this role:
+ *     NOISE_ERROR_LOCAL_KEY_REQUIRED (static or ephemeral private key),
+ *     NOISE_ERROR_REMOTE_KEY_REQUIRED, NOISE_ERROR_PSK_REQUIRED (d_psk is
+ *     required with NoisePSK and ignored otherwise);
+ *   - a message over 65535 bytes, or msg_len below the overhead:
+ *     NOISE_ERROR_INVALID_LENGTH;
+ *   - a NULL pointer, a stride in 1..31 (keys) or below the length, an output
+ *     stride that is too short, or an output span
+ *     [out, out + (n - 1) * stride + bytes) that meets the input span of the
+ *     same call (split: two outputs that meet): NOISE_ERROR_INVALID_PARAM.
+ * n == 0 gives a valid object whose calls check the state and the lengths,
+ * launch nothing and advance the action.
+ *
+ * Per-session failures stay on the device: status[i] is 0 (ok), 1 (a tag
+ * failed: NOISE_ERROR_MAC_FAILURE) or 3 (the received ephemeral was all-zero:
+ * NOISE_ERROR_INVALID_PUBLIC_KEY, :1464-1470); 2 stays reserved as in the
+ * ragged calls.  The first failure is sticky.  A failed session writes only
+ * inside its own slots and its later output bytes are unspecified; its opens
+ * never write unauthenticated plaintext (the verify-first order) and nothing
+ * more is sealed, opened or passed through for it; the split writes zeros for
+ * its two keys.  Every other session is unaffected, byte for byte, and the
+ * host action advances for the batch regardless.
+ *
+ * _free scrubs every device array the object owns before freeing it (it
+ * waits for the device to do so), at any point of the handshake.  _status is
+ * the n status bytes, _remote_static the n x 32 remote static public keys
+ * (given to _new or received in an `s` token); both are device pointers owned
+ * by the object. */
+typedef struct NoiseAeadDevHandshake NoiseAeadDevHandshake;
+typedef struct NoiseAeadHandshakeConfig {
+    const char *protocol_name;   /* "Noise_XX_25519_ChaChaPoly_BLAKE2s", "NoisePSK_IK_25519_AESGCM_SHA512", ... */
+    int role;                    /* NOISE_ROLE_INITIATOR / NOISE_ROLE_RESPONDER */
+    uint32_t n;
+    const uint8_t *d_prologue;  uint64_t prologue_stride; uint32_t prologue_len;
+    const uint8_t *d_psk;       uint64_t psk_stride;       /* 32 bytes each */
+    const uint8_t *d_local_static_priv;    uint64_t local_static_stride;
+    const uint8_t *d_local_ephemeral_priv; uint64_t local_ephemeral_stride;
+    const uint8_t *d_remote_static_pub;    uint64_t remote_static_stride;
+} NoiseAeadHandshakeConfig;
+
+int noise_aead_dev_handshake_new(NoiseAeadDevHandshake **hs, const NoiseAeadHandshakeConfig *cfg, void *stream);
+int noise_aead_dev_handshake_free(NoiseAeadDevHandshake *hs);
+int noise_aead_dev_handshake_get_action(const NoiseAeadDevHandshake *hs);
+size_t noise_aead_dev_handshake_overhead(const NoiseAeadDevHandshake *hs);
+int noise_aead_dev_handshake_write_message(NoiseAeadDevHandshake *hs, const uint8_t *d_payload,
+                                           uint64_t payload_stride, uint32_t payload_len, uint8_t *d_msg,
+                                           uint64_t msg_stride, void *stream);
+int noise_aead_dev_handshake_read_message(NoiseAeadDevHandshake *hs, const uint8_t *d_msg, uint64_t msg_stride,
+                                          uint32_t msg_len, uint8_t *d_payload, uint64_t payload_stride,
+                                          void *stream);
+int noise_aead_dev_handshake_split(NoiseAeadDevHandshake *hs, uint8_t *d_k1, uint8_t *d_k2,
+                                   uint8_t *d_handshake_hash, void *stream);
+const uint8_t *noise_aead_dev_handshake_status(const NoiseAeadDevHandshake *hs);
+const uint8_t *noise_aead_dev_handshake_remote_static(const NoiseAeadDevHandshake *hs);
 
 /* ------------------------------------------------ error reports
  * include/noise/protocol/errors.h; src/protocol/errors.c:92-127. */

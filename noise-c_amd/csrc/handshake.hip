@@ -1,0 +1,558 @@
+/*
+ * handshake.hip — batched Noise handshakes on the device:
+ * noise_aead_dev_handshake_* (include/noise_aead_hip.h section 8).
+ *
+ * The host object walks the steps handshake_plan.h makes of a message and
+ * issues, per step, launches over all n sessions; nothing comes back to the
+ * host, so the action, the nonce and "is a key set" — which are the same for
+ * every session of a batch — live on the host and everything per session
+ * (ck, h, k, statuses, public keys) lives on the device.
+ *
+ * The kernels here run one lane per session in 64-lane workgroups over the
+ * Hasher of hasher.h:
+ *   hs_init       h = the protocol name padded or hashed, ck = h
+ *                 (symmetricstate.c:97-108);
+ *   hs_mix_hash   h = HASH(h || bytes) over strided bytes, with an optional
+ *                 copy of the bytes (the pass-through of an unkeyed
+ *                 encrypt/decrypt_and_hash, an `e` into or out of a message),
+ *                 and, after an open, the sticky status merge: a session
+ *                 whose tag failed keeps its h and takes status 1;
+ *   hs_mix_key    ck, k = HKDF(ck, ikm) in place, zeroing the shared secret
+ *                 it consumed (noise_clean(shared), handshakestate.c:1136);
+ *                 for the PSK start-up step ck, temp = HKDF(ck, psk) and
+ *                 MixHash(temp) (:833-842);
+ *   hs_null_check the all-zero received ephemeral (:1464-1470) -> status 3;
+ *   hs_build_recs the NoiseAeadRecord array of one AEAD step from (stride,
+ *                 length, nonce, i * ctx_bytes, i * hash_len); a failed
+ *                 session gets a length the ragged kernels refuse, so nothing
+ *                 more is sealed or opened for it;
+ *   hs_split      k1, k2 = HKDF(ck, ""), zeros for a failed session, and h.
+ * DH tokens are the ladder launches of noise_aead_dev_dh_calculate into an
+ * arena the object owns; the AEAD steps are noise_aead_dev_seal_ragged /
+ * _open_ragged (verify-first) under AD = h; AES-GCM key contexts are prepared
+ * again only when k changed since the last prepare (ChaChaPoly's context is
+ * the key itself).
+ */
+#include "launch.h"
+
+#include "handshake_plan.h"
+#include "hasher.h"
+
+#include <new>
+
+using namespace na;
+
+namespace {
+
+constexpr uint32_t HS_BLOCK = 64;
+constexpr uint32_t HS_REFUSED_LEN = MAX_RECORD_LEN + 1; /* aead_kernels.h reject_len */
+constexpr uint8_t HS_STATUS_MAC = 1, HS_STATUS_NULL_KEY = 3;
+constexpr size_t HS_NAME_MAX = 64; /* the longest name in scope has 36 characters */
+
+NA_DEV void hs_load_h(uint8_t *dst, const uint8_t *h, uint32_t hl)
+{
+    for (uint32_t j = 0; j < hl; ++j) dst[j] = h[j];
+}
+
+/* noise_hashstate_hkdf (hashstate.c:476-516) of one lane, both outputs whole */
+NA_DEV void hs_hkdf(int hid, uint32_t hl, const uint8_t *key, const uint8_t *data, uint32_t data_len, uint8_t *o1,
+                    uint8_t *o2)
+{
+    uint8_t tk[64];
+    const uint8_t one = 0x01, two = 0x02;
+    kdf_hmac(hid, key, hl, data, data_len, nullptr, 0, tk);
+    kdf_hmac(hid, tk, hl, &one, 1, nullptr, 0, o1);
+    kdf_hmac(hid, tk, hl, o1, hl, &two, 1, o2);
+    for (int j = 0; j < 64; ++j) tk[j] = 0;
+}
+
+struct InitArgs {
+    int hash_id;
+    uint32_t hl, n, name_len;
+    uint8_t *h, *ck;
+    uint8_t name[HS_NAME_MAX];
+};
+
+__global__ __launch_bounds__(HS_BLOCK) void hs_init(InitArgs a)
+{
+    const uint32_t i = blockIdx.x * HS_BLOCK + threadIdx.x;
+    if (i >= a.n) return;
+    uint8_t h[64];
+    if (a.name_len <= a.hl) {
+        for (uint32_t j = 0; j < a.hl; ++j) h[j] = j < a.name_len ? a.name[j] : 0;
+    } else {
+        Hasher H;
+        H.init(a.hash_id);
+        H.update(a.name, a.name_len);
+        H.final(h);
+    }
+    for (uint32_t j = 0; j < a.hl; ++j) a.h[(size_t)i * a.hl + j] = a.ck[(size_t)i * a.hl + j] = h[j];
+}
+
+struct MixHashStrided {
+    int hash_id;
+    uint32_t hl, n, len;
+    uint8_t *h;
+    const uint8_t *src;   /* session i hashes src + i * src_stride, len bytes */
+    uint64_t src_stride;
+    uint8_t *dst;         /* not NULL: the bytes are also copied to dst + i * dst_stride */
+    uint64_t dst_stride;
+    uint8_t *status;      /* the sticky statuses: a failed session does nothing */
+    const uint8_t *step;  /* not NULL: the statuses of the open just done */
+};
+
+__global__ __launch_bounds__(HS_BLOCK) void hs_mix_hash(MixHashStrided a)
+{
+    const uint32_t i = blockIdx.x * HS_BLOCK + threadIdx.x;
+    if (i >= a.n) return;
+    if (a.status[i]) return;
+    if (a.step && a.step[i]) { /* the reference leaves h as it was (symmetricstate.c:436-443) */
+        a.status[i] = HS_STATUS_MAC;
+        return;
+    }
+    const uint8_t *src = a.src + (uint64_t)i * a.src_stride;
+    if (a.dst) {
+        uint8_t *dst = a.dst + (uint64_t)i * a.dst_stride;
+        for (uint32_t j = 0; j < a.len; ++j) dst[j] = src[j];
+    }
+    uint8_t h[64];
+    hs_load_h(h, a.h + (size_t)i * a.hl, a.hl);
+    Hasher H;
+    H.init(a.hash_id);
+    H.update(h, a.hl);
+    H.update(src, a.len);
+    H.final(h);
+    for (uint32_t j = 0; j < a.hl; ++j) a.h[(size_t)i * a.hl + j] = h[j];
+}
+
+struct MixKeyArgs {
+    int hash_id;
+    uint32_t hl, n;
+    uint8_t *ck, *k;
+    uint8_t *h;           /* psk: MixHash(temp) instead of k = temp */
+    uint8_t *ikm;         /* 32 bytes at ikm + i * ikm_stride */
+    uint64_t ikm_stride;
+    uint32_t zero_ikm, psk;
+};
+
+__global__ __launch_bounds__(HS_BLOCK) void hs_mix_key(MixKeyArgs a)
+{
+    const uint32_t i = blockIdx.x * HS_BLOCK + threadIdx.x;
+    if (i >= a.n) return;
+    uint8_t *ikm_p = a.ikm + (uint64_t)i * a.ikm_stride;
+    uint8_t ck[64], ikm[32], o1[64], o2[64];
+    hs_load_h(ck, a.ck + (size_t)i * a.hl, a.hl);
+    for (int j = 0; j < 32; ++j) ikm[j] = ikm_p[j];
+    hs_hkdf(a.hash_id, a.hl, ck, ikm, 32, o1, o2);
+    for (uint32_t j = 0; j < a.hl; ++j) a.ck[(size_t)i * a.hl + j] = o1[j];
+    if (a.psk) {
+        uint8_t h[64];
+        hs_load_h(h, a.h + (size_t)i * a.hl, a.hl);
+        Hasher H;
+        H.init(a.hash_id);
+        H.update(h, a.hl);
+        H.update(o2, a.hl);
+        H.final(h);
+        for (uint32_t j = 0; j < a.hl; ++j) a.h[(size_t)i * a.hl + j] = h[j];
+    } else {
+        for (int j = 0; j < 32; ++j) a.k[(size_t)i * 32 + j] = o2[j];
+    }
+    if (a.zero_ikm)
+        for (int j = 0; j < 32; ++j) ikm_p[j] = 0;
+    for (int j = 0; j < 64; ++j) ck[j] = o1[j] = o2[j] = 0;
+    for (int j = 0; j < 32; ++j) ikm[j] = 0;
+}
+
+__global__ __launch_bounds__(HS_BLOCK) void hs_null_check(const uint8_t *re, uint8_t *status, uint32_t n)
+{
+    const uint32_t i = blockIdx.x * HS_BLOCK + threadIdx.x;
+    if (i >= n || status[i]) return;
+    uint8_t acc = 0;
+    for (int j = 0; j < 32; ++j) acc |= re[(size_t)i * 32 + j];
+    if (!acc) status[i] = HS_STATUS_NULL_KEY;
+}
+
+__global__ __launch_bounds__(HS_BLOCK) void hs_copy32(const uint8_t *src, uint64_t src_stride, uint8_t *dst, uint32_t n)
+{
+    const uint32_t i = blockIdx.x * HS_BLOCK + threadIdx.x;
+    if (i >= n) return;
+    for (int j = 0; j < 32; ++j) dst[(size_t)i * 32 + j] = src[(uint64_t)i * src_stride + j];
+}
+
+struct BuildRecs {
+    RecDesc *recs;
+    const uint8_t *status;
+    uint64_t in_stride, out_stride, nonce, ctx_bytes;
+    uint32_t len, hl, n;
+};
+
+__global__ __launch_bounds__(HS_BLOCK) void hs_build_recs(BuildRecs a)
+{
+    const uint32_t i = blockIdx.x * HS_BLOCK + threadIdx.x;
+    if (i >= a.n) return;
+    RecDesc d;
+    d.in_off = (uint64_t)i * a.in_stride;
+    d.out_off = (uint64_t)i * a.out_stride;
+    d.nonce = a.nonce;
+    d.ctx_off = (uint64_t)i * a.ctx_bytes;
+    d.ad_off = (uint64_t)i * a.hl;
+    d.len = a.status[i] ? HS_REFUSED_LEN : a.len;
+    d.ad_len = a.hl;
+    a.recs[i] = d;
+}
+
+struct SplitArgs {
+    int hash_id;
+    uint32_t hl, n;
+    const uint8_t *ck, *h, *status;
+    uint8_t *k1, *k2, *hh;
+};
+
+/* symmetricstate.c:530-533; a failed session's keys are zeros */
+__global__ __launch_bounds__(HS_BLOCK) void hs_split(SplitArgs a)
+{
+    const uint32_t i = blockIdx.x * HS_BLOCK + threadIdx.x;
+    if (i >= a.n) return;
+    uint8_t ck[64], o1[64], o2[64];
+    hs_load_h(ck, a.ck + (size_t)i * a.hl, a.hl);
+    hs_hkdf(a.hash_id, a.hl, ck, nullptr, 0, o1, o2);
+    const bool failed = a.status[i] != 0;
+    for (int j = 0; j < 32; ++j) {
+        a.k1[(size_t)i * 32 + j] = failed ? 0 : o1[j];
+        a.k2[(size_t)i * 32 + j] = failed ? 0 : o2[j];
+    }
+    if (a.hh)
+        for (uint32_t j = 0; j < a.hl; ++j) a.hh[(size_t)i * a.hl + j] = a.h[(size_t)i * a.hl + j];
+    for (int j = 0; j < 64; ++j) ck[j] = o1[j] = o2[j] = 0;
+}
+
+dim3 hs_grid(uint32_t n) { return dim3((uint32_t)(((uint64_t)n + HS_BLOCK - 1) / HS_BLOCK)); }
+
+} // namespace
+
+struct NoiseAeadDevHandshake {
+    HsName name;
+    int role, action, index;
+    uint32_t n, hl;
+    bool keyed, ctx_stale;
+    uint64_t nonce;
+    size_t ctx_bytes;
+    /* the caller's private keys (read by the DH steps) */
+    const uint8_t *ls_priv, *le_priv;
+    uint64_t ls_stride, le_stride;
+    /* one device allocation, carved */
+    uint8_t *mem;
+    size_t mem_bytes;
+    uint8_t *ck, *h, *k, *ctx, *arena, *status, *step, *ls_pub, *le_pub, *re, *rs;
+    RecDesc *recs;
+    uint64_t ls_pub_stride, le_pub_stride;
+};
+
+namespace {
+
+typedef NoiseAeadDevHandshake Hs;
+
+const HsPattern &pattern_of(const Hs *hs) { return HS_PATTERNS[hs->name.pattern]; }
+
+HsMessage next_message(const Hs *hs) { return hs_message(pattern_of(hs), hs->role, hs->name.psk, hs->index, hs->keyed); }
+
+int mix_hash(Hs *hs, const uint8_t *src, uint64_t src_stride, uint32_t len, uint8_t *dst, uint64_t dst_stride,
+             const uint8_t *step, hipStream_t s)
+{
+    const MixHashStrided a = {hs->name.hash_id, hs->hl, hs->n, len, hs->h, src, src_stride, dst, dst_stride,
+                              hs->status, step};
+    hipLaunchKernelGGL(hs_mix_hash, hs_grid(hs->n), dim3(HS_BLOCK), 0, s, a);
+    return hip_rc(hipGetLastError());
+}
+
+int mix_key(Hs *hs, const uint8_t *ikm, uint64_t ikm_stride, bool zero_ikm, bool psk, hipStream_t s)
+{
+    const MixKeyArgs a = {hs->name.hash_id, hs->hl, hs->n, hs->ck, hs->k, hs->h, (uint8_t *)ikm, ikm_stride,
+                          zero_ikm, psk};
+    hipLaunchKernelGGL(hs_mix_key, hs_grid(hs->n), dim3(HS_BLOCK), 0, s, a);
+    if (!psk) {
+        hs->keyed = true;
+        hs->nonce = 0;
+        hs->ctx_stale = true;
+    }
+    return hip_rc(hipGetLastError());
+}
+
+/* encrypt_and_hash / decrypt_and_hash of `len` bytes for every session once
+   a key is set: seal or open under AD = h, then h = HASH(h || CT || tag) —
+   after an open only where the tag verified */
+int aead_step(Hs *hs, bool open, const uint8_t *in, uint64_t in_stride, uint8_t *out, uint64_t out_stride,
+              uint32_t len, hipStream_t s)
+{
+    const int cipher = hs->name.cipher_id;
+    int rc = NOISE_ERROR_NONE;
+    if (cipher == NOISE_CIPHER_AESGCM && hs->ctx_stale)
+        rc = noise_aead_dev_prepare(cipher, hs->k, hs->n, hs->ctx, s);
+    hs->ctx_stale = false;
+    if (rc) return rc;
+    const BuildRecs b = {hs->recs, hs->status, in_stride, out_stride, hs->nonce, hs->ctx_bytes, len, hs->hl, hs->n};
+    hipLaunchKernelGGL(hs_build_recs, hs_grid(hs->n), dim3(HS_BLOCK), 0, s, b);
+    rc = hip_rc(hipGetLastError());
+    if (rc) return rc;
+    NoiseAeadRagged job = {};
+    job.ctx_base = cipher == NOISE_CIPHER_AESGCM ? hs->ctx : hs->k;
+    job.recs = (const NoiseAeadRecord *)hs->recs;
+    /* an empty payload may come without a pointer; the ragged job wants one */
+    job.in = in ? in : hs->arena;
+    job.out = out ? out : hs->arena;
+    job.ad = hs->h;
+    job.status = hs->step;
+    job.n_records = hs->n;
+    rc = open ? noise_aead_dev_open_ragged(cipher, &job, s) : noise_aead_dev_seal_ragged(cipher, &job, s);
+    if (rc) return rc;
+    ++hs->nonce;
+    return open ? mix_hash(hs, job.in, in_stride, len + HS_MAC_LEN, nullptr, 0, hs->step, s)
+                : mix_hash(hs, job.out, out_stride, len + HS_MAC_LEN, nullptr, 0, nullptr, s);
+}
+
+int dh_step(Hs *hs, const HsStep &st, hipStream_t s)
+{
+    const uint8_t *priv = st.priv_static ? hs->ls_priv : hs->le_priv;
+    const uint64_t priv_stride = st.priv_static ? hs->ls_stride : hs->le_stride;
+    const int rc = noise_aead_dev_dh_calculate(NOISE_DH_CURVE25519, priv, priv_stride, st.pub_static ? hs->rs : hs->re,
+                                               HS_DH_LEN, hs->n, hs->arena, s);
+    return rc ? rc : mix_key(hs, hs->arena, HS_DH_LEN, true, false, s);
+}
+
+/* the tokens and the payload of the next message; write: payload -> msg */
+int run_message(Hs *hs, const HsMessage &m, bool write, uint8_t *msg, uint64_t msg_stride, uint8_t *payload,
+                uint64_t payload_stride, uint32_t payload_len, hipStream_t s)
+{
+    uint64_t off = 0;
+    int rc = NOISE_ERROR_NONE;
+    for (int t = 0; t < m.n_steps && !rc; ++t) {
+        const HsStep &st = m.steps[t];
+        uint8_t *at = msg + off;
+        switch (st.kind) {
+        case HS_STEP_E:
+            if (write) {
+                rc = mix_hash(hs, hs->le_pub, hs->le_pub_stride, HS_DH_LEN, at, msg_stride, nullptr, s);
+                if (!rc && st.mix_key) rc = mix_key(hs, hs->le_pub, hs->le_pub_stride, false, false, s);
+            } else {
+                rc = mix_hash(hs, at, msg_stride, HS_DH_LEN, hs->re, HS_DH_LEN, nullptr, s);
+                if (!rc) {
+                    hipLaunchKernelGGL(hs_null_check, hs_grid(hs->n), dim3(HS_BLOCK), 0, s, (const uint8_t *)hs->re,
+                                       hs->status, hs->n);
+                    rc = hip_rc(hipGetLastError());
+                }
+                if (!rc && st.mix_key) rc = mix_key(hs, hs->re, HS_DH_LEN, false, false, s);
+            }
+            off += HS_DH_LEN;
+            break;
+        case HS_STEP_S:
+            if (write)
+                rc = st.keyed ? aead_step(hs, false, hs->ls_pub, hs->ls_pub_stride, at, msg_stride, HS_DH_LEN, s)
+                              : mix_hash(hs, hs->ls_pub, hs->ls_pub_stride, HS_DH_LEN, at, msg_stride, nullptr, s);
+            else
+                rc = st.keyed ? aead_step(hs, true, at, msg_stride, hs->rs, HS_DH_LEN, HS_DH_LEN, s)
+                              : mix_hash(hs, at, msg_stride, HS_DH_LEN, hs->rs, HS_DH_LEN, nullptr, s);
+            off += HS_DH_LEN + (st.keyed ? HS_MAC_LEN : 0);
+            break;
+        case HS_STEP_DH:
+            rc = dh_step(hs, st, s);
+            break;
+        case HS_STEP_PAYLOAD:
+            if (write)
+                rc = st.keyed ? aead_step(hs, false, payload, payload_stride, at, msg_stride, payload_len, s)
+                              : mix_hash(hs, payload, payload_stride, payload_len, at, msg_stride, nullptr, s);
+            else
+                rc = st.keyed ? aead_step(hs, true, at, msg_stride, payload, payload_stride, payload_len, s)
+                              : mix_hash(hs, at, msg_stride, payload_len, payload, payload_stride, nullptr, s);
+            break;
+        }
+    }
+    return rc;
+}
+
+void advance(Hs *hs, const HsMessage &m)
+{
+    hs->keyed = m.keyed_after;
+    hs->action = m.next_action;
+    ++hs->index;
+}
+
+size_t carve(size_t &off, size_t bytes)
+{
+    const size_t at = off;
+    off += (bytes + 63) & ~(size_t)63;
+    return at;
+}
+
+/* everything _new launches, after the allocation */
+int start(Hs *hs, const NoiseAeadHandshakeConfig *cfg, hipStream_t s)
+{
+    const HsPattern &p = pattern_of(hs);
+    const HsNeeds need = hs_needs(p, hs->role);
+    int rc = hip_rc(hipMemsetAsync(hs->mem, 0, hs->mem_bytes, s));
+    /* the local public keys: one ladder launch each, one lane for a shared key */
+    if (!rc && need.local_static)
+        rc = noise_aead_dev_dh_public(NOISE_DH_CURVE25519, hs->ls_priv, hs->ls_stride, hs->ls_stride ? hs->n : 1,
+                                      hs->ls_pub, s);
+    if (!rc && need.local_ephemeral)
+        rc = noise_aead_dev_dh_public(NOISE_DH_CURVE25519, hs->le_priv, hs->le_stride, hs->le_stride ? hs->n : 1,
+                                      hs->le_pub, s);
+    if (!rc && need.remote_static) {
+        hipLaunchKernelGGL(hs_copy32, hs_grid(hs->n), dim3(HS_BLOCK), 0, s, cfg->d_remote_static_pub,
+                           cfg->remote_static_stride, hs->rs, hs->n);
+        rc = hip_rc(hipGetLastError());
+    }
+    if (rc) return rc;
+    InitArgs ia = {};
+    ia.hash_id = hs->name.hash_id;
+    ia.hl = hs->hl;
+    ia.n = hs->n;
+    ia.name_len = (uint32_t)strlen(cfg->protocol_name);
+    ia.h = hs->h;
+    ia.ck = hs->ck;
+    memcpy(ia.name, cfg->protocol_name, ia.name_len);
+    hipLaunchKernelGGL(hs_init, hs_grid(hs->n), dim3(HS_BLOCK), 0, s, ia);
+    rc = hip_rc(hipGetLastError());
+    /* handshakestate.c:822-877 */
+    if (!rc)
+        rc = mix_hash(hs, cfg->prologue_len ? cfg->d_prologue : hs->arena, cfg->prologue_stride, cfg->prologue_len,
+                      nullptr, 0, nullptr, s);
+    if (!rc && hs->name.psk) rc = mix_key(hs, cfg->d_psk, cfg->psk_stride, false, true, s);
+    const bool init = hs_is_initiator(hs->role);
+    if (!rc && p.pre_i_s)
+        rc = init ? mix_hash(hs, hs->ls_pub, hs->ls_pub_stride, HS_DH_LEN, nullptr, 0, nullptr, s)
+                  : mix_hash(hs, hs->rs, HS_DH_LEN, HS_DH_LEN, nullptr, 0, nullptr, s);
+    if (!rc && p.pre_r_s)
+        rc = init ? mix_hash(hs, hs->rs, HS_DH_LEN, HS_DH_LEN, nullptr, 0, nullptr, s)
+                  : mix_hash(hs, hs->ls_pub, hs->ls_pub_stride, HS_DH_LEN, nullptr, 0, nullptr, s);
+    return rc;
+}
+
+} // namespace
+
+extern "C" {
+
+int noise_aead_dev_handshake_new(NoiseAeadDevHandshake **out, const NoiseAeadHandshakeConfig *cfg, void *stream)
+{
+    if (!out) return NOISE_ERROR_INVALID_PARAM;
+    *out = nullptr;
+    HsName name;
+    int rc = hs_check_config(cfg, &name);
+    if (rc) return rc;
+    if (strlen(cfg->protocol_name) > HS_NAME_MAX) return NOISE_ERROR_UNKNOWN_NAME; /* no name in scope is */
+    Hs *hs = new (std::nothrow) Hs();
+    if (!hs) return NOISE_ERROR_NO_MEMORY;
+    hs->name = name;
+    hs->role = cfg->role;
+    hs->action = hs_first_action(cfg->role);
+    hs->n = cfg->n;
+    hs->hl = hs_hash_len(name.hash_id);
+    hs->ctx_bytes = noise_aead_dev_ctx_bytes(name.cipher_id);
+    hs->ls_priv = cfg->d_local_static_priv;
+    hs->ls_stride = cfg->local_static_stride;
+    hs->le_priv = cfg->d_local_ephemeral_priv;
+    hs->le_stride = cfg->local_ephemeral_stride;
+    hs->ls_pub_stride = hs->ls_stride ? HS_DH_LEN : 0;
+    hs->le_pub_stride = hs->le_stride ? HS_DH_LEN : 0;
+    if (hs->n) {
+        const size_t n = hs->n;
+        size_t off = 0;
+        const size_t o_ck = carve(off, n * hs->hl), o_h = carve(off, n * hs->hl), o_k = carve(off, n * 32);
+        const size_t o_ctx = carve(off, name.cipher_id == NOISE_CIPHER_AESGCM ? n * hs->ctx_bytes : 0);
+        const size_t o_arena = carve(off, n * 32), o_status = carve(off, n), o_step = carve(off, n);
+        const size_t o_ls = carve(off, n * 32), o_le = carve(off, n * 32), o_re = carve(off, n * 32);
+        const size_t o_rs = carve(off, n * 32), o_recs = carve(off, n * sizeof(RecDesc));
+        if (hipMalloc((void **)&hs->mem, off) != hipSuccess) {
+            delete hs;
+            return NOISE_ERROR_NO_MEMORY;
+        }
+        hs->mem_bytes = off;
+        uint8_t *m = hs->mem;
+        hs->ck = m + o_ck; hs->h = m + o_h; hs->k = m + o_k; hs->ctx = m + o_ctx; hs->arena = m + o_arena;
+        hs->status = m + o_status; hs->step = m + o_step; hs->ls_pub = m + o_ls; hs->le_pub = m + o_le;
+        hs->re = m + o_re; hs->rs = m + o_rs; hs->recs = (RecDesc *)(m + o_recs);
+        rc = start(hs, cfg, (hipStream_t)stream);
+        if (rc) {
+            noise_aead_dev_handshake_free(hs);
+            return rc;
+        }
+    }
+    *out = hs;
+    return NOISE_ERROR_NONE;
+}
+
+int noise_aead_dev_handshake_free(NoiseAeadDevHandshake *hs)
+{
+    if (!hs) return NOISE_ERROR_INVALID_PARAM;
+    int rc = NOISE_ERROR_NONE;
+    if (hs->mem) {
+        /* work of this object may still be in flight on the caller's streams */
+        rc = hip_rc(hipDeviceSynchronize());
+        const int rc2 = hip_rc(hipMemset(hs->mem, 0, hs->mem_bytes));
+        const int rc3 = hip_rc(hipFree(hs->mem));
+        rc = rc ? rc : (rc2 ? rc2 : rc3);
+    }
+    memset((void *)hs, 0, sizeof(*hs));
+    delete hs;
+    return rc;
+}
+
+int noise_aead_dev_handshake_get_action(const NoiseAeadDevHandshake *hs) { return hs ? hs->action : NOISE_ACTION_NONE; }
+
+size_t noise_aead_dev_handshake_overhead(const NoiseAeadDevHandshake *hs)
+{
+    if (!hs || (hs->action != NOISE_ACTION_WRITE_MESSAGE && hs->action != NOISE_ACTION_READ_MESSAGE)) return 0;
+    return next_message(hs).overhead;
+}
+
+int noise_aead_dev_handshake_write_message(NoiseAeadDevHandshake *hs, const uint8_t *d_payload,
+                                           uint64_t payload_stride, uint32_t payload_len, uint8_t *d_msg,
+                                           uint64_t msg_stride, void *stream)
+{
+    if (!hs) return NOISE_ERROR_INVALID_PARAM;
+    if (hs->action != NOISE_ACTION_WRITE_MESSAGE) return NOISE_ERROR_INVALID_STATE;
+    const HsMessage m = next_message(hs);
+    int rc = hs_check_write(hs->action, hs->n, m.overhead, d_payload, payload_stride, payload_len, d_msg, msg_stride);
+    if (rc) return rc;
+    if (hs->n)
+        rc = run_message(hs, m, true, d_msg, msg_stride, (uint8_t *)d_payload, payload_stride, payload_len,
+                         (hipStream_t)stream);
+    advance(hs, m);
+    return rc;
+}
+
+int noise_aead_dev_handshake_read_message(NoiseAeadDevHandshake *hs, const uint8_t *d_msg, uint64_t msg_stride,
+                                          uint32_t msg_len, uint8_t *d_payload, uint64_t payload_stride,
+                                          void *stream)
+{
+    if (!hs) return NOISE_ERROR_INVALID_PARAM;
+    if (hs->action != NOISE_ACTION_READ_MESSAGE) return NOISE_ERROR_INVALID_STATE;
+    const HsMessage m = next_message(hs);
+    int rc = hs_check_read(hs->action, hs->n, m.overhead, d_msg, msg_stride, msg_len, d_payload, payload_stride);
+    if (rc) return rc;
+    if (hs->n)
+        rc = run_message(hs, m, false, (uint8_t *)d_msg, msg_stride, d_payload, payload_stride, msg_len - m.overhead,
+                         (hipStream_t)stream);
+    advance(hs, m);
+    return rc;
+}
+
+int noise_aead_dev_handshake_split(NoiseAeadDevHandshake *hs, uint8_t *d_k1, uint8_t *d_k2,
+                                   uint8_t *d_handshake_hash, void *stream)
+{
+    if (!hs) return NOISE_ERROR_INVALID_PARAM;
+    int rc = hs_check_split(hs->action, hs->n, hs->hl, d_k1, d_k2, d_handshake_hash);
+    if (rc) return rc;
+    if (hs->n) {
+        const SplitArgs a = {hs->name.hash_id, hs->hl, hs->n, hs->ck, hs->h, hs->status, d_k1, d_k2, d_handshake_hash};
+        hipLaunchKernelGGL(hs_split, hs_grid(hs->n), dim3(HS_BLOCK), 0, (hipStream_t)stream, a);
+        rc = hip_rc(hipGetLastError());
+    }
+    hs->action = NOISE_ACTION_COMPLETE;
+    return rc;
+}
+
+const uint8_t *noise_aead_dev_handshake_status(const NoiseAeadDevHandshake *hs) { return hs ? hs->status : nullptr; }
+
+const uint8_t *noise_aead_dev_handshake_remote_static(const NoiseAeadDevHandshake *hs) { return hs ? hs->rs : nullptr; }
+
+} // extern "C"

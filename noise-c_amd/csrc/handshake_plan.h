@@ -1,0 +1,351 @@
+/*
+ * handshake_plan.h — the host-only half of the batched Noise handshake
+ * (include/noise_aead_hip.h section 8): the protocol-name parser, the token
+ * table of the fifteen one-way and interactive patterns, the ordered steps and
+ * the overhead of every message for (pattern, role, prefix, message index),
+ * and the argument checks of the entry points.
+ *
+ * No HIP header is included and no device pointer is dereferenced, so all of
+ * it compiles with a host compiler alone and runs under ASan/UBSan
+ * (asan/handshake_check.cpp, tests/test_handshake_host.py) — in the manner of
+ * dispatch.h.  handshake.hip turns the steps into launches.
+ *
+ * The table is the Noise specification's (section 7); the parser follows the
+ * name grammar prefix_pattern_dh_cipher_hash.  The old-style "NoisePSK" prefix
+ * is the one of noise-c v0.0.1: HKDF(ck, psk) after the prologue, and every
+ * `e` token is also a MixKey of the ephemeral public key.
+ */
+#pragma once
+#include "noise_aead_hip.h"
+
+#include <stdint.h>
+#include <string.h>
+
+namespace na {
+
+enum HsTok : uint8_t { HT_E, HT_S, HT_EE, HT_ES, HT_SE, HT_SS };
+
+constexpr int HS_MAX_MSGS = 3, HS_MAX_TOKS = 5, HS_MAX_STEPS = HS_MAX_TOKS + 1;
+constexpr uint32_t HS_DH_LEN = 32, HS_MAC_LEN = 16;
+
+struct HsPattern {
+    const char *name;
+    bool pre_i_s, pre_r_s; /* the initiator's / responder's static key is a pre-message */
+    uint8_t n_msgs;
+    uint8_t n_toks[HS_MAX_MSGS];
+    HsTok toks[HS_MAX_MSGS][HS_MAX_TOKS];
+};
+
+/* initiator pre-message | responder pre-message | messages (-> <- -> ...) */
+constexpr HsPattern HS_PATTERNS[] = {
+    {"N", false, true, 1, {2}, {{HT_E, HT_ES}}},
+    {"K", true, true, 1, {3}, {{HT_E, HT_ES, HT_SS}}},
+    {"X", false, true, 1, {4}, {{HT_E, HT_ES, HT_S, HT_SS}}},
+    {"NN", false, false, 2, {1, 2}, {{HT_E}, {HT_E, HT_EE}}},
+    {"NK", false, true, 2, {2, 2}, {{HT_E, HT_ES}, {HT_E, HT_EE}}},
+    {"NX", false, false, 2, {1, 4}, {{HT_E}, {HT_E, HT_EE, HT_S, HT_ES}}},
+    {"XN", false, false, 3, {1, 2, 2}, {{HT_E}, {HT_E, HT_EE}, {HT_S, HT_SE}}},
+    {"XK", false, true, 3, {2, 2, 2}, {{HT_E, HT_ES}, {HT_E, HT_EE}, {HT_S, HT_SE}}},
+    {"XX", false, false, 3, {1, 4, 2}, {{HT_E}, {HT_E, HT_EE, HT_S, HT_ES}, {HT_S, HT_SE}}},
+    {"KN", true, false, 2, {1, 3}, {{HT_E}, {HT_E, HT_EE, HT_SE}}},
+    {"KK", true, true, 2, {3, 3}, {{HT_E, HT_ES, HT_SS}, {HT_E, HT_EE, HT_SE}}},
+    {"KX", true, false, 2, {1, 5}, {{HT_E}, {HT_E, HT_EE, HT_SE, HT_S, HT_ES}}},
+    {"IN", false, false, 2, {2, 3}, {{HT_E, HT_S}, {HT_E, HT_EE, HT_SE}}},
+    {"IK", false, true, 2, {4, 3}, {{HT_E, HT_ES, HT_S, HT_SS}, {HT_E, HT_EE, HT_SE}}},
+    {"IX", false, false, 2, {2, 5}, {{HT_E, HT_S}, {HT_E, HT_EE, HT_SE, HT_S, HT_ES}}},
+};
+constexpr int HS_N_PATTERNS = (int)(sizeof(HS_PATTERNS) / sizeof(HS_PATTERNS[0]));
+
+/* ------------------------------------------------------------ name parser */
+
+struct HsName {
+    int pattern; /* index into HS_PATTERNS */
+    int cipher_id, hash_id;
+    bool psk;
+};
+
+inline bool hs_field_is(const char *f, size_t n, const char *word) { return strlen(word) == n && !memcmp(f, word, n); }
+
+inline int hs_find_pattern(const char *f, size_t n)
+{
+    for (int i = 0; i < HS_N_PATTERNS; ++i)
+        if (hs_field_is(f, n, HS_PATTERNS[i].name)) return i;
+    return -1;
+}
+
+/* a DH field this library knows of: 1 Curve25519, 2 one it does not compute
+   (Curve448, NewHope), 0 no DH name */
+inline int hs_dh_word(const char *f, size_t n)
+{
+    if (hs_field_is(f, n, "25519")) return 1;
+    return hs_field_is(f, n, "448") || hs_field_is(f, n, "NewHope") ? 2 : 0;
+}
+
+/* prefix_pattern_dh_cipher_hash.  NOISE_ERROR_NONE and *out for the names in
+   scope; NOISE_ERROR_NOT_APPLICABLE for a well-formed name that needs
+   Curve448, NewHope, a hybrid ("hfs") pattern or XXfallback;
+   NOISE_ERROR_UNKNOWN_NAME for everything else. */
+inline int hs_parse_name(const char *name, HsName *out)
+{
+    if (!name || !out) return NOISE_ERROR_INVALID_PARAM;
+    const char *f[5];
+    size_t n[5];
+    int nf = 0;
+    const char *p = name;
+    for (;;) {
+        const char *u = strchr(p, '_');
+        if (nf == 5) return NOISE_ERROR_UNKNOWN_NAME;
+        f[nf] = p;
+        n[nf] = u ? (size_t)(u - p) : strlen(p);
+        ++nf;
+        if (!u) break;
+        p = u + 1;
+    }
+    if (nf != 5) return NOISE_ERROR_UNKNOWN_NAME;
+    bool unsupported = false;
+    HsName r = {};
+    if (hs_field_is(f[0], n[0], "NoisePSK")) r.psk = true;
+    else if (!hs_field_is(f[0], n[0], "Noise")) return NOISE_ERROR_UNKNOWN_NAME;
+    /* pattern: one of the fifteen or XXfallback, then an optional hybrid
+       modifier ("hfs" after a base pattern, "+hfs" after "fallback") */
+    {
+        size_t len = n[1];
+        const bool hfs = len > 3 && !memcmp(f[1] + len - 3, "hfs", 3);
+        if (hfs) len -= 3;
+        bool fallback = false;
+        if (hfs && len > 1 && f[1][len - 1] == '+') {
+            --len;
+            fallback = true; /* "+hfs" only follows another modifier */
+        }
+        if (hs_field_is(f[1], len, "XXfallback")) {
+            unsupported = true;
+        } else if (fallback) {
+            return NOISE_ERROR_UNKNOWN_NAME;
+        } else {
+            r.pattern = hs_find_pattern(f[1], len);
+            if (r.pattern < 0) return NOISE_ERROR_UNKNOWN_NAME;
+            if (hfs) unsupported = true;
+        }
+    }
+    /* dh: one name, or two joined by '+' (a hybrid's second exchange) */
+    {
+        const char *plus = (const char *)memchr(f[2], '+', n[2]);
+        const size_t a = plus ? (size_t)(plus - f[2]) : n[2];
+        const int w = hs_dh_word(f[2], a);
+        if (!w) return NOISE_ERROR_UNKNOWN_NAME;
+        if (w != 1) unsupported = true;
+        if (plus) {
+            if (!hs_dh_word(plus + 1, n[2] - a - 1)) return NOISE_ERROR_UNKNOWN_NAME;
+            unsupported = true;
+        }
+    }
+    if (hs_field_is(f[3], n[3], "ChaChaPoly")) r.cipher_id = NOISE_CIPHER_CHACHAPOLY;
+    else if (hs_field_is(f[3], n[3], "AESGCM")) r.cipher_id = NOISE_CIPHER_AESGCM;
+    else return NOISE_ERROR_UNKNOWN_NAME;
+    if (hs_field_is(f[4], n[4], "BLAKE2s")) r.hash_id = NOISE_HASH_BLAKE2s;
+    else if (hs_field_is(f[4], n[4], "BLAKE2b")) r.hash_id = NOISE_HASH_BLAKE2b;
+    else if (hs_field_is(f[4], n[4], "SHA256")) r.hash_id = NOISE_HASH_SHA256;
+    else if (hs_field_is(f[4], n[4], "SHA512")) r.hash_id = NOISE_HASH_SHA512;
+    else return NOISE_ERROR_UNKNOWN_NAME;
+    if (unsupported) return NOISE_ERROR_NOT_APPLICABLE;
+    *out = r;
+    return NOISE_ERROR_NONE;
+}
+
+inline uint32_t hs_hash_len(int hash_id)
+{
+    return hash_id == NOISE_HASH_BLAKE2b || hash_id == NOISE_HASH_SHA512 ? 64 : 32;
+}
+
+/* ------------------------------------------------------------------ steps */
+
+enum HsStepKind : uint8_t {
+    HS_STEP_E,       /* the ephemeral public key, in the clear; mix_key under NoisePSK */
+    HS_STEP_S,       /* the static public key through encrypt/decrypt_and_hash */
+    HS_STEP_DH,      /* a ladder launch and MixKey of its output */
+    HS_STEP_PAYLOAD, /* the payload through encrypt/decrypt_and_hash */
+};
+
+struct HsStep {
+    HsStepKind kind;
+    HsTok tok;                /* E, S, DH */
+    bool keyed;               /* S, PAYLOAD: a key is set, so AEAD and 16 more bytes */
+    bool mix_key;             /* E: NoisePSK */
+    bool priv_static;         /* DH: the local static key (else the local ephemeral) */
+    bool pub_static;          /* DH: the remote static key (else the remote ephemeral) */
+};
+
+struct HsMessage {
+    int n_steps;
+    HsStep steps[HS_MAX_STEPS];
+    uint32_t overhead; /* bytes the message adds to its payload */
+    bool keyed_after;
+    int next_action;   /* of the role the plan was made for */
+};
+
+inline bool hs_is_initiator(int role) { return role == NOISE_ROLE_INITIATOR; }
+
+/* whether a key is set when message `index` starts: a DH token, or an `e`
+   under NoisePSK, of an earlier message set it (the PSK start-up step itself
+   sets none) */
+inline bool hs_keyed_before(const HsPattern &p, bool psk, int index)
+{
+    for (int m = 0; m < index && m < p.n_msgs; ++m)
+        for (int t = 0; t < p.n_toks[m]; ++t)
+            if (p.toks[m][t] >= HT_EE || (psk && p.toks[m][t] == HT_E)) return true;
+    return false;
+}
+
+/* Message `index` (0: the initiator's first) as `role` sees it, whether it
+   writes or reads it; keyed: hs_keyed_before. */
+inline HsMessage hs_message(const HsPattern &p, int role, bool psk, int index, bool keyed)
+{
+    HsMessage m = {};
+    const bool init = hs_is_initiator(role);
+    for (int t = 0; t < p.n_toks[index]; ++t) {
+        HsStep s = {};
+        s.tok = p.toks[index][t];
+        switch (s.tok) {
+        case HT_E:
+            s.kind = HS_STEP_E;
+            s.mix_key = psk;
+            m.overhead += HS_DH_LEN;
+            if (psk) keyed = true;
+            break;
+        case HT_S:
+            s.kind = HS_STEP_S;
+            s.keyed = keyed;
+            m.overhead += HS_DH_LEN + (keyed ? HS_MAC_LEN : 0);
+            break;
+        default:
+            s.kind = HS_STEP_DH;
+            s.priv_static = s.tok == HT_SS || s.tok == (init ? HT_SE : HT_ES);
+            s.pub_static = s.tok == HT_SS || s.tok == (init ? HT_ES : HT_SE);
+            keyed = true;
+            break;
+        }
+        m.steps[m.n_steps++] = s;
+    }
+    HsStep pl = {};
+    pl.kind = HS_STEP_PAYLOAD;
+    pl.keyed = keyed;
+    m.overhead += keyed ? HS_MAC_LEN : 0;
+    m.steps[m.n_steps++] = pl;
+    m.keyed_after = keyed;
+    if (index + 1 == p.n_msgs) m.next_action = NOISE_ACTION_SPLIT;
+    else m.next_action = ((index + 1) % 2 == 0) == init ? NOISE_ACTION_WRITE_MESSAGE : NOISE_ACTION_READ_MESSAGE;
+    return m;
+}
+
+/* the first action of a role */
+inline int hs_first_action(int role)
+{
+    return hs_is_initiator(role) ? NOISE_ACTION_WRITE_MESSAGE : NOISE_ACTION_READ_MESSAGE;
+}
+
+/* What a role must bring: its static key pair when it has a pre-message `s`
+   or sends an `s` token, its ephemeral private key when it sends an `e`, the
+   remote static public key when the other side's `s` is a pre-message. */
+struct HsNeeds {
+    bool local_static, local_ephemeral, remote_static;
+};
+
+inline HsNeeds hs_needs(const HsPattern &p, int role)
+{
+    const bool init = hs_is_initiator(role);
+    HsNeeds r = {init ? p.pre_i_s : p.pre_r_s, false, init ? p.pre_r_s : p.pre_i_s};
+    for (int m = init ? 0 : 1; m < p.n_msgs; m += 2)
+        for (int t = 0; t < p.n_toks[m]; ++t) {
+            if (p.toks[m][t] == HT_S) r.local_static = true;
+            if (p.toks[m][t] == HT_E) r.local_ephemeral = true;
+        }
+    return r;
+}
+
+/* --------------------------------------------------------- argument checks
+   Pointers are compared as numbers and never dereferenced. */
+
+typedef unsigned __int128 hs_u128;
+
+inline bool hs_key_stride_ok(uint64_t stride) { return stride == 0 || stride >= HS_DH_LEN; }
+
+/* [p, p + (n - 1) * stride + len) of an input (stride 0: one value) meets
+   the same of an output */
+inline bool hs_spans_meet(const void *in, uint64_t in_stride, uint64_t in_len, const void *out, uint64_t out_stride,
+                          uint64_t out_len, uint32_t n)
+{
+    if (!n || !in_len || !out_len) return false;
+    const hs_u128 a = (uintptr_t)in, b = (uintptr_t)out;
+    const hs_u128 a_hi = a + (hs_u128)(n - 1) * in_stride + in_len, b_hi = b + (hs_u128)(n - 1) * out_stride + out_len;
+    return a < b_hi && b < a_hi;
+}
+
+/* noise_aead_dev_handshake_new: the configuration against the parsed name */
+inline int hs_check_config(const NoiseAeadHandshakeConfig *cfg, HsName *name)
+{
+    if (!cfg || !name || !cfg->protocol_name) return NOISE_ERROR_INVALID_PARAM;
+    const int rc = hs_parse_name(cfg->protocol_name, name);
+    if (rc) return rc;
+    if (cfg->role != NOISE_ROLE_INITIATOR && cfg->role != NOISE_ROLE_RESPONDER) return NOISE_ERROR_INVALID_PARAM;
+    const HsNeeds need = hs_needs(HS_PATTERNS[name->pattern], cfg->role);
+    if ((need.local_static && !cfg->d_local_static_priv) || (need.local_ephemeral && !cfg->d_local_ephemeral_priv))
+        return NOISE_ERROR_LOCAL_KEY_REQUIRED;
+    if (need.remote_static && !cfg->d_remote_static_pub) return NOISE_ERROR_REMOTE_KEY_REQUIRED;
+    if (name->psk && !cfg->d_psk) return NOISE_ERROR_PSK_REQUIRED;
+    if (cfg->prologue_len && !cfg->d_prologue) return NOISE_ERROR_INVALID_PARAM;
+    if (cfg->prologue_len && cfg->prologue_stride && cfg->prologue_stride < cfg->prologue_len)
+        return NOISE_ERROR_INVALID_PARAM;
+    if ((name->psk && !hs_key_stride_ok(cfg->psk_stride)) ||
+        (need.local_static && !hs_key_stride_ok(cfg->local_static_stride)) ||
+        (need.local_ephemeral && !hs_key_stride_ok(cfg->local_ephemeral_stride)) ||
+        (need.remote_static && !hs_key_stride_ok(cfg->remote_static_stride)))
+        return NOISE_ERROR_INVALID_PARAM;
+    return NOISE_ERROR_NONE;
+}
+
+/* noise_aead_dev_handshake_write_message; NOISE_ERROR_NONE with n == 0 once
+   the state and the lengths are right */
+inline int hs_check_write(int action, uint32_t n, uint32_t overhead, const void *d_payload, uint64_t payload_stride,
+                          uint32_t payload_len, const void *d_msg, uint64_t msg_stride)
+{
+    if (action != NOISE_ACTION_WRITE_MESSAGE) return NOISE_ERROR_INVALID_STATE;
+    if ((uint64_t)payload_len + overhead > NOISE_MAX_PAYLOAD_LEN) return NOISE_ERROR_INVALID_LENGTH;
+    if (!n) return NOISE_ERROR_NONE;
+    const uint32_t msg_len = payload_len + overhead;
+    if (!d_msg || (payload_len && !d_payload)) return NOISE_ERROR_INVALID_PARAM;
+    if (msg_stride < msg_len) return NOISE_ERROR_INVALID_PARAM;
+    if (payload_len && payload_stride && payload_stride < payload_len) return NOISE_ERROR_INVALID_PARAM;
+    if (hs_spans_meet(d_payload, payload_stride, payload_len, d_msg, msg_stride, msg_len, n)) return NOISE_ERROR_INVALID_PARAM;
+    return NOISE_ERROR_NONE;
+}
+
+/* noise_aead_dev_handshake_read_message */
+inline int hs_check_read(int action, uint32_t n, uint32_t overhead, const void *d_msg, uint64_t msg_stride,
+                         uint32_t msg_len, const void *d_payload, uint64_t payload_stride)
+{
+    if (action != NOISE_ACTION_READ_MESSAGE) return NOISE_ERROR_INVALID_STATE;
+    if (msg_len > NOISE_MAX_PAYLOAD_LEN || msg_len < overhead) return NOISE_ERROR_INVALID_LENGTH;
+    if (!n) return NOISE_ERROR_NONE;
+    const uint32_t payload_len = msg_len - overhead;
+    if (!d_msg || (payload_len && !d_payload)) return NOISE_ERROR_INVALID_PARAM;
+    if (msg_stride && msg_stride < msg_len) return NOISE_ERROR_INVALID_PARAM;
+    if (payload_len && payload_stride < payload_len) return NOISE_ERROR_INVALID_PARAM;
+    if (hs_spans_meet(d_msg, msg_stride, msg_len, d_payload, payload_stride, payload_len, n)) return NOISE_ERROR_INVALID_PARAM;
+    return NOISE_ERROR_NONE;
+}
+
+/* noise_aead_dev_handshake_split: the three packed outputs must be disjoint */
+inline int hs_check_split(int action, uint32_t n, uint32_t hash_len, const void *d_k1, const void *d_k2,
+                          const void *d_hh)
+{
+    if (action != NOISE_ACTION_SPLIT) return NOISE_ERROR_INVALID_STATE;
+    if (!n) return NOISE_ERROR_NONE;
+    if (!d_k1 || !d_k2) return NOISE_ERROR_INVALID_PARAM;
+    const uint64_t kb = 32ull * n, hb = (uint64_t)hash_len * n;
+    if (hs_spans_meet(d_k1, 0, kb, d_k2, 0, kb, 1)) return NOISE_ERROR_INVALID_PARAM;
+    if (d_hh && (hs_spans_meet(d_k1, 0, kb, d_hh, 0, hb, 1) || hs_spans_meet(d_k2, 0, kb, d_hh, 0, hb, 1)))
+        return NOISE_ERROR_INVALID_PARAM;
+    return NOISE_ERROR_NONE;
+}
+
+} // namespace na

@@ -32,11 +32,23 @@ ERROR_NO_MEMORY = NOISE_ID("E", 1)
 ERROR_UNKNOWN_ID = NOISE_ID("E", 2)
 ERROR_UNKNOWN_NAME = NOISE_ID("E", 3)
 ERROR_MAC_FAILURE = NOISE_ID("E", 4)
+ERROR_NOT_APPLICABLE = NOISE_ID("E", 5)
 ERROR_SYSTEM = NOISE_ID("E", 6)
+ERROR_REMOTE_KEY_REQUIRED = NOISE_ID("E", 7)
+ERROR_LOCAL_KEY_REQUIRED = NOISE_ID("E", 8)
+ERROR_PSK_REQUIRED = NOISE_ID("E", 9)
 ERROR_INVALID_LENGTH = NOISE_ID("E", 10)
 ERROR_INVALID_PARAM = NOISE_ID("E", 11)
 ERROR_INVALID_STATE = NOISE_ID("E", 12)
 ERROR_INVALID_NONCE = NOISE_ID("E", 13)
+ERROR_INVALID_PUBLIC_KEY = NOISE_ID("E", 15)
+ROLE_INITIATOR = NOISE_ID("R", 1)  # constants.h:111-112
+ROLE_RESPONDER = NOISE_ID("R", 2)
+ACTION_NONE = 0  # constants.h:115-120
+ACTION_WRITE_MESSAGE = NOISE_ID("A", 1)
+ACTION_READ_MESSAGE = NOISE_ID("A", 2)
+ACTION_SPLIT = NOISE_ID("A", 4)
+ACTION_COMPLETE = NOISE_ID("A", 5)
 MAX_PAYLOAD_LEN = 65535
 HASH_BLAKE2s = NOISE_ID("H", 1)  # constants.h:43-46
 HASH_BLAKE2b = NOISE_ID("H", 2)
@@ -79,6 +91,15 @@ class NoiseAeadRagged(C.Structure):
                 ("out", C.c_void_p), ("ad", C.c_void_p), ("status", C.c_void_p),
                 ("n_records", C.c_uint32), ("lanes_per_record", C.c_uint32),
                 ("flags", C.c_uint32), ("reserved_", C.c_uint32)]
+
+
+class NoiseAeadHandshakeConfig(C.Structure):
+    _fields_ = [("protocol_name", C.c_char_p), ("role", C.c_int), ("n", C.c_uint32),
+                ("d_prologue", C.c_void_p), ("prologue_stride", C.c_uint64), ("prologue_len", C.c_uint32),
+                ("d_psk", C.c_void_p), ("psk_stride", C.c_uint64),
+                ("d_local_static_priv", C.c_void_p), ("local_static_stride", C.c_uint64),
+                ("d_local_ephemeral_priv", C.c_void_p), ("local_ephemeral_stride", C.c_uint64),
+                ("d_remote_static_pub", C.c_void_p), ("remote_static_stride", C.c_uint64)]
 
 
 FLAG_FAST = 1
@@ -150,6 +171,15 @@ def lib() -> C.CDLL:
         "noise_aead_dev_pad": (i, [vp, vp, C.c_uint64, vp, C.c_uint32, C.c_uint32, i, vp, vp]),
         "noise_aead_dev_dh_calculate": (i, [i, vp, C.c_uint64, vp, C.c_uint64, C.c_uint32, vp, vp]),
         "noise_aead_dev_dh_public": (i, [i, vp, C.c_uint64, C.c_uint32, vp, vp]),
+        "noise_aead_dev_handshake_new": (i, [P(vp), P(NoiseAeadHandshakeConfig), vp]),
+        "noise_aead_dev_handshake_free": (i, [vp]),
+        "noise_aead_dev_handshake_get_action": (i, [vp]),
+        "noise_aead_dev_handshake_overhead": (sz, [vp]),
+        "noise_aead_dev_handshake_write_message": (i, [vp, vp, C.c_uint64, C.c_uint32, vp, C.c_uint64, vp]),
+        "noise_aead_dev_handshake_read_message": (i, [vp, vp, C.c_uint64, C.c_uint32, vp, C.c_uint64, vp]),
+        "noise_aead_dev_handshake_split": (i, [vp, vp, vp, vp, vp]),
+        "noise_aead_dev_handshake_status": (vp, [vp]),
+        "noise_aead_dev_handshake_remote_static": (vp, [vp]),
         "noise_strerror": (i, [i, C.c_char_p, sz]),
         "noise_perror": (None, [C.c_char_p, i]),
         "noise_aead_debug_batch_stats": (None, [P(C.c_uint64), P(C.c_uint64)]),
@@ -455,6 +485,64 @@ def dev_dh_public(dh_id: int, *, priv: int, priv_stride: int = 32, n: int, pub_o
     """noise_aead_dev_dh_public: the public key of each of n private keys."""
     return lib().noise_aead_dev_dh_public(dh_id, priv or None, priv_stride, n, pub_out or None,
                                           stream or None)
+
+
+# ---- batched handshakes (include/noise_aead_hip.h section 8); `hs` is the
+# NoiseAeadDevHandshake* as an integer, every data argument a device pointer
+
+def dev_handshake_new(name, role: int, n: int, *, prologue: int = 0, prologue_stride: int = 0,
+                      prologue_len: int = 0, psk: int = 0, psk_stride: int = 32, local_static: int = 0,
+                      local_static_stride: int = 32, local_ephemeral: int = 0, local_ephemeral_stride: int = 32,
+                      remote_static: int = 0, remote_static_stride: int = 32, stream: int = 0):
+    """noise_aead_dev_handshake_new: (rc, hs); hs is None unless rc == 0."""
+    if isinstance(name, str):
+        name = name.encode()
+    cfg = NoiseAeadHandshakeConfig(name, role, n, prologue or None, prologue_stride, prologue_len,
+                                   psk or None, psk_stride, local_static or None, local_static_stride,
+                                   local_ephemeral or None, local_ephemeral_stride,
+                                   remote_static or None, remote_static_stride)
+    hs = C.c_void_p()
+    rc = lib().noise_aead_dev_handshake_new(C.byref(hs), C.byref(cfg), stream or None)
+    return rc, hs.value
+
+
+def dev_handshake_free(hs: int) -> int:
+    return lib().noise_aead_dev_handshake_free(hs)
+
+
+def dev_handshake_get_action(hs: int) -> int:
+    return lib().noise_aead_dev_handshake_get_action(hs)
+
+
+def dev_handshake_overhead(hs: int) -> int:
+    return lib().noise_aead_dev_handshake_overhead(hs)
+
+
+def dev_handshake_write_message(hs: int, *, payload: int = 0, payload_stride: int = 0, payload_len: int = 0,
+                                msg: int, msg_stride: int, stream: int = 0) -> int:
+    return lib().noise_aead_dev_handshake_write_message(hs, payload or None, payload_stride, payload_len,
+                                                        msg or None, msg_stride, stream or None)
+
+
+def dev_handshake_read_message(hs: int, *, msg: int, msg_stride: int, msg_len: int, payload: int = 0,
+                               payload_stride: int = 0, stream: int = 0) -> int:
+    return lib().noise_aead_dev_handshake_read_message(hs, msg or None, msg_stride, msg_len, payload or None,
+                                                       payload_stride, stream or None)
+
+
+def dev_handshake_split(hs: int, *, k1: int, k2: int, handshake_hash: int = 0, stream: int = 0) -> int:
+    return lib().noise_aead_dev_handshake_split(hs, k1 or None, k2 or None, handshake_hash or None,
+                                                stream or None)
+
+
+def dev_handshake_status(hs: int) -> int:
+    """device pointer of the n status bytes (0 ok, 1 MAC failure, 3 null ephemeral)"""
+    return lib().noise_aead_dev_handshake_status(hs) or 0
+
+
+def dev_handshake_remote_static(hs: int) -> int:
+    """device pointer of the n x 32 remote static public keys"""
+    return lib().noise_aead_dev_handshake_remote_static(hs) or 0
 
 
 def dev_fill_splitmix(d_out: int, nbytes: int, seed: int, word0: int = 0, stream: int = 0) -> int:
