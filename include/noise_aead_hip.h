@@ -599,6 +599,102 @@ int noise_aead_dev_handshake_split(NoiseAeadDevHandshake *hs, uint8_t *d_k1, uin
 const uint8_t *noise_aead_dev_handshake_status(const NoiseAeadDevHandshake *hs);
 const uint8_t *noise_aead_dev_handshake_remote_static(const NoiseAeadDevHandshake *hs);
 
+/* ------------------------------------------------ 9. device-resident transport sessions
+ *
+ * The transport phase of n Noise sessions without a host round trip: what
+ * noise_wire_seal / _open / _echo (section 3b) do for one pair of
+ * CipherStates, done for session i of the batch alone, in one call for all
+ * sessions.  An opaque host object owns the device state: a send and a
+ * receive key context and a send and a receive nonce per session, and what a
+ * call needs (descriptors and statuses for max_frames records, twice the
+ * descriptors for an echo, per-session counts and bases, scan scratch), all
+ * allocated by _new.  A message call allocates nothing, copies nothing to the
+ * host and never synchronises.  Every data pointer is a device pointer; every
+ * call is asynchronous on `stream`; the calls of one object must be issued in
+ * stream order (one stream, or streams the caller orders).
+ *
+ * _new takes the two packed arrays of n 32-byte keys exactly as
+ * noise_aead_dev_handshake_split / noise_aead_dev_split write them and builds
+ * the contexts with noise_aead_dev_prepare: the initiator sends under k1 and
+ * receives under k2, the responder sends under k2 and receives under k1.
+ * All 2n nonces start at 0.  The keys are consumed: the caller may scrub them
+ * once `stream` has passed the call.  _free scrubs every device array the
+ * object owns before freeing it (it waits for the device to do so), at any
+ * point.  _nonces returns the object's device array of n nonces of one
+ * direction (0 send, 1 receive; NULL for anything else, and for n == 0): that
+ * array is the state, and a caller may read or write it in stream order — the
+ * batch form of noise_cipherstate_set_nonce.
+ *
+ * A call: session i's stream is the d_len[i] bytes at d_wire + d_off[i]
+ * (no alignment needed; d_len[i] may be 0), holding frames in the format of
+ * section 3b: a 2-byte big-endian L, then L bytes.  The streams of different
+ * sessions are disjoint; the offsets live in device memory, so this is the
+ * caller's guarantee (not checked, as for the ragged calls).  For each
+ * session alone the result is that of noise_wire_seal / _open / _echo on that
+ * stream with that session's states:
+ *   - frames are taken in order from the start of the stream, frame k under
+ *     nonce[i] + k;
+ *   - the walk stops at a partial frame with NOISE_ERROR_NONE, at a complete
+ *     frame with L < 16 with NOISE_ERROR_INVALID_LENGTH, and where
+ *     nonce + k == 2^64 - 1 with NOISE_ERROR_INVALID_NONCE (an echo: where
+ *     either direction runs out; both directions advance by the same k).  The
+ *     stopping frame and everything after it are untouched;
+ *   - seal_frames: each walked frame's L - 16 plaintext bytes and 16 bytes of
+ *     room become CT || tag; the send nonce advances by `frames`;
+ *   - open_frames: the opens verify first.  A frame that verifies becomes its
+ *     plaintext in place (its 16 tag bytes are left as they were).  At the
+ *     first frame whose tag fails, error = NOISE_ERROR_MAC_FAILURE (it wins
+ *     over a later stop code), frames and consumed cover the verified prefix
+ *     only, the receive nonce advances by that prefix and stays at the failed
+ *     frame's nonce (nothing is sticky: cipherstate.c:400-405), and the failed
+ *     frame is byte for byte untouched;
+ *   - echo_frames: the open under the receive state, then the seal of the
+ *     verified prefix only under the send state, in place; result and both
+ *     nonces as for the open.
+ * Unlike noise_wire_open, a walked frame AFTER the failed one in the same call
+ * is not read back as given: it holds either its bytes as given or its
+ * plaintext, the latter when its own tag verified under nonce + k — never
+ * anything else and never unauthenticated plaintext.  result.frames says what
+ * is valid.  (Reading them back as given would cost a restoring launch per
+ * call.)
+ *
+ * The cap: the walked frames of a call are numbered across the batch in
+ * session order (session 0's first, then session 1's, ...), in 64 bits.  A
+ * frame whose number is max_frames or more is not processed in this call:
+ * its session reports the frames before it with NOISE_ERROR_NONE (it did not
+ * reach its stop), later sessions report 0 frames, 0 bytes and
+ * NOISE_ERROR_NONE; the caller adds `consumed` to its offsets (and takes it
+ * from its lengths) and calls again.  One session's failure or stop changes
+ * nothing, byte for byte, for any other session.
+ *
+ * Checked on the host before any launch, in this order:
+ *   - _new: a cipher other than NOISE_CIPHER_CHACHAPOLY / _AESGCM gives
+ *     NOISE_ERROR_UNKNOWN_ID; a role that is neither NOISE_ROLE_INITIATOR nor
+ *     _RESPONDER, a NULL tr, d_k1 or d_k2, and, with n > 0, max_frames == 0
+ *     or over 2^31 give NOISE_ERROR_INVALID_PARAM;
+ *   - a call: a NULL tr, d_wire, d_off, d_len or d_result, and
+ *     [d_result, + 16 n) meeting [d_off, + 8 n) or [d_len, + 4 n), give
+ *     NOISE_ERROR_INVALID_PARAM.
+ * n == 0 gives a valid object whose calls launch nothing. */
+typedef struct NoiseAeadDevTransport NoiseAeadDevTransport;
+typedef struct NoiseAeadTransportResult {
+    uint32_t frames;    /* frames of this session processed by the call */
+    uint32_t consumed;  /* bytes they span, headers included */
+    int32_t  error;     /* NOISE_ERROR_NONE / _INVALID_LENGTH / _INVALID_NONCE / _MAC_FAILURE */
+    uint32_t reserved_; /* written as 0 */
+} NoiseAeadTransportResult;
+
+int noise_aead_dev_transport_new(NoiseAeadDevTransport **tr, int cipher_id, int role, uint32_t n,
+                                 const uint8_t *d_k1, const uint8_t *d_k2, uint32_t max_frames, void *stream);
+int noise_aead_dev_transport_free(NoiseAeadDevTransport *tr);
+uint64_t *noise_aead_dev_transport_nonces(const NoiseAeadDevTransport *tr, int direction); /* 0 send, 1 receive */
+int noise_aead_dev_transport_seal_frames(NoiseAeadDevTransport *tr, uint8_t *d_wire, const uint64_t *d_off,
+                                         const uint32_t *d_len, NoiseAeadTransportResult *d_result, void *stream);
+int noise_aead_dev_transport_open_frames(NoiseAeadDevTransport *tr, uint8_t *d_wire, const uint64_t *d_off,
+                                         const uint32_t *d_len, NoiseAeadTransportResult *d_result, void *stream);
+int noise_aead_dev_transport_echo_frames(NoiseAeadDevTransport *tr, uint8_t *d_wire, const uint64_t *d_off,
+                                         const uint32_t *d_len, NoiseAeadTransportResult *d_result, void *stream);
+
 /* ------------------------------------------------ error reports
  * include/noise/protocol/errors.h; src/protocol/errors.c:92-127. */
 void noise_perror(const char *s, int err);

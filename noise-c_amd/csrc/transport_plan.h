@@ -1,0 +1,135 @@
+/*
+ * transport_plan.h — the host-only half of the device-resident transport
+ * sessions (noise_aead_dev_transport_*, include/noise_aead_hip.h section 9):
+ * the frame walk of one session, the cap rule across sessions, and the
+ * argument checks.  One source for both compilers, as fe25519.h is: hipcc's
+ * device pass builds the kernels of transport.hip from tr_walk and tr_cap,
+ * plain g++ builds asan/transport_check.cpp from them, so the CPU check under
+ * ASan/UBSan runs the walk the GPU runs.
+ *
+ * The wire format is that of csrc/wire.c (echo-common.c:643-688): a 2-byte
+ * big-endian length L, then L bytes of CT || tag.
+ */
+#pragma once
+#include "noise_aead_hip.h"
+#include <stdint.h>
+
+#if defined(__HIPCC__)
+#define TR_FN __host__ __device__ __forceinline__
+#define TR_MEMBER __host__ __device__ __forceinline__
+#else
+#define TR_FN static inline __attribute__((always_inline))
+#define TR_MEMBER inline
+#endif
+
+namespace na {
+
+constexpr uint64_t TR_NONCE_LIMIT = ~0ull;     /* cipherstate.c: n == 2^64 - 1 is exhausted */
+constexpr uint32_t TR_MAC_LEN = 16;
+constexpr uint32_t TR_MAX_FRAMES = 1u << 31;   /* the most records one call may describe */
+constexpr uint64_t TR_NO_BUDGET = ~0ull;
+
+struct TrWalk {
+    uint64_t frames;    /* frames taken */
+    uint64_t consumed;  /* bytes they span, headers included */
+    int32_t stop;       /* why the walk ended: NOISE_ERROR_NONE / _INVALID_LENGTH / _INVALID_NONCE */
+};
+
+/* a frame the walk took: emit(k, body, L) with body the offset of its L bytes in the stream */
+struct TrNoEmit {
+    TR_MEMBER void operator()(uint64_t, uint64_t, uint32_t) const {}
+};
+
+/* The walk of one session's stream, in the order of wire.c scan_frames: the
+   frames from the start of p[0..len), frame k under nonce + k.  It ends with
+   NOISE_ERROR_NONE at a partial (or absent) frame, with _INVALID_LENGTH at a
+   complete frame with L < 16, with _INVALID_NONCE where nonce + k is
+   2^64 - 1; the stopping frame is not taken.  A frame that would be taken as
+   number `budget` is left for the next call instead: the walk ends there with
+   NOISE_ERROR_NONE, having taken `budget` frames — so a stop that comes
+   right after the budget's last frame is still reported.  For an echo, nonce
+   is the larger of the two directions' (the first to run out).  Reads only
+   p[0..len). */
+template <class Emit>
+TR_FN TrWalk tr_walk(const uint8_t *p, uint64_t len, uint64_t nonce, uint64_t budget, Emit emit)
+{
+    TrWalk w = {0, 0, NOISE_ERROR_NONE};
+    uint64_t off = 0;
+    while (len - off >= 2) {
+        const uint32_t L = ((uint32_t)p[off] << 8) | p[off + 1];
+        if (len - off - 2 < L) break;
+        /* both the tag of seal and the MAC of open need L >= 16 (cipherstate.c:305-318 / :379-390) */
+        if (L < TR_MAC_LEN) {
+            w.stop = NOISE_ERROR_INVALID_LENGTH;
+            break;
+        }
+        if (nonce + w.frames == TR_NONCE_LIMIT) { /* nonce + frames never wraps: it stops here first */
+            w.stop = NOISE_ERROR_INVALID_NONCE;
+            break;
+        }
+        if (w.frames == budget) break;
+        emit(w.frames, off + 2, L);
+        off += 2 + (uint64_t)L;
+        ++w.frames;
+    }
+    w.consumed = off;
+    return w;
+}
+
+TR_FN TrWalk tr_walk(const uint8_t *p, uint64_t len, uint64_t nonce, uint64_t budget)
+{
+    return tr_walk(p, len, nonce, budget, TrNoEmit());
+}
+
+/* The cap across sessions.  The walked frames of a call are numbered in
+   session order; a session whose uncapped walk takes `count` frames starts at
+   number `base` (the exclusive sum of the counts before it, in 64 bits).  What
+   the session may take in a call over max_frames records: everything when its
+   frames all lie below max_frames (its walk then reports its own stop), else
+   the frames below max_frames (none from base == max_frames on) and the call
+   reports NOISE_ERROR_NONE for it: it did not reach its stop.  A session after
+   the cut takes nothing.  Returns the budget of the session's walk; *cut says
+   the session reports NOISE_ERROR_NONE whatever its walk met. */
+TR_FN uint64_t tr_cap(uint64_t base, uint64_t count, uint64_t max_frames, bool *cut)
+{
+    *cut = count > max_frames || base > max_frames - count; /* base + count > max_frames, without a wrap */
+    if (!*cut) return count;
+    return base < max_frames ? max_frames - base : 0;
+}
+
+/* --------------------------------------------------------- argument checks
+   Pointers are compared as numbers and never dereferenced. */
+
+typedef unsigned __int128 tr_u128;
+
+/* [a, a + a_bytes) meets [b, b + b_bytes) */
+inline bool tr_ranges_meet(const void *a, tr_u128 a_bytes, const void *b, tr_u128 b_bytes)
+{
+    if (!a_bytes || !b_bytes) return false;
+    const tr_u128 x = (uintptr_t)a, y = (uintptr_t)b;
+    return x < y + b_bytes && y < x + a_bytes;
+}
+
+/* noise_aead_dev_transport_new, in the order of the header */
+inline int tr_check_new(const void *out, int cipher_id, int role, uint32_t n, const void *d_k1, const void *d_k2,
+                        uint32_t max_frames)
+{
+    if (cipher_id != NOISE_CIPHER_CHACHAPOLY && cipher_id != NOISE_CIPHER_AESGCM) return NOISE_ERROR_UNKNOWN_ID;
+    if (role != NOISE_ROLE_INITIATOR && role != NOISE_ROLE_RESPONDER) return NOISE_ERROR_INVALID_PARAM;
+    if (!out || !d_k1 || !d_k2) return NOISE_ERROR_INVALID_PARAM;
+    if (n && (max_frames == 0 || max_frames > TR_MAX_FRAMES)) return NOISE_ERROR_INVALID_PARAM;
+    return NOISE_ERROR_NONE;
+}
+
+/* noise_aead_dev_transport_{seal,open,echo}_frames of an object of n sessions */
+inline int tr_check_call(const void *tr, uint32_t n, const void *d_wire, const void *d_off, const void *d_len,
+                         const void *d_result)
+{
+    if (!tr || !d_wire || !d_off || !d_len || !d_result) return NOISE_ERROR_INVALID_PARAM;
+    const tr_u128 rb = (tr_u128)sizeof(NoiseAeadTransportResult) * n;
+    if (tr_ranges_meet(d_result, rb, d_off, (tr_u128)8 * n) || tr_ranges_meet(d_result, rb, d_len, (tr_u128)4 * n))
+        return NOISE_ERROR_INVALID_PARAM;
+    return NOISE_ERROR_NONE;
+}
+
+} // namespace na

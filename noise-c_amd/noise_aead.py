@@ -102,6 +102,11 @@ class NoiseAeadHandshakeConfig(C.Structure):
                 ("d_remote_static_pub", C.c_void_p), ("remote_static_stride", C.c_uint64)]
 
 
+class NoiseAeadTransportResult(C.Structure):
+    _fields_ = [("frames", C.c_uint32), ("consumed", C.c_uint32), ("error", C.c_int32),
+                ("reserved_", C.c_uint32)]
+
+
 FLAG_FAST = 1
 FLAG_CT_GHASH = 2
 FLAG_VERIFY_FIRST = 4  # the default open order since round 6 (accepted, overrides ONE_PASS)
@@ -180,6 +185,12 @@ def lib() -> C.CDLL:
         "noise_aead_dev_handshake_split": (i, [vp, vp, vp, vp, vp]),
         "noise_aead_dev_handshake_status": (vp, [vp]),
         "noise_aead_dev_handshake_remote_static": (vp, [vp]),
+        "noise_aead_dev_transport_new": (i, [P(vp), i, i, C.c_uint32, vp, vp, C.c_uint32, vp]),
+        "noise_aead_dev_transport_free": (i, [vp]),
+        "noise_aead_dev_transport_nonces": (vp, [vp, i]),
+        "noise_aead_dev_transport_seal_frames": (i, [vp, vp, vp, vp, vp, vp]),
+        "noise_aead_dev_transport_open_frames": (i, [vp, vp, vp, vp, vp, vp]),
+        "noise_aead_dev_transport_echo_frames": (i, [vp, vp, vp, vp, vp, vp]),
         "noise_strerror": (i, [i, C.c_char_p, sz]),
         "noise_perror": (None, [C.c_char_p, i]),
         "noise_aead_debug_batch_stats": (None, [P(C.c_uint64), P(C.c_uint64)]),
@@ -543,6 +554,43 @@ def dev_handshake_status(hs: int) -> int:
 def dev_handshake_remote_static(hs: int) -> int:
     """device pointer of the n x 32 remote static public keys"""
     return lib().noise_aead_dev_handshake_remote_static(hs) or 0
+
+
+# ---- device-resident transport sessions (include/noise_aead_hip.h section 9);
+# `tr` is the NoiseAeadDevTransport* as an integer, every data argument a device
+# pointer; a result is n NoiseAeadTransportResult (frames, consumed, error, 0)
+
+def dev_transport_new(cipher: int, role: int, n: int, *, k1: int, k2: int, max_frames: int, stream: int = 0):
+    """noise_aead_dev_transport_new: (rc, tr); tr is None unless rc == 0."""
+    tr = C.c_void_p()
+    rc = lib().noise_aead_dev_transport_new(C.byref(tr), cipher, role, n, k1 or None, k2 or None, max_frames,
+                                            stream or None)
+    return rc, tr.value
+
+
+def dev_transport_free(tr: int) -> int:
+    return lib().noise_aead_dev_transport_free(tr)
+
+
+def dev_transport_nonces(tr: int, direction: int) -> int:
+    """device pointer of the n 64-bit nonces of one direction (0 send, 1 receive)"""
+    return lib().noise_aead_dev_transport_nonces(tr, direction) or 0
+
+
+def _transport_call(fn, tr, wire, off, length, result, stream):
+    return fn(tr, wire or None, off or None, length or None, result or None, stream or None)
+
+
+def dev_transport_seal_frames(tr: int, *, wire: int, off: int, length: int, result: int, stream: int = 0) -> int:
+    return _transport_call(lib().noise_aead_dev_transport_seal_frames, tr, wire, off, length, result, stream)
+
+
+def dev_transport_open_frames(tr: int, *, wire: int, off: int, length: int, result: int, stream: int = 0) -> int:
+    return _transport_call(lib().noise_aead_dev_transport_open_frames, tr, wire, off, length, result, stream)
+
+
+def dev_transport_echo_frames(tr: int, *, wire: int, off: int, length: int, result: int, stream: int = 0) -> int:
+    return _transport_call(lib().noise_aead_dev_transport_echo_frames, tr, wire, off, length, result, stream)
 
 
 def dev_fill_splitmix(d_out: int, nbytes: int, seed: int, word0: int = 0, stream: int = 0) -> int:
