@@ -695,6 +695,97 @@ int noise_aead_dev_transport_open_frames(NoiseAeadDevTransport *tr, uint8_t *d_w
 int noise_aead_dev_transport_echo_frames(NoiseAeadDevTransport *tr, uint8_t *d_wire, const uint64_t *d_off,
                                          const uint32_t *d_len, NoiseAeadTransportResult *d_result, void *stream);
 
+/* ------------------------------------------------ 10. the session table
+ *
+ * One long-lived transport object (section 9) as a server's table of
+ * sessions: its n slots are keyed from finished handshake batches and
+ * un-keyed when a connection closes, on the device and in stream order, and a
+ * call may address only the slots that have traffic.  Nothing of section 9
+ * changes: an object from noise_aead_dev_transport_new behaves byte for byte
+ * as described there.
+ *
+ * Slots and their state.  Each of an object's n slots is keyed or unkeyed,
+ * the batch form of noise_cipherstate_has_key: one byte per slot (1 / 0) in a
+ * device array the object owns, which _has_key returns (NULL for n == 0 and
+ * for a NULL tr).  An object from noise_aead_dev_transport_new starts with
+ * every slot keyed; _new_unkeyed makes one with every slot unkeyed, every
+ * context byte 0 and every nonce 0.  In any frame call (section 9's or the
+ * _of ones) an unkeyed slot gives result = {0, 0, NOISE_ERROR_INVALID_STATE,
+ * 0}, what noise_wire_seal / _open / _echo return for an unkeyed state
+ * (wire.c:199), checked before anything else as there: none of the slot's
+ * stream is read or written, it takes no frame numbers (its count is 0, so it
+ * never moves another session's place under the cap), and it reports
+ * NOISE_ERROR_INVALID_STATE on either side of a cut too.
+ *
+ * _set_keys is the batch form of noise_cipherstate_init_key on both states of
+ * a slot.  Entry j (j < m) addresses slot d_slots[j]; its keys are the 32
+ * bytes at d_k1 + 32 j and d_k2 + 32 j, the packing
+ * noise_aead_dev_handshake_split and noise_aead_dev_split write; the role
+ * picks send and receive as for _new.  It builds both key contexts of the
+ * slot, sets both nonces to 0 (init_key resets n, cipherstate.c:231-233, so a
+ * keyed slot is simply re-keyed) and marks the slot keyed.  With d_status
+ * given (noise_aead_dev_handshake_status(hs) as it lies; it may be NULL), an
+ * entry whose d_status[j] != 0 is cleared instead, as by _clear_keys: a
+ * failed handshake never becomes a session and nobody reads a status on the
+ * host.  The keys are consumed once `stream` has passed the call.
+ *
+ * _clear_keys zeroes every byte of both contexts of each named slot, zeroes
+ * both nonces and marks the slot unkeyed.
+ *
+ * Both: a slot number >= n is ignored, nothing is read or written for it.
+ * The slot numbers of one call must be distinct; they live in device memory,
+ * so that is the caller's guarantee, unchecked like the ragged calls' ranges.
+ * Both are asynchronous on `stream`, allocate nothing, copy nothing to the
+ * host and never synchronise.  Slots not named are unchanged byte for byte:
+ * contexts, nonces and state.
+ *
+ * _seal_frames_of / _open_frames_of / _echo_frames_of are the three frame
+ * calls over a list of slots.  Entry j (j < m) is slot d_slots[j] with its
+ * stream the d_len[j] bytes at d_wire + d_off[j], and its result goes to
+ * d_result[j]: the per-call arrays are m long, not n long.  Frames are
+ * numbered across the call in list order.  max_frames is this call's cap: 0
+ * means the object's own, and a value above the object's is refused.  The
+ * AEAD launches cover only that many records, so a small tick on a large
+ * table does not pay for the table's max_frames.  For each keyed in-range
+ * entry the outcome (bytes, result, both nonces) is that of the call of
+ * section 9 on a batch made of exactly the listed sessions in list order.  An
+ * out-of-range entry (d_slots[j] >= n) gives {0, 0, NOISE_ERROR_INVALID_PARAM,
+ * 0} and takes no frame numbers; an unkeyed entry behaves as described above.
+ * The listed slots must be distinct: the caller's guarantee.  The three calls
+ * of section 9 are the list 0 .. n-1 with max_frames == 0.
+ *
+ * Checked on the host before any launch, in this order:
+ *   - _new_unkeyed: as _new, without the key pointers;
+ *   - _set_keys, _clear_keys and the _of calls:
+ *       1. a NULL tr gives NOISE_ERROR_INVALID_PARAM;
+ *       2. m == 0 gives NOISE_ERROR_NONE, and nothing is launched;
+ *       3. m > n gives NOISE_ERROR_INVALID_PARAM;
+ *       4. a NULL d_slots, and a NULL d_k1 or d_k2 (_set_keys), d_wire, d_off,
+ *          d_len or d_result (_of), give NOISE_ERROR_INVALID_PARAM;
+ *       5. _of only: a max_frames above the object's gives
+ *          NOISE_ERROR_INVALID_PARAM;
+ *       6. _of only: [d_result, + 16 m) meeting [d_off, + 8 m), [d_len, + 4 m)
+ *          or [d_slots, + 4 m) gives NOISE_ERROR_INVALID_PARAM.
+ *     An _of call whose scan of m items would need more scratch than _new
+ *     carved for n gives NOISE_ERROR_SYSTEM (nothing is launched). */
+int noise_aead_dev_transport_new_unkeyed(NoiseAeadDevTransport **tr, int cipher_id, int role,
+                                         uint32_t n, uint32_t max_frames, void *stream);
+int noise_aead_dev_transport_set_keys(NoiseAeadDevTransport *tr, const uint32_t *d_slots, uint32_t m,
+                                      const uint8_t *d_k1, const uint8_t *d_k2,
+                                      const uint8_t *d_status /* may be NULL */, void *stream);
+int noise_aead_dev_transport_clear_keys(NoiseAeadDevTransport *tr, const uint32_t *d_slots, uint32_t m,
+                                        void *stream);
+const uint8_t *noise_aead_dev_transport_has_key(const NoiseAeadDevTransport *tr); /* n bytes, 1 / 0; NULL for n == 0 */
+int noise_aead_dev_transport_seal_frames_of(NoiseAeadDevTransport *tr, const uint32_t *d_slots, uint32_t m,
+                                            uint32_t max_frames, uint8_t *d_wire, const uint64_t *d_off,
+                                            const uint32_t *d_len, NoiseAeadTransportResult *d_result, void *stream);
+int noise_aead_dev_transport_open_frames_of(NoiseAeadDevTransport *tr, const uint32_t *d_slots, uint32_t m,
+                                            uint32_t max_frames, uint8_t *d_wire, const uint64_t *d_off,
+                                            const uint32_t *d_len, NoiseAeadTransportResult *d_result, void *stream);
+int noise_aead_dev_transport_echo_frames_of(NoiseAeadDevTransport *tr, const uint32_t *d_slots, uint32_t m,
+                                            uint32_t max_frames, uint8_t *d_wire, const uint64_t *d_off,
+                                            const uint32_t *d_len, NoiseAeadTransportResult *d_result, void *stream);
+
 /* ------------------------------------------------ error reports
  * include/noise/protocol/errors.h; src/protocol/errors.c:92-127. */
 void noise_perror(const char *s, int err);
@@ -770,6 +861,12 @@ int noise_aead_debug_last_plan(char *buf, size_t n);
 #define NOISE_AEAD_F25_INVERT     7
 int noise_aead_debug_f25_op(int op, const uint8_t *d_a, const uint8_t *d_b, uint32_t n,
                             uint8_t *d_out, void *stream);
+/* noise_aead_debug_transport_ctx: a transport object's device array of n key
+ *   contexts of one direction (0 send, 1 receive) and, in *ctx_bytes, the
+ *   bytes per context (noise_aead_dev_ctx_bytes of its cipher), so that a test
+ *   can read back what _set_keys built and _clear_keys zeroed (section 10).
+ *   NULL for any other direction, a NULL tr or n == 0. */
+const uint8_t *noise_aead_debug_transport_ctx(const NoiseAeadDevTransport *tr, int direction, size_t *ctx_bytes);
 
 /* Default lanes per record the library picks for a standalone uniform seal
  * or open of n records (noise_aead_dev_{seal,open}_uniform, lanes 0) in a

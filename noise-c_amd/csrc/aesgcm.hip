@@ -304,21 +304,18 @@ NA_DEV void gf_mul_bytes(const uint8_t x[16], const uint8_t h[16], uint8_t out[1
 }
 
 #ifndef NA_NO_SETUP_KERNELS
-/* One workgroup per state: round keys, H, and the H^1..H^4 tables. */
-__global__ __launch_bounds__(256) void gcm_prepare(const uint8_t *__restrict__ raw_keys,
-                                                   AesCtx *__restrict__ ctx, uint32_t n_states)
+/* One workgroup of 256 threads builds one state from the 32 key bytes at k:
+   round keys, H, and the H^1..H^4 tables. */
+__device__ __forceinline__ void gcm_prepare_one(const uint8_t *__restrict__ k, AesCtx *__restrict__ c)
 {
     __shared__ uint32_t te[256], sb[256], rk[60];
     __shared__ uint8_t hp[GCM_LANES + 1][16];       /* H^1..H^4, H^8, bytes */
     __shared__ uint8_t V[GCM_LANES + 1][128][16];   /* x^i * H^m */
-    const uint32_t st = blockIdx.x;
-    if (st >= n_states) return;
     const int t = threadIdx.x;
     te[t] = g_te0[t];
     sb[t] = g_sbox[t];
     __syncthreads();
     if (t == 0) {
-        const uint8_t *k = raw_keys + (size_t)st * 32;
         for (int i = 0; i < 8; ++i)
             rk[i] = ((uint32_t)k[4 * i] << 24) | ((uint32_t)k[4 * i + 1] << 16) |
                     ((uint32_t)k[4 * i + 2] << 8) | k[4 * i + 3];
@@ -354,7 +351,6 @@ __global__ __launch_bounds__(256) void gcm_prepare(const uint8_t *__restrict__ r
         }
     }
     __syncthreads();
-    AesCtx *c = ctx + st;
     if (t < 60) c->rk[t] = rk[t];
     if (t < 4) {
         uint32_t w = 0;
@@ -379,6 +375,34 @@ __global__ __launch_bounds__(256) void gcm_prepare(const uint8_t *__restrict__ r
             dst[w] = (uint32_t)acc[4 * w] | ((uint32_t)acc[4 * w + 1] << 8) |
                      ((uint32_t)acc[4 * w + 2] << 16) | ((uint32_t)acc[4 * w + 3] << 24);
     }
+}
+
+/* One workgroup per state. */
+__global__ __launch_bounds__(256) void gcm_prepare(const uint8_t *__restrict__ raw_keys,
+                                                   AesCtx *__restrict__ ctx, uint32_t n_states)
+{
+    const uint32_t st = blockIdx.x;
+    if (st >= n_states) return;
+    gcm_prepare_one(raw_keys + (size_t)st * 32, ctx + st);
+}
+
+/* The states of a transport object's slots (transport.hip, _set_keys): one
+   workgroup per (entry, direction), 2m in all.  ctx holds the object's n send
+   contexts, then its n receive contexts; entry j's keys are the 32 bytes at
+   k1 + 32 j and k2 + 32 j, and the initiator sends under k1.  An entry whose
+   slot is out of range, or whose status byte is not 0, is left alone: the
+   clear path zeroes the contexts of a failed one. */
+__global__ __launch_bounds__(256) void gcm_prepare_slots(const uint32_t *__restrict__ slots, uint32_t m, uint32_t n,
+                                                         const uint8_t *__restrict__ k1, const uint8_t *__restrict__ k2,
+                                                         const uint8_t *__restrict__ status, uint32_t initiator,
+                                                         AesCtx *__restrict__ ctx)
+{
+    const uint32_t j = blockIdx.x >> 1, receive = blockIdx.x & 1;
+    if (j >= m) return;
+    uint32_t i;
+    if (!tr_slot(slots, j, n, &i) || (status && status[j])) return;
+    const uint8_t *keys = (receive != 0) == (initiator != 0) ? k2 : k1;
+    gcm_prepare_one(keys + (size_t)j * 32, ctx + ((size_t)receive * n + i));
 }
 #endif
 

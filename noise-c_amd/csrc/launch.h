@@ -55,5 +55,11 @@ NA_HIDDEN int aes_launch(const Plan &p, const PlanArgs &args, hipStream_t s);
 /* S-box / T-table of the current device, built once (private stream) */
 NA_HIDDEN hipError_t ensure_aes_tables();
 NA_HIDDEN int aes_prepare(const uint8_t *raw_keys, uint32_t n_states, void *ctx, hipStream_t s);
+/* the contexts of a transport object's slots (transport.hip): entry j < m is
+   slot slots[j] of n, keyed from k1 + 32 j and k2 + 32 j by role; ctx: n send
+   contexts, then n receive ones.  Entries out of range or with a non-zero
+   status byte (status may be null) are left alone.  Builds the tables first. */
+NA_HIDDEN int aes_prepare_slots(const uint32_t *slots, uint32_t m, uint32_t n, const uint8_t *k1, const uint8_t *k2,
+                                const uint8_t *status, bool initiator, void *ctx, hipStream_t s);
 
 } // namespace na

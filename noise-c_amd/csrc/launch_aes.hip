@@ -13,6 +13,7 @@
  * compile no other order.
  */
 #include "launch.h"
+#include "transport_plan.h"
 #include "aesgcm.hip"
 #include <mutex>
 
@@ -114,6 +115,18 @@ AnyKernel aes_kernel(const Plan &p)
 int aes_prepare(const uint8_t *raw_keys, uint32_t n_states, void *ctx, hipStream_t s)
 {
     hipLaunchKernelGGL(gcm_prepare, dim3(n_states), dim3(256), 0, s, raw_keys, (AesCtx *)ctx, n_states);
+    return hip_rc(hipGetLastError());
+}
+
+int aes_prepare_slots(const uint32_t *slots, uint32_t m, uint32_t n, const uint8_t *k1, const uint8_t *k2,
+                      const uint8_t *status, bool initiator, void *ctx, hipStream_t s)
+{
+    if (!m) return NOISE_ERROR_NONE;
+    if (m > 0x7fffffffu / 2) return NOISE_ERROR_INVALID_PARAM; /* 2m workgroups in one grid */
+    const int rc = hip_rc(ensure_aes_tables());
+    if (rc) return rc;
+    hipLaunchKernelGGL(gcm_prepare_slots, dim3(2 * m), dim3(256), 0, s, slots, m, n, k1, k2, status,
+                       initiator ? 1u : 0u, (AesCtx *)ctx);
     return hip_rc(hipGetLastError());
 }
 

@@ -1,6 +1,6 @@
 /*
  * transport.hip — device-resident transport sessions:
- * noise_aead_dev_transport_* (include/noise_aead_hip.h section 9).
+ * noise_aead_dev_transport_* (include/noise_aead_hip.h sections 9 and 10).
  *
  * The object holds, for n sessions, a send and a receive key context and a
  * send and a receive nonce on the device, and what a call needs: descriptors
@@ -25,6 +25,24 @@
  *              whose status is not 0, advances the nonce(s) by that prefix
  *              and writes the result; for an echo it also writes the seal
  *              descriptors: the prefix under the send state, the rest refused.
+ *
+ * The session table (section 10): every slot has a state byte (keyed or not),
+ * and a call may name the m slots it is about in a device list.  Entry j of
+ * such a call is slot tr_slot(slots, j) (transport_plan.h): the caller's
+ * arrays and the per-call scratch are indexed by j, nonces, contexts and
+ * state by the slot; an entry out of range or unkeyed counts no frames and
+ * gets its fixed result from tr_build.  The calls of section 9 are the list
+ * NULL (entry j is slot j), m == n and the object's own cap.  The AEAD
+ * launches cover the call's cap, not the object's.
+ *   tr_set_keys  ChaChaPoly, one lane per entry: both contexts (the context is
+ *                the key), both nonces, the state; an entry whose status byte
+ *                is not 0 is cleared instead.  AES-GCM builds its contexts
+ *                with gcm_prepare_slots (aesgcm.hip), then tr_clear_wide marks
+ *                the entries and zeroes the failed ones;
+ *   tr_clear_lane / tr_clear_wide  _clear_keys: zero both contexts with 16-byte
+ *                stores, both nonces and the state; a lane per entry for the
+ *                32-byte ChaChaPoly contexts, a workgroup per (entry,
+ *                direction) for the 41 344-byte AES-GCM ones.
  */
 #include "launch.h"
 
@@ -40,6 +58,7 @@ namespace {
 #define TR_DEV __device__ __forceinline__
 
 constexpr uint32_t TR_BLOCK = 64;
+constexpr uint32_t TR_WIDE_BLOCK = 256;
 constexpr uint32_t TR_REFUSED_LEN = MAX_RECORD_LEN + 1; /* aead_kernels.h reject_len */
 
 enum TrMode : uint32_t { TR_SEAL = 0, TR_OPEN = 1, TR_ECHO = 2 };
@@ -55,9 +74,18 @@ struct TrArgs {
     int32_t *stop;
     RecDesc *recs, *seal_recs;   /* max_frames each; seal_recs: the echo's second job */
     const uint8_t *status;
-    uint64_t ctx_bytes, max_frames;
+    uint64_t ctx_bytes, max_frames; /* max_frames: this call's cap */
     uint32_t n, mode;
+    const uint32_t *slots;       /* the call's list (null: entry j is slot j) of m entries */
+    const uint8_t *keyed;        /* per slot: 1 keyed, 0 not */
+    uint32_t m;
 };
+
+/* entry j's slot; false (nothing of a slot may be touched) when it is out of range or unkeyed */
+TR_DEV bool tr_live(const TrArgs &a, uint32_t j, uint32_t *i)
+{
+    return tr_slot(a.slots, j, a.n, i) && a.keyed[*i];
+}
 
 TR_DEV uint64_t tr_start_nonce(const TrArgs &a, uint32_t i)
 {
@@ -75,9 +103,10 @@ TR_DEV RecDesc tr_refused()
 
 __global__ __launch_bounds__(TR_BLOCK) void tr_count(TrArgs a)
 {
-    const uint32_t i = blockIdx.x * TR_BLOCK + threadIdx.x;
-    if (i >= a.n) return;
-    a.count[i] = tr_walk(a.wire + a.off[i], a.len[i], tr_start_nonce(a, i), TR_NO_BUDGET).frames;
+    const uint32_t j = blockIdx.x * TR_BLOCK + threadIdx.x;
+    if (j >= a.m) return;
+    uint32_t i;
+    a.count[j] = tr_live(a, j, &i) ? tr_walk(a.wire + a.off[j], a.len[j], tr_start_nonce(a, i), TR_NO_BUDGET).frames : 0;
 }
 
 struct TrEmit {
@@ -99,29 +128,35 @@ struct TrEmit {
 __global__ __launch_bounds__(TR_BLOCK) void tr_build(TrArgs a)
 {
     const uint64_t t = (uint64_t)blockIdx.x * TR_BLOCK + threadIdx.x;
-    const uint64_t all = a.base[a.n - 1] + a.count[a.n - 1];
+    const uint64_t all = a.base[a.m - 1] + a.count[a.m - 1];
     const uint64_t total = all < a.max_frames ? all : a.max_frames;
     if (t >= total && t < a.max_frames) a.recs[t] = tr_refused();
-    if (t >= a.n) return;
-    const uint32_t i = (uint32_t)t;
+    if (t >= a.m) return;
+    const uint32_t j = (uint32_t)t;
+    uint32_t i;
+    if (!tr_live(a, j, &i)) { /* before anything else, cut or not (wire.c:199); tr_commit leaves the entry alone */
+        const NoiseAeadTransportResult r = {0, 0, i < a.n ? NOISE_ERROR_INVALID_STATE : NOISE_ERROR_INVALID_PARAM, 0};
+        a.result[j] = r;
+        return;
+    }
     bool cut;
-    const uint64_t base = a.base[i], budget = tr_cap(base, a.count[i], a.max_frames, &cut);
+    const uint64_t base = a.base[j], budget = tr_cap(base, a.count[j], a.max_frames, &cut);
     /* the session's context: send contexts first, then the receive ones */
     const bool seal = a.mode == TR_SEAL;
-    const TrEmit emit = {a.recs + base, a.off[i], seal ? a.send[i] : a.recv[i],
+    const TrEmit emit = {a.recs + base, a.off[j], seal ? a.send[i] : a.recv[i],
                          (seal ? (uint64_t)i : (uint64_t)a.n + i) * a.ctx_bytes};
     TrWalk w = {0, 0, NOISE_ERROR_NONE};
-    if (budget || !cut) w = tr_walk(a.wire + a.off[i], a.len[i], tr_start_nonce(a, i), budget, emit);
+    if (budget || !cut) w = tr_walk(a.wire + a.off[j], a.len[j], tr_start_nonce(a, i), budget, emit);
     if (cut) w.stop = NOISE_ERROR_NONE;
     if (seal) {
         a.send[i] += w.frames;
         const NoiseAeadTransportResult r = {(uint32_t)w.frames, (uint32_t)w.consumed, w.stop, 0};
-        a.result[i] = r;
+        a.result[j] = r;
         return;
     }
-    a.frames[i] = (uint32_t)w.frames;
-    a.consumed[i] = (uint32_t)w.consumed;
-    a.stop[i] = w.stop;
+    a.frames[j] = (uint32_t)w.frames;
+    a.consumed[j] = (uint32_t)w.consumed;
+    a.stop[j] = w.stop;
 }
 
 __global__ __launch_bounds__(TR_BLOCK) void tr_commit(TrArgs a)
@@ -129,19 +164,21 @@ __global__ __launch_bounds__(TR_BLOCK) void tr_commit(TrArgs a)
     const uint64_t t = (uint64_t)blockIdx.x * TR_BLOCK + threadIdx.x;
     const bool echo = a.mode == TR_ECHO;
     if (echo) {
-        const uint64_t all = a.base[a.n - 1] + a.count[a.n - 1];
+        const uint64_t all = a.base[a.m - 1] + a.count[a.m - 1];
         const uint64_t total = all < a.max_frames ? all : a.max_frames;
         if (t >= total && t < a.max_frames) a.seal_recs[t] = tr_refused();
     }
-    if (t >= a.n) return;
-    const uint32_t i = (uint32_t)t;
-    const uint32_t frames = a.frames[i];
-    const uint64_t base = a.base[i]; /* base + frames <= max_frames (tr_cap); not read when frames == 0 */
+    if (t >= a.m) return;
+    const uint32_t j = (uint32_t)t;
+    uint32_t i;
+    if (!tr_live(a, j, &i)) return; /* tr_build wrote its result; it has no frames */
+    const uint32_t frames = a.frames[j];
+    const uint64_t base = a.base[j]; /* base + frames <= max_frames (tr_cap); not read when frames == 0 */
     uint32_t prefix = 0;
     while (prefix < frames && a.status[base + prefix] == 0) ++prefix;
-    NoiseAeadTransportResult r = {prefix, a.consumed[i], a.stop[i], 0};
+    NoiseAeadTransportResult r = {prefix, a.consumed[j], a.stop[j], 0};
     if (prefix < frames) { /* the first tag that failed wins over a later stop (wire.c wire_run) */
-        r.consumed = (uint32_t)(a.recs[base + prefix].in_off - 2 - a.off[i]);
+        r.consumed = (uint32_t)(a.recs[base + prefix].in_off - 2 - a.off[j]);
         r.error = NOISE_ERROR_MAC_FAILURE;
     }
     if (echo) {
@@ -158,7 +195,85 @@ __global__ __launch_bounds__(TR_BLOCK) void tr_commit(TrArgs a)
         a.send[i] = send + prefix;
     }
     a.recv[i] += prefix; /* it stays at the failed frame's nonce (cipherstate.c:400-405) */
-    a.result[i] = r;
+    a.result[j] = r;
+}
+
+/* ---- keying and un-keying slots (section 10) */
+
+struct TrKeyArgs {
+    const uint32_t *slots;
+    const uint8_t *k1, *k2;      /* tr_set_keys: entry j's keys at + 32 j */
+    const uint8_t *status;       /* may be null; set: an entry whose byte is not 0 is cleared instead */
+    uint8_t *ctx;                /* n send contexts, then n receive contexts */
+    uint64_t *send, *recv;
+    uint8_t *keyed;
+    uint64_t ctx_bytes;          /* a multiple of 16; the contexts are 16-byte aligned */
+    uint32_t m, n;
+    uint32_t set;                /* tr_clear_wide: 1 after gcm_prepare_slots (zero the failed, mark the rest keyed) */
+    uint32_t initiator;
+};
+
+TR_DEV uint4 tr_load_key16(const uint8_t *p)
+{
+    uint32_t w[4];
+    for (int q = 0; q < 4; ++q)
+        w[q] = (uint32_t)p[4 * q] | ((uint32_t)p[4 * q + 1] << 8) | ((uint32_t)p[4 * q + 2] << 16) | ((uint32_t)p[4 * q + 3] << 24);
+    return make_uint4(w[0], w[1], w[2], w[3]);
+}
+
+/* both nonces and the state of slot i */
+TR_DEV void tr_mark(const TrKeyArgs &a, uint32_t i, bool keyed)
+{
+    a.send[i] = 0;
+    a.recv[i] = 0;
+    a.keyed[i] = keyed ? 1 : 0;
+}
+
+/* ChaChaPoly: the context is the key.  One lane per entry. */
+__global__ __launch_bounds__(TR_BLOCK) void tr_set_keys(TrKeyArgs a)
+{
+    const uint32_t j = blockIdx.x * TR_BLOCK + threadIdx.x;
+    if (j >= a.m) return;
+    uint32_t i;
+    if (!tr_slot(a.slots, j, a.n, &i)) return;
+    const bool failed = a.status && a.status[j];
+    /* the initiator sends under k1 and receives under k2, the responder the other way round */
+    const uint8_t *ks = (a.initiator ? a.k1 : a.k2) + (uint64_t)j * 32, *kr = (a.initiator ? a.k2 : a.k1) + (uint64_t)j * 32;
+    uint4 *cs = (uint4 *)(a.ctx + (uint64_t)i * 32), *cr = (uint4 *)(a.ctx + ((uint64_t)a.n + i) * 32);
+    const uint4 zero = make_uint4(0, 0, 0, 0);
+    for (int h = 0; h < 2; ++h) {
+        cs[h] = failed ? zero : tr_load_key16(ks + 16 * h);
+        cr[h] = failed ? zero : tr_load_key16(kr + 16 * h);
+    }
+    tr_mark(a, i, !failed);
+}
+
+/* contexts of at most a few 16-byte words: one lane per entry zeroes both */
+__global__ __launch_bounds__(TR_BLOCK) void tr_clear_lane(TrKeyArgs a)
+{
+    const uint32_t j = blockIdx.x * TR_BLOCK + threadIdx.x;
+    if (j >= a.m) return;
+    uint32_t i;
+    if (!tr_slot(a.slots, j, a.n, &i)) return;
+    const uint64_t words = a.ctx_bytes / 16;
+    uint4 *cs = (uint4 *)(a.ctx + (uint64_t)i * a.ctx_bytes), *cr = (uint4 *)(a.ctx + ((uint64_t)a.n + i) * a.ctx_bytes);
+    for (uint64_t w = 0; w < words; ++w) cs[w] = cr[w] = make_uint4(0, 0, 0, 0);
+    tr_mark(a, i, false);
+}
+
+/* large contexts: one workgroup per (entry, direction), 2m in all.  With
+   a.set, an entry that gcm_prepare_slots keyed is only marked. */
+__global__ __launch_bounds__(TR_WIDE_BLOCK) void tr_clear_wide(TrKeyArgs a)
+{
+    const uint32_t j = blockIdx.x >> 1, receive = blockIdx.x & 1;
+    if (j >= a.m) return;
+    uint32_t i;
+    if (!tr_slot(a.slots, j, a.n, &i)) return;
+    const bool keep = a.set && !(a.status && a.status[j]);
+    if (!receive && threadIdx.x == 0) tr_mark(a, i, keep);
+    if (keep) return;
+    uint4 *c = (uint4 *)(a.ctx + ((uint64_t)receive * a.n + i) * a.ctx_bytes);
+    for (uint64_t w = threadIdx.x, words = a.ctx_bytes / 16; w < words; w += TR_WIDE_BLOCK) c[w] = make_uint4(0, 0, 0, 0);
 }
 
 size_t carve(size_t &off, size_t bytes)
@@ -183,6 +298,7 @@ struct NoiseAeadDevTransport {
     int32_t *stop;
     RecDesc *recs, *seal_recs;
     uint8_t *status;
+    uint8_t *keyed;           /* per slot: 1 keyed, 0 not */
     void *scan_tmp;
     size_t scan_bytes;
 };
@@ -191,25 +307,32 @@ namespace {
 
 typedef NoiseAeadDevTransport Tr;
 
-int scan_counts(const Tr *tr, void *tmp, size_t &bytes, hipStream_t s)
+/* the exclusive scan of the first m counts; tmp == nullptr asks for the size only */
+int scan_counts(const Tr *tr, void *tmp, size_t &bytes, uint32_t m, hipStream_t s)
 {
-    return hip_rc(rocprim::exclusive_scan(tmp, bytes, (const uint64_t *)tr->count, tr->base, (uint64_t)0, (size_t)tr->n,
+    return hip_rc(rocprim::exclusive_scan(tmp, bytes, (const uint64_t *)tr->count, tr->base, (uint64_t)0, (size_t)m,
                                           rocprim::plus<uint64_t>(), s));
 }
 
-int run(Tr *tr, TrMode mode, uint8_t *d_wire, const uint64_t *d_off, const uint32_t *d_len,
-        NoiseAeadTransportResult *d_result, hipStream_t s)
+/* One call over the m entries of `slots` (null: the n slots in order) under
+   the cap `cap`; the arguments are checked. */
+int run(Tr *tr, TrMode mode, const uint32_t *slots, uint32_t m, uint32_t cap, uint8_t *d_wire, const uint64_t *d_off,
+        const uint32_t *d_len, NoiseAeadTransportResult *d_result, hipStream_t s)
 {
-    const int rc0 = tr_check_call(tr, tr ? tr->n : 0, d_wire, d_off, d_len, d_result);
-    if (rc0 || !tr->n) return rc0;
+    size_t bytes = tr->scan_bytes;
+    if (m != tr->n) { /* _new carved the scan's scratch for n items */
+        size_t need = 0;
+        const int rc1 = scan_counts(tr, nullptr, need, m, s);
+        if (rc1) return rc1;
+        if (need > tr->scan_bytes) return NOISE_ERROR_SYSTEM;
+    }
     const TrArgs a = {d_wire, d_off, d_len, d_result, tr->send, tr->recv, tr->count, tr->base, tr->frames, tr->consumed,
-                      tr->stop, tr->recs, tr->seal_recs, tr->status, tr->ctx_bytes, tr->max_frames, tr->n, mode};
-    const uint32_t most = tr->n > tr->max_frames ? tr->n : tr->max_frames;
-    const dim3 per_session((tr->n + TR_BLOCK - 1) / TR_BLOCK), padded((uint32_t)(((uint64_t)most + TR_BLOCK - 1) / TR_BLOCK));
+                      tr->stop, tr->recs, tr->seal_recs, tr->status, tr->ctx_bytes, cap, tr->n, mode, slots, tr->keyed, m};
+    const uint32_t most = m > cap ? m : cap;
+    const dim3 per_session((m + TR_BLOCK - 1) / TR_BLOCK), padded((uint32_t)(((uint64_t)most + TR_BLOCK - 1) / TR_BLOCK));
     hipLaunchKernelGGL(tr_count, per_session, dim3(TR_BLOCK), 0, s, a);
     int rc = hip_rc(hipGetLastError());
-    size_t bytes = tr->scan_bytes;
-    if (!rc) rc = scan_counts(tr, tr->scan_tmp, bytes, s);
+    if (!rc) rc = scan_counts(tr, tr->scan_tmp, bytes, m, s);
     if (rc) return rc;
     hipLaunchKernelGGL(tr_build, padded, dim3(TR_BLOCK), 0, s, a);
     rc = hip_rc(hipGetLastError());
@@ -220,7 +343,7 @@ int run(Tr *tr, TrMode mode, uint8_t *d_wire, const uint64_t *d_off, const uint3
     job.in = job.out = d_wire;
     job.ad = d_wire; /* never read: every ad_len is 0 */
     job.status = tr->status;
-    job.n_records = tr->max_frames;
+    job.n_records = cap;
     if (mode == TR_SEAL) return noise_aead_dev_seal_ragged(tr->cipher_id, &job, s);
     rc = noise_aead_dev_open_ragged(tr->cipher_id, &job, s);
     if (rc) return rc;
@@ -230,6 +353,99 @@ int run(Tr *tr, TrMode mode, uint8_t *d_wire, const uint64_t *d_off, const uint3
     job.recs = (const NoiseAeadRecord *)tr->seal_recs;
     job.status = nullptr;
     return noise_aead_dev_seal_ragged(tr->cipher_id, &job, s);
+}
+
+/* the calls of section 9: every slot in order, the object's own cap */
+int run_all(Tr *tr, TrMode mode, uint8_t *d_wire, const uint64_t *d_off, const uint32_t *d_len,
+            NoiseAeadTransportResult *d_result, void *stream)
+{
+    const int rc = tr_check_call(tr, tr ? tr->n : 0, d_wire, d_off, d_len, d_result);
+    if (rc || !tr->n) return rc;
+    return run(tr, mode, nullptr, tr->n, tr->max_frames, d_wire, d_off, d_len, d_result, (hipStream_t)stream);
+}
+
+/* the calls of section 10: the listed slots, the call's cap */
+int run_of(Tr *tr, TrMode mode, const uint32_t *d_slots, uint32_t m, uint32_t max_frames, uint8_t *d_wire,
+           const uint64_t *d_off, const uint32_t *d_len, NoiseAeadTransportResult *d_result, void *stream)
+{
+    const int rc = tr_check_call_of(tr, tr ? tr->n : 0, tr ? tr->max_frames : 0, d_slots, m, max_frames, d_wire, d_off,
+                                    d_len, d_result);
+    if (rc || !m) return rc;
+    return run(tr, mode, d_slots, m, max_frames ? max_frames : tr->max_frames, d_wire, d_off, d_len, d_result,
+               (hipStream_t)stream);
+}
+
+/* The object and its one device allocation, zeroed on s: every slot unkeyed,
+   every nonce 0.  The arguments are checked. */
+int make(Tr **out, int cipher_id, int role, uint32_t n, uint32_t max_frames, hipStream_t s)
+{
+    *out = nullptr;
+    Tr *tr = new (std::nothrow) Tr();
+    if (!tr) return NOISE_ERROR_NO_MEMORY;
+    tr->cipher_id = cipher_id;
+    tr->role = role;
+    tr->n = n;
+    tr->max_frames = max_frames;
+    tr->ctx_bytes = noise_aead_dev_ctx_bytes(cipher_id);
+    if (n) {
+        int rc = scan_counts(tr, nullptr, tr->scan_bytes, n, s); /* the size question: nothing is launched */
+        if (rc) {
+            delete tr;
+            return rc;
+        }
+        const size_t ns = n, nf = max_frames;
+        size_t off = 0;
+        const size_t o_ctx = carve(off, 2 * ns * tr->ctx_bytes), o_send = carve(off, ns * 8), o_recv = carve(off, ns * 8);
+        const size_t o_count = carve(off, ns * 8), o_base = carve(off, ns * 8), o_frames = carve(off, ns * 4);
+        const size_t o_consumed = carve(off, ns * 4), o_stop = carve(off, ns * 4);
+        const size_t o_recs = carve(off, nf * sizeof(RecDesc)), o_seal = carve(off, nf * sizeof(RecDesc));
+        const size_t o_status = carve(off, nf), o_keyed = carve(off, ns), o_scan = carve(off, tr->scan_bytes);
+        if (hipMalloc((void **)&tr->mem, off) != hipSuccess) {
+            delete tr;
+            return NOISE_ERROR_NO_MEMORY;
+        }
+        tr->mem_bytes = off;
+        uint8_t *m = tr->mem;
+        tr->ctx = m + o_ctx; tr->send = (uint64_t *)(m + o_send); tr->recv = (uint64_t *)(m + o_recv);
+        tr->count = (uint64_t *)(m + o_count); tr->base = (uint64_t *)(m + o_base);
+        tr->frames = (uint32_t *)(m + o_frames); tr->consumed = (uint32_t *)(m + o_consumed);
+        tr->stop = (int32_t *)(m + o_stop); tr->recs = (RecDesc *)(m + o_recs); tr->seal_recs = (RecDesc *)(m + o_seal);
+        tr->status = m + o_status; tr->keyed = m + o_keyed; tr->scan_tmp = m + o_scan;
+        rc = hip_rc(hipMemsetAsync(tr->mem, 0, tr->mem_bytes, s));
+        if (rc) {
+            noise_aead_dev_transport_free(tr);
+            return rc;
+        }
+    }
+    *out = tr;
+    return NOISE_ERROR_NONE;
+}
+
+TrKeyArgs key_args(const Tr *tr, const uint32_t *d_slots, uint32_t m)
+{
+    TrKeyArgs a = {};
+    a.slots = d_slots;
+    a.ctx = tr->ctx;
+    a.send = tr->send;
+    a.recv = tr->recv;
+    a.keyed = tr->keyed;
+    a.ctx_bytes = tr->ctx_bytes;
+    a.m = m;
+    a.n = tr->n;
+    a.initiator = tr->role == NOISE_ROLE_INITIATOR;
+    return a;
+}
+
+/* zero and un-key (set: after gcm_prepare_slots, the failed entries only; the rest are marked keyed) */
+int launch_clear(const Tr *tr, const TrKeyArgs &a, hipStream_t s)
+{
+    if (tr->ctx_bytes <= 64)
+        hipLaunchKernelGGL(tr_clear_lane, dim3((a.m + TR_BLOCK - 1) / TR_BLOCK), dim3(TR_BLOCK), 0, s, a);
+    else if (a.m > 0x7fffffffu / 2) /* 2m workgroups in one grid */
+        return NOISE_ERROR_INVALID_PARAM;
+    else
+        hipLaunchKernelGGL(tr_clear_wide, dim3(2 * a.m), dim3(TR_WIDE_BLOCK), 0, s, a);
+    return hip_rc(hipGetLastError());
 }
 
 } // namespace
@@ -242,41 +458,15 @@ int noise_aead_dev_transport_new(NoiseAeadDevTransport **out, int cipher_id, int
     int rc = tr_check_new(out, cipher_id, role, n, d_k1, d_k2, max_frames);
     if (rc) return rc;
     *out = nullptr;
-    Tr *tr = new (std::nothrow) Tr();
-    if (!tr) return NOISE_ERROR_NO_MEMORY;
-    tr->cipher_id = cipher_id;
-    tr->role = role;
-    tr->n = n;
-    tr->max_frames = max_frames;
-    tr->ctx_bytes = noise_aead_dev_ctx_bytes(cipher_id);
+    hipStream_t s = (hipStream_t)stream;
+    Tr *tr = nullptr;
+    rc = make(&tr, cipher_id, role, n, max_frames, s);
+    if (rc) return rc;
     if (n) {
-        hipStream_t s = (hipStream_t)stream;
-        rc = scan_counts(tr, nullptr, tr->scan_bytes, s); /* the size question: nothing is launched */
-        if (rc) {
-            delete tr;
-            return rc;
-        }
-        const size_t ns = n, nf = max_frames;
-        size_t off = 0;
-        const size_t o_ctx = carve(off, 2 * ns * tr->ctx_bytes), o_send = carve(off, ns * 8), o_recv = carve(off, ns * 8);
-        const size_t o_count = carve(off, ns * 8), o_base = carve(off, ns * 8), o_frames = carve(off, ns * 4);
-        const size_t o_consumed = carve(off, ns * 4), o_stop = carve(off, ns * 4);
-        const size_t o_recs = carve(off, nf * sizeof(RecDesc)), o_seal = carve(off, nf * sizeof(RecDesc));
-        const size_t o_status = carve(off, nf), o_scan = carve(off, tr->scan_bytes);
-        if (hipMalloc((void **)&tr->mem, off) != hipSuccess) {
-            delete tr;
-            return NOISE_ERROR_NO_MEMORY;
-        }
-        tr->mem_bytes = off;
-        uint8_t *m = tr->mem;
-        tr->ctx = m + o_ctx; tr->send = (uint64_t *)(m + o_send); tr->recv = (uint64_t *)(m + o_recv);
-        tr->count = (uint64_t *)(m + o_count); tr->base = (uint64_t *)(m + o_base);
-        tr->frames = (uint32_t *)(m + o_frames); tr->consumed = (uint32_t *)(m + o_consumed);
-        tr->stop = (int32_t *)(m + o_stop); tr->recs = (RecDesc *)(m + o_recs); tr->seal_recs = (RecDesc *)(m + o_seal);
-        tr->status = m + o_status; tr->scan_tmp = m + o_scan;
-        /* every nonce starts at 0; the initiator sends under k1, the responder under k2 */
+        /* every slot keyed; the initiator sends under k1, the responder under k2 */
         const bool init = role == NOISE_ROLE_INITIATOR;
-        rc = hip_rc(hipMemsetAsync(tr->mem, 0, tr->mem_bytes, s));
+        const size_t ns = n;
+        rc = hip_rc(hipMemsetAsync(tr->keyed, 1, ns, s));
         if (!rc) rc = noise_aead_dev_prepare(cipher_id, init ? d_k1 : d_k2, n, tr->ctx, s);
         if (!rc) rc = noise_aead_dev_prepare(cipher_id, init ? d_k2 : d_k1, n, tr->ctx + ns * tr->ctx_bytes, s);
         if (rc) {
@@ -286,6 +476,52 @@ int noise_aead_dev_transport_new(NoiseAeadDevTransport **out, int cipher_id, int
     }
     *out = tr;
     return NOISE_ERROR_NONE;
+}
+
+int noise_aead_dev_transport_new_unkeyed(NoiseAeadDevTransport **out, int cipher_id, int role, uint32_t n,
+                                         uint32_t max_frames, void *stream)
+{
+    const int rc = tr_check_new_unkeyed(out, cipher_id, role, n, max_frames);
+    if (rc) return rc;
+    return make(out, cipher_id, role, n, max_frames, (hipStream_t)stream);
+}
+
+int noise_aead_dev_transport_set_keys(NoiseAeadDevTransport *tr, const uint32_t *d_slots, uint32_t m, const uint8_t *d_k1,
+                                      const uint8_t *d_k2, const uint8_t *d_status, void *stream)
+{
+    int rc = tr_check_set_keys(tr, tr ? tr->n : 0, d_slots, m, d_k1, d_k2);
+    if (rc || !m) return rc;
+    hipStream_t s = (hipStream_t)stream;
+    TrKeyArgs a = key_args(tr, d_slots, m);
+    a.k1 = d_k1;
+    a.k2 = d_k2;
+    a.status = d_status;
+    a.set = 1;
+    if (tr->cipher_id == NOISE_CIPHER_CHACHAPOLY) {
+        hipLaunchKernelGGL(tr_set_keys, dim3((m + TR_BLOCK - 1) / TR_BLOCK), dim3(TR_BLOCK), 0, s, a);
+        return hip_rc(hipGetLastError());
+    }
+    rc = aes_prepare_slots(d_slots, m, tr->n, d_k1, d_k2, d_status, a.initiator != 0, tr->ctx, s);
+    return rc ? rc : launch_clear(tr, a, s);
+}
+
+int noise_aead_dev_transport_clear_keys(NoiseAeadDevTransport *tr, const uint32_t *d_slots, uint32_t m, void *stream)
+{
+    const int rc = tr_check_clear_keys(tr, tr ? tr->n : 0, d_slots, m);
+    if (rc || !m) return rc;
+    return launch_clear(tr, key_args(tr, d_slots, m), (hipStream_t)stream);
+}
+
+const uint8_t *noise_aead_dev_transport_has_key(const NoiseAeadDevTransport *tr)
+{
+    return tr ? tr->keyed : nullptr;
+}
+
+const uint8_t *noise_aead_debug_transport_ctx(const NoiseAeadDevTransport *tr, int direction, size_t *ctx_bytes)
+{
+    if (!tr || !tr->n || (direction != 0 && direction != 1)) return nullptr;
+    if (ctx_bytes) *ctx_bytes = tr->ctx_bytes;
+    return tr->ctx + (size_t)direction * tr->n * tr->ctx_bytes;
 }
 
 int noise_aead_dev_transport_free(NoiseAeadDevTransport *tr)
@@ -313,19 +549,40 @@ uint64_t *noise_aead_dev_transport_nonces(const NoiseAeadDevTransport *tr, int d
 int noise_aead_dev_transport_seal_frames(NoiseAeadDevTransport *tr, uint8_t *d_wire, const uint64_t *d_off,
                                          const uint32_t *d_len, NoiseAeadTransportResult *d_result, void *stream)
 {
-    return run(tr, TR_SEAL, d_wire, d_off, d_len, d_result, (hipStream_t)stream);
+    return run_all(tr, TR_SEAL, d_wire, d_off, d_len, d_result, stream);
 }
 
 int noise_aead_dev_transport_open_frames(NoiseAeadDevTransport *tr, uint8_t *d_wire, const uint64_t *d_off,
                                          const uint32_t *d_len, NoiseAeadTransportResult *d_result, void *stream)
 {
-    return run(tr, TR_OPEN, d_wire, d_off, d_len, d_result, (hipStream_t)stream);
+    return run_all(tr, TR_OPEN, d_wire, d_off, d_len, d_result, stream);
 }
 
 int noise_aead_dev_transport_echo_frames(NoiseAeadDevTransport *tr, uint8_t *d_wire, const uint64_t *d_off,
                                          const uint32_t *d_len, NoiseAeadTransportResult *d_result, void *stream)
 {
-    return run(tr, TR_ECHO, d_wire, d_off, d_len, d_result, (hipStream_t)stream);
+    return run_all(tr, TR_ECHO, d_wire, d_off, d_len, d_result, stream);
+}
+
+int noise_aead_dev_transport_seal_frames_of(NoiseAeadDevTransport *tr, const uint32_t *d_slots, uint32_t m,
+                                            uint32_t max_frames, uint8_t *d_wire, const uint64_t *d_off,
+                                            const uint32_t *d_len, NoiseAeadTransportResult *d_result, void *stream)
+{
+    return run_of(tr, TR_SEAL, d_slots, m, max_frames, d_wire, d_off, d_len, d_result, stream);
+}
+
+int noise_aead_dev_transport_open_frames_of(NoiseAeadDevTransport *tr, const uint32_t *d_slots, uint32_t m,
+                                            uint32_t max_frames, uint8_t *d_wire, const uint64_t *d_off,
+                                            const uint32_t *d_len, NoiseAeadTransportResult *d_result, void *stream)
+{
+    return run_of(tr, TR_OPEN, d_slots, m, max_frames, d_wire, d_off, d_len, d_result, stream);
+}
+
+int noise_aead_dev_transport_echo_frames_of(NoiseAeadDevTransport *tr, const uint32_t *d_slots, uint32_t m,
+                                            uint32_t max_frames, uint8_t *d_wire, const uint64_t *d_off,
+                                            const uint32_t *d_len, NoiseAeadTransportResult *d_result, void *stream)
+{
+    return run_of(tr, TR_ECHO, d_slots, m, max_frames, d_wire, d_off, d_len, d_result, stream);
 }
 
 } // extern "C"

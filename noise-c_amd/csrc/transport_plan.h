@@ -1,10 +1,11 @@
 /*
  * transport_plan.h — the host-only half of the device-resident transport
  * sessions (noise_aead_dev_transport_*, include/noise_aead_hip.h section 9):
- * the frame walk of one session, the cap rule across sessions, and the
- * argument checks.  One source for both compilers, as fe25519.h is: hipcc's
+ * the frame walk of one session, the cap rule across sessions, the slot of a
+ * call's entry (section 10, the session table), and the argument checks.  One source for both compilers, as fe25519.h is: hipcc's
  * device pass builds the kernels of transport.hip from tr_walk and tr_cap,
- * plain g++ builds asan/transport_check.cpp from them, so the CPU check under
+ * plain g++ builds asan/transport_check.cpp and asan/transport_table_check.cpp
+ * from them, so the CPU check under
  * ASan/UBSan runs the walk the GPU runs.
  *
  * The wire format is that of csrc/wire.c (echo-common.c:643-688): a 2-byte
@@ -97,6 +98,16 @@ TR_FN uint64_t tr_cap(uint64_t base, uint64_t count, uint64_t max_frames, bool *
     return base < max_frames ? max_frames - base : 0;
 }
 
+/* The slot of entry j of a call (section 10): slots[j], or j itself for the
+   calls that take no list (slots == NULL).  Returns whether it names one of
+   the object's n slots; an entry that does not is skipped by every kernel,
+   which resolves its slot through this one function.  Reads only slots[j]. */
+TR_FN bool tr_slot(const uint32_t *slots, uint32_t j, uint32_t n, uint32_t *i)
+{
+    *i = slots ? slots[j] : j;
+    return *i < n;
+}
+
 /* --------------------------------------------------------- argument checks
    Pointers are compared as numbers and never dereferenced. */
 
@@ -128,6 +139,53 @@ inline int tr_check_call(const void *tr, uint32_t n, const void *d_wire, const v
     if (!tr || !d_wire || !d_off || !d_len || !d_result) return NOISE_ERROR_INVALID_PARAM;
     const tr_u128 rb = (tr_u128)sizeof(NoiseAeadTransportResult) * n;
     if (tr_ranges_meet(d_result, rb, d_off, (tr_u128)8 * n) || tr_ranges_meet(d_result, rb, d_len, (tr_u128)4 * n))
+        return NOISE_ERROR_INVALID_PARAM;
+    return NOISE_ERROR_NONE;
+}
+
+/* ---- the session table (section 10), each in the order of the header.  A
+   check that returns NOISE_ERROR_NONE with m == 0 means: nothing to launch. */
+
+/* noise_aead_dev_transport_new_unkeyed: _new's checks without the key pointers */
+inline int tr_check_new_unkeyed(const void *out, int cipher_id, int role, uint32_t n, uint32_t max_frames)
+{
+    return tr_check_new(out, cipher_id, role, n, out, out, max_frames);
+}
+
+/* noise_aead_dev_transport_set_keys on an object of n slots (d_status may be NULL) */
+inline int tr_check_set_keys(const void *tr, uint32_t n, const void *d_slots, uint32_t m, const void *d_k1,
+                             const void *d_k2)
+{
+    if (!tr) return NOISE_ERROR_INVALID_PARAM;
+    if (!m) return NOISE_ERROR_NONE;
+    if (m > n) return NOISE_ERROR_INVALID_PARAM;
+    if (!d_slots || !d_k1 || !d_k2) return NOISE_ERROR_INVALID_PARAM;
+    return NOISE_ERROR_NONE;
+}
+
+/* noise_aead_dev_transport_clear_keys */
+inline int tr_check_clear_keys(const void *tr, uint32_t n, const void *d_slots, uint32_t m)
+{
+    if (!tr) return NOISE_ERROR_INVALID_PARAM;
+    if (!m) return NOISE_ERROR_NONE;
+    if (m > n || !d_slots) return NOISE_ERROR_INVALID_PARAM;
+    return NOISE_ERROR_NONE;
+}
+
+/* noise_aead_dev_transport_{seal,open,echo}_frames_of on an object of n slots
+   made for object_max_frames records */
+inline int tr_check_call_of(const void *tr, uint32_t n, uint32_t object_max_frames, const void *d_slots, uint32_t m,
+                            uint32_t max_frames, const void *d_wire, const void *d_off, const void *d_len,
+                            const void *d_result)
+{
+    if (!tr) return NOISE_ERROR_INVALID_PARAM;
+    if (!m) return NOISE_ERROR_NONE;
+    if (m > n) return NOISE_ERROR_INVALID_PARAM;
+    if (!d_slots || !d_wire || !d_off || !d_len || !d_result) return NOISE_ERROR_INVALID_PARAM;
+    if (max_frames > object_max_frames) return NOISE_ERROR_INVALID_PARAM;
+    const tr_u128 rb = (tr_u128)sizeof(NoiseAeadTransportResult) * m;
+    if (tr_ranges_meet(d_result, rb, d_off, (tr_u128)8 * m) || tr_ranges_meet(d_result, rb, d_len, (tr_u128)4 * m) ||
+        tr_ranges_meet(d_result, rb, d_slots, (tr_u128)4 * m))
         return NOISE_ERROR_INVALID_PARAM;
     return NOISE_ERROR_NONE;
 }

@@ -191,6 +191,14 @@ def lib() -> C.CDLL:
         "noise_aead_dev_transport_seal_frames": (i, [vp, vp, vp, vp, vp, vp]),
         "noise_aead_dev_transport_open_frames": (i, [vp, vp, vp, vp, vp, vp]),
         "noise_aead_dev_transport_echo_frames": (i, [vp, vp, vp, vp, vp, vp]),
+        "noise_aead_dev_transport_new_unkeyed": (i, [P(vp), i, i, C.c_uint32, C.c_uint32, vp]),
+        "noise_aead_dev_transport_set_keys": (i, [vp, vp, C.c_uint32, vp, vp, vp, vp]),
+        "noise_aead_dev_transport_clear_keys": (i, [vp, vp, C.c_uint32, vp]),
+        "noise_aead_dev_transport_has_key": (vp, [vp]),
+        "noise_aead_dev_transport_seal_frames_of": (i, [vp, vp, C.c_uint32, C.c_uint32, vp, vp, vp, vp, vp]),
+        "noise_aead_dev_transport_open_frames_of": (i, [vp, vp, C.c_uint32, C.c_uint32, vp, vp, vp, vp, vp]),
+        "noise_aead_dev_transport_echo_frames_of": (i, [vp, vp, C.c_uint32, C.c_uint32, vp, vp, vp, vp, vp]),
+        "noise_aead_debug_transport_ctx": (vp, [vp, i, P(sz)]),
         "noise_strerror": (i, [i, C.c_char_p, sz]),
         "noise_perror": (None, [C.c_char_p, i]),
         "noise_aead_debug_batch_stats": (None, [P(C.c_uint64), P(C.c_uint64)]),
@@ -591,6 +599,58 @@ def dev_transport_open_frames(tr: int, *, wire: int, off: int, length: int, resu
 
 def dev_transport_echo_frames(tr: int, *, wire: int, off: int, length: int, result: int, stream: int = 0) -> int:
     return _transport_call(lib().noise_aead_dev_transport_echo_frames, tr, wire, off, length, result, stream)
+
+
+# ---- the session table (section 10): slots keyed and un-keyed on the device,
+# calls over a device list of m slot numbers (32-bit)
+
+def dev_transport_new_unkeyed(cipher: int, role: int, n: int, *, max_frames: int, stream: int = 0):
+    """noise_aead_dev_transport_new_unkeyed: (rc, tr); tr is None unless rc == 0."""
+    tr = C.c_void_p()
+    rc = lib().noise_aead_dev_transport_new_unkeyed(C.byref(tr), cipher, role, n, max_frames, stream or None)
+    return rc, tr.value
+
+
+def dev_transport_set_keys(tr: int, *, slots: int, m: int, k1: int, k2: int, status: int = 0, stream: int = 0) -> int:
+    return lib().noise_aead_dev_transport_set_keys(tr, slots or None, m, k1 or None, k2 or None, status or None,
+                                                   stream or None)
+
+
+def dev_transport_clear_keys(tr: int, *, slots: int, m: int, stream: int = 0) -> int:
+    return lib().noise_aead_dev_transport_clear_keys(tr, slots or None, m, stream or None)
+
+
+def dev_transport_has_key(tr: int) -> int:
+    """device pointer of the n state bytes (1 keyed, 0 unkeyed)"""
+    return lib().noise_aead_dev_transport_has_key(tr) or 0
+
+
+def _transport_call_of(fn, tr, slots, m, max_frames, wire, off, length, result, stream):
+    return fn(tr, slots or None, m, max_frames, wire or None, off or None, length or None, result or None, stream or None)
+
+
+def dev_transport_seal_frames_of(tr: int, *, slots: int, m: int, max_frames: int = 0, wire: int, off: int, length: int,
+                                 result: int, stream: int = 0) -> int:
+    return _transport_call_of(lib().noise_aead_dev_transport_seal_frames_of, tr, slots, m, max_frames, wire, off, length,
+                              result, stream)
+
+
+def dev_transport_open_frames_of(tr: int, *, slots: int, m: int, max_frames: int = 0, wire: int, off: int, length: int,
+                                 result: int, stream: int = 0) -> int:
+    return _transport_call_of(lib().noise_aead_dev_transport_open_frames_of, tr, slots, m, max_frames, wire, off, length,
+                              result, stream)
+
+
+def dev_transport_echo_frames_of(tr: int, *, slots: int, m: int, max_frames: int = 0, wire: int, off: int, length: int,
+                                 result: int, stream: int = 0) -> int:
+    return _transport_call_of(lib().noise_aead_dev_transport_echo_frames_of, tr, slots, m, max_frames, wire, off, length,
+                              result, stream)
+
+
+def debug_transport_ctx(tr: int, direction: int):
+    """(device pointer of the n contexts of one direction, bytes per context); (0, 0) when there is none"""
+    size = C.c_size_t(0)
+    return lib().noise_aead_debug_transport_ctx(tr, direction, C.byref(size)) or 0, size.value
 
 
 def dev_fill_splitmix(d_out: int, nbytes: int, seed: int, word0: int = 0, stream: int = 0) -> int:
