@@ -335,7 +335,9 @@ static void check_argument_rules()
             CHECK(uni(c, with(ok, [](auto &j) { j.out = (uint8_t *)(FAKE + 64), j.out_stride = 1408; })) == PARAM,
                   "output shifted into the input");
             CHECK(uni(c, with(ok, [](auto &j) { j.out = (uint8_t *)(FAKE + 4 * 1408 - 16); })) == PARAM, "spans touch");
-            /* one stride, input and output slots alternating */
+            /* one stride, input and output slots alternating.  The
+               accepted ones are checked here alone: through the library an
+               accepted job is launched, which invented pointers must never be */
             const NoiseAeadUniform inter = with(ok, [](auto &j) { j.in_stride = j.out_stride = 2848; });
             CHECK(uni(c, with(inter, [](auto &j) { j.out = (uint8_t *)(FAKE + 1424); })) == OK, "interleaved above");
             CHECK(uni(c, with(inter, [](auto &j) { j.out = (uint8_t *)(FAKE - 1424); })) == OK, "interleaved below");

@@ -216,12 +216,8 @@ int noise_aead_dev_hkdf(int hash_id, const uint8_t *d_keys, uint32_t key_len,
                         const uint8_t *d_data, uint32_t data_len, uint32_t n, uint8_t *d_out1,
                         uint32_t out1_len, uint8_t *d_out2, uint32_t out2_len, void *stream)
 {
-    uint32_t hl;
-    switch (hash_id) {
-    case NOISE_HASH_BLAKE2s: case NOISE_HASH_SHA256: hl = 32; break;
-    case NOISE_HASH_BLAKE2b: case NOISE_HASH_SHA512: hl = 64; break;
-    default: return NOISE_ERROR_UNKNOWN_ID;
-    }
+    const uint32_t hl = hash_len(hash_id);
+    if (!hl) return NOISE_ERROR_UNKNOWN_ID;
     if (!n) return NOISE_ERROR_NONE;
     if (!d_keys || !d_out1 || !d_out2 || (data_len && !d_data)) return NOISE_ERROR_INVALID_PARAM;
     /* hashstate.c:496-497 */
@@ -234,29 +230,20 @@ int noise_aead_dev_hkdf(int hash_id, const uint8_t *d_keys, uint32_t key_len,
     a.data = data_len ? d_data : nullptr;
     a.out1 = d_out1;
     a.out2 = d_out2;
+    a.hlen = hl;
     a.key_len = key_len;
     a.data_len = data_len;
     a.out1_len = out1_len;
     a.out2_len = out2_len;
     a.n = n;
-    hipLaunchKernelGGL(hkdf_batch, dim3((n + 63) / 64), dim3(64), 0, (hipStream_t)stream, a);
-    return hip_rc(hipGetLastError());
+    return launch_items(hkdf_batch, n, KDF_BLOCK, (hipStream_t)stream, a);
 }
 
 int noise_aead_dev_split(int hash_id, const uint8_t *d_ck, uint32_t n, uint8_t *d_k1,
                          uint8_t *d_k2, void *stream)
 {
-    const uint32_t hl = (hash_id == NOISE_HASH_BLAKE2b || hash_id == NOISE_HASH_SHA512) ? 64 : 32;
-    return noise_aead_dev_hkdf(hash_id, d_ck, hl, nullptr, 0, n, d_k1, 32, d_k2, 32, stream);
-}
-
-static uint32_t hash_len_of(int hash_id)
-{
-    switch (hash_id) {
-    case NOISE_HASH_BLAKE2s: case NOISE_HASH_SHA256: return 32;
-    case NOISE_HASH_BLAKE2b: case NOISE_HASH_SHA512: return 64;
-    }
-    return 0;
+    /* an unknown id: key_len 0 here, and noise_aead_dev_hkdf answers UNKNOWN_ID before it looks at it */
+    return noise_aead_dev_hkdf(hash_id, d_ck, hash_len(hash_id), nullptr, 0, n, d_k1, 32, d_k2, 32, stream);
 }
 
 static int launch_mix_hash(int hash_id, uint32_t hl, const uint8_t *h_in, uint8_t *h_out,
@@ -271,14 +258,13 @@ static int launch_mix_hash(int hash_id, uint32_t hl, const uint8_t *h_in, uint8_
     m.base = use_out ? job->out : job->in;
     m.recs = (const RecDesc *)job->recs;
     m.use_out_off = use_out;
-    hipLaunchKernelGGL(mix_hash_batch, dim3((job->n_records + 63) / 64), dim3(64), 0, s, m);
-    return hip_rc(hipGetLastError());
+    return launch_items(mix_hash_batch, job->n_records, KDF_BLOCK, s, m);
 }
 
 int noise_aead_dev_encrypt_and_hash(int cipher_id, int hash_id, uint8_t *d_h,
                                     const NoiseAeadRagged *job, void *stream)
 {
-    const uint32_t hl = hash_len_of(hash_id);
+    const uint32_t hl = hash_len(hash_id);
     if (!hl) return NOISE_ERROR_UNKNOWN_ID;
     if (!d_h || !job || job->ad != d_h) return NOISE_ERROR_INVALID_PARAM;
     if (job->n_records == 0) return NOISE_ERROR_NONE;
@@ -290,7 +276,7 @@ int noise_aead_dev_encrypt_and_hash(int cipher_id, int hash_id, uint8_t *d_h,
 int noise_aead_dev_decrypt_and_hash(int cipher_id, int hash_id, uint8_t *d_h,
                                     const NoiseAeadRagged *job, void *stream)
 {
-    const uint32_t hl = hash_len_of(hash_id);
+    const uint32_t hl = hash_len(hash_id);
     if (!hl) return NOISE_ERROR_UNKNOWN_ID;
     if (!d_h || !job || job->ad != d_h || !job->status) return NOISE_ERROR_INVALID_PARAM;
     if (job->n_records == 0) return NOISE_ERROR_NONE;
@@ -303,13 +289,9 @@ int noise_aead_dev_decrypt_and_hash(int cipher_id, int hash_id, uint8_t *d_h,
     /* hash the ciphertext before the (in-place) decryption overwrites it */
     int rc = launch_mix_hash(hash_id, hl, d_h, h_new, job, false, s);
     if (!rc) rc = run_ragged(cipher_id, job, stream, true);
-    if (!rc) {
-        const uint64_t total = (uint64_t)job->n_records * hl;
-        hipLaunchKernelGGL(commit_hash, dim3((uint32_t)((total + 255) / 256)), dim3(256), 0, s, d_h,
-                           (const uint8_t *)h_new, (const uint8_t *)job->status, hl,
-                           job->n_records);
-        rc = hip_rc(hipGetLastError());
-    }
+    if (!rc) /* one lane per byte of h */
+        rc = launch_items(commit_hash, (uint64_t)job->n_records * hl, KDF_COMMIT_BLOCK, s, d_h, h_new, job->status, hl,
+                          job->n_records);
     (void)hipFreeAsync(h_new, s);
     return rc;
 }

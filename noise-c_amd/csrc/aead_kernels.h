@@ -69,6 +69,18 @@ __device__ __forceinline__ bool reject_len(const RaggedArgs &a, uint32_t rec, ui
     return true;
 }
 
+/* The descriptor of a record the ragged kernels refuse: what a kernel that
+   builds descriptors on the device (handshake.hip, transport.hip) writes where
+   nothing may be sealed or opened. */
+constexpr uint32_t REFUSED_LEN = MAX_RECORD_LEN + 1;
+
+__device__ __forceinline__ RecDesc refused_rec()
+{
+    RecDesc d = {};
+    d.len = REFUSED_LEN;
+    return d;
+}
+
 /* Length-balanced record order for a workgroup of a ragged batch.  A wave is
    as slow as its longest record, so the NREC records of the workgroup's
    window [base, base + NREC) are ranked by length (bitonic sort of

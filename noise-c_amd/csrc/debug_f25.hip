@@ -58,7 +58,5 @@ extern "C" int noise_aead_debug_f25_op(int op, const uint8_t *d_a, const uint8_t
     if (!d_a || !d_out || (binary && !d_b)) return NOISE_ERROR_INVALID_PARAM;
     const uint64_t bytes = (uint64_t)32 * n;
     if (meets(d_out, d_a, bytes) || (binary && meets(d_out, d_b, bytes))) return NOISE_ERROR_INVALID_PARAM;
-    const dim3 grid((uint32_t)(((uint64_t)n + F25_BLOCK - 1) / F25_BLOCK)), block(F25_BLOCK);
-    hipLaunchKernelGGL(f25_op_batch, grid, block, 0, (hipStream_t)stream, op, d_a, binary ? d_b : nullptr, d_out, n);
-    return hip_rc(hipGetLastError());
+    return launch_items(f25_op_batch, n, F25_BLOCK, (hipStream_t)stream, op, d_a, binary ? d_b : nullptr, d_out, n);
 }

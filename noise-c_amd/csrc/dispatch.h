@@ -27,6 +27,18 @@ constexpr uint32_t PLAN_GCM_WG = 1024;    /* GCM_WG */
 constexpr uint32_t PLAN_GCM_WG_RECS = 256; /* GCM_WG_RECS */
 constexpr uint32_t PLAN_SEG_KMAX = 16;    /* SEG_KMAX */
 
+/* The length of a Noise hash (constants.h:43-46); 0 for an id that is none.
+   The one place the host knows it: the entry points turn 0 into their answer
+   for an unknown id and hand the kernels the length. */
+inline uint32_t hash_len(int hash_id)
+{
+    switch (hash_id) {
+    case NOISE_HASH_BLAKE2s: case NOISE_HASH_SHA256: return 32;
+    case NOISE_HASH_BLAKE2b: case NOISE_HASH_SHA512: return 64;
+    }
+    return 0;
+}
+
 /* ------------------------------------------------------------ the switches
    env_flag: a switch that is on by default goes off with "0", one that is
    off goes on with "1"; env_int: a positive number, else dflt; env_choice:

@@ -6,10 +6,13 @@
  * issues, per step, launches over all n sessions; nothing comes back to the
  * host, so the action, the nonce and "is a key set" — which are the same for
  * every session of a batch — live on the host and everything per session
- * (ck, h, k, statuses, public keys) lives on the device.
+ * (ck, h, k, statuses, public keys) lives on the device, in one DevArena
+ * (launch.h): zeroed before use, zeroed again before it is freed.
  *
- * The kernels here run one lane per session in 64-lane workgroups over the
- * Hasher of hasher.h:
+ * The kernels here run one lane per session in 64-lane workgroups
+ * (launch_items, launch.h) over the SymmetricState arithmetic of hasher.h —
+ * kdf_hkdf, kdf_mix_hash, load_row / store_row for a session's h or ck; none
+ * of it is restated here:
  *   hs_init       h = the protocol name padded or hashed, ck = h
  *                 (symmetricstate.c:97-108);
  *   hs_mix_hash   h = HASH(h || bytes) over strided bytes, with an optional
@@ -24,8 +27,8 @@
  *   hs_null_check the all-zero received ephemeral (:1464-1470) -> status 3;
  *   hs_build_recs the NoiseAeadRecord array of one AEAD step from (stride,
  *                 length, nonce, i * ctx_bytes, i * hash_len); a failed
- *                 session gets a length the ragged kernels refuse, so nothing
- *                 more is sealed or opened for it;
+ *                 session gets the length the ragged kernels refuse (REFUSED_LEN,
+ *                 aead_kernels.h), so nothing more is sealed or opened for it;
  *   hs_split      k1, k2 = HKDF(ck, ""), zeros for a failed session, and h.
  * DH tokens are the ladder launches of noise_aead_dev_dh_calculate into an
  * arena the object owns; the AEAD steps are noise_aead_dev_seal_ragged /
@@ -45,26 +48,9 @@ using namespace na;
 namespace {
 
 constexpr uint32_t HS_BLOCK = 64;
-constexpr uint32_t HS_REFUSED_LEN = MAX_RECORD_LEN + 1; /* aead_kernels.h reject_len */
+constexpr size_t HS_ALIGN = 64; /* of the parts of the object's device allocation */
 constexpr uint8_t HS_STATUS_MAC = 1, HS_STATUS_NULL_KEY = 3;
 constexpr size_t HS_NAME_MAX = 64; /* the longest name in scope has 36 characters */
-
-NA_DEV void hs_load_h(uint8_t *dst, const uint8_t *h, uint32_t hl)
-{
-    for (uint32_t j = 0; j < hl; ++j) dst[j] = h[j];
-}
-
-/* noise_hashstate_hkdf (hashstate.c:476-516) of one lane, both outputs whole */
-NA_DEV void hs_hkdf(int hid, uint32_t hl, const uint8_t *key, const uint8_t *data, uint32_t data_len, uint8_t *o1,
-                    uint8_t *o2)
-{
-    uint8_t tk[64];
-    const uint8_t one = 0x01, two = 0x02;
-    kdf_hmac(hid, key, hl, data, data_len, nullptr, 0, tk);
-    kdf_hmac(hid, tk, hl, &one, 1, nullptr, 0, o1);
-    kdf_hmac(hid, tk, hl, o1, hl, &two, 1, o2);
-    for (int j = 0; j < 64; ++j) tk[j] = 0;
-}
 
 struct InitArgs {
     int hash_id;
@@ -86,7 +72,7 @@ __global__ __launch_bounds__(HS_BLOCK) void hs_init(InitArgs a)
         H.update(a.name, a.name_len);
         H.final(h);
     }
-    for (uint32_t j = 0; j < a.hl; ++j) a.h[(size_t)i * a.hl + j] = a.ck[(size_t)i * a.hl + j] = h[j];
+    for (uint32_t j = 0; j < a.hl; ++j) a.h[(size_t)i * a.hl + j] = a.ck[(size_t)i * a.hl + j] = h[j]; /* one pass, two rows */
 }
 
 struct MixHashStrided {
@@ -116,13 +102,9 @@ __global__ __launch_bounds__(HS_BLOCK) void hs_mix_hash(MixHashStrided a)
         for (uint32_t j = 0; j < a.len; ++j) dst[j] = src[j];
     }
     uint8_t h[64];
-    hs_load_h(h, a.h + (size_t)i * a.hl, a.hl);
-    Hasher H;
-    H.init(a.hash_id);
-    H.update(h, a.hl);
-    H.update(src, a.len);
-    H.final(h);
-    for (uint32_t j = 0; j < a.hl; ++j) a.h[(size_t)i * a.hl + j] = h[j];
+    load_row(h, a.h, i, a.hl);
+    kdf_mix_hash(a.hash_id, a.hl, h, src, a.len);
+    store_row(a.h, i, a.hl, h);
 }
 
 struct MixKeyArgs {
@@ -141,19 +123,15 @@ __global__ __launch_bounds__(HS_BLOCK) void hs_mix_key(MixKeyArgs a)
     if (i >= a.n) return;
     uint8_t *ikm_p = a.ikm + (uint64_t)i * a.ikm_stride;
     uint8_t ck[64], ikm[32], o1[64], o2[64];
-    hs_load_h(ck, a.ck + (size_t)i * a.hl, a.hl);
+    load_row(ck, a.ck, i, a.hl);
     for (int j = 0; j < 32; ++j) ikm[j] = ikm_p[j];
-    hs_hkdf(a.hash_id, a.hl, ck, ikm, 32, o1, o2);
-    for (uint32_t j = 0; j < a.hl; ++j) a.ck[(size_t)i * a.hl + j] = o1[j];
+    kdf_hkdf(a.hash_id, a.hl, ck, a.hl, ikm, 32, o1, o2);
+    store_row(a.ck, i, a.hl, o1);
     if (a.psk) {
         uint8_t h[64];
-        hs_load_h(h, a.h + (size_t)i * a.hl, a.hl);
-        Hasher H;
-        H.init(a.hash_id);
-        H.update(h, a.hl);
-        H.update(o2, a.hl);
-        H.final(h);
-        for (uint32_t j = 0; j < a.hl; ++j) a.h[(size_t)i * a.hl + j] = h[j];
+        load_row(h, a.h, i, a.hl);
+        kdf_mix_hash(a.hash_id, a.hl, h, o2, a.hl);
+        store_row(a.h, i, a.hl, h);
     } else {
         for (int j = 0; j < 32; ++j) a.k[(size_t)i * 32 + j] = o2[j];
     }
@@ -196,7 +174,7 @@ __global__ __launch_bounds__(HS_BLOCK) void hs_build_recs(BuildRecs a)
     d.nonce = a.nonce;
     d.ctx_off = (uint64_t)i * a.ctx_bytes;
     d.ad_off = (uint64_t)i * a.hl;
-    d.len = a.status[i] ? HS_REFUSED_LEN : a.len;
+    d.len = a.status[i] ? REFUSED_LEN : a.len;
     d.ad_len = a.hl;
     a.recs[i] = d;
 }
@@ -214,8 +192,8 @@ __global__ __launch_bounds__(HS_BLOCK) void hs_split(SplitArgs a)
     const uint32_t i = blockIdx.x * HS_BLOCK + threadIdx.x;
     if (i >= a.n) return;
     uint8_t ck[64], o1[64], o2[64];
-    hs_load_h(ck, a.ck + (size_t)i * a.hl, a.hl);
-    hs_hkdf(a.hash_id, a.hl, ck, nullptr, 0, o1, o2);
+    load_row(ck, a.ck, i, a.hl);
+    kdf_hkdf(a.hash_id, a.hl, ck, a.hl, nullptr, 0, o1, o2);
     const bool failed = a.status[i] != 0;
     for (int j = 0; j < 32; ++j) {
         a.k1[(size_t)i * 32 + j] = failed ? 0 : o1[j];
@@ -225,8 +203,6 @@ __global__ __launch_bounds__(HS_BLOCK) void hs_split(SplitArgs a)
         for (uint32_t j = 0; j < a.hl; ++j) a.hh[(size_t)i * a.hl + j] = a.h[(size_t)i * a.hl + j];
     for (int j = 0; j < 64; ++j) ck[j] = o1[j] = o2[j] = 0;
 }
-
-dim3 hs_grid(uint32_t n) { return dim3((uint32_t)(((uint64_t)n + HS_BLOCK - 1) / HS_BLOCK)); }
 
 } // namespace
 
@@ -240,9 +216,7 @@ struct NoiseAeadDevHandshake {
     /* the caller's private keys (read by the DH steps) */
     const uint8_t *ls_priv, *le_priv;
     uint64_t ls_stride, le_stride;
-    /* one device allocation, carved */
-    uint8_t *mem;
-    size_t mem_bytes;
+    DevArena dev; /* the one device allocation; the pointers below are its parts */
     uint8_t *ck, *h, *k, *ctx, *arena, *status, *step, *ls_pub, *le_pub, *re, *rs;
     RecDesc *recs;
     uint64_t ls_pub_stride, le_pub_stride;
@@ -261,21 +235,20 @@ int mix_hash(Hs *hs, const uint8_t *src, uint64_t src_stride, uint32_t len, uint
 {
     const MixHashStrided a = {hs->name.hash_id, hs->hl, hs->n, len, hs->h, src, src_stride, dst, dst_stride,
                               hs->status, step};
-    hipLaunchKernelGGL(hs_mix_hash, hs_grid(hs->n), dim3(HS_BLOCK), 0, s, a);
-    return hip_rc(hipGetLastError());
+    return launch_items(hs_mix_hash, hs->n, HS_BLOCK, s, a);
 }
 
 int mix_key(Hs *hs, const uint8_t *ikm, uint64_t ikm_stride, bool zero_ikm, bool psk, hipStream_t s)
 {
     const MixKeyArgs a = {hs->name.hash_id, hs->hl, hs->n, hs->ck, hs->k, hs->h, (uint8_t *)ikm, ikm_stride,
                           zero_ikm, psk};
-    hipLaunchKernelGGL(hs_mix_key, hs_grid(hs->n), dim3(HS_BLOCK), 0, s, a);
+    const int rc = launch_items(hs_mix_key, hs->n, HS_BLOCK, s, a);
     if (!psk) {
         hs->keyed = true;
         hs->nonce = 0;
         hs->ctx_stale = true;
     }
-    return hip_rc(hipGetLastError());
+    return rc;
 }
 
 /* encrypt_and_hash / decrypt_and_hash of `len` bytes for every session once
@@ -291,8 +264,7 @@ int aead_step(Hs *hs, bool open, const uint8_t *in, uint64_t in_stride, uint8_t 
     hs->ctx_stale = false;
     if (rc) return rc;
     const BuildRecs b = {hs->recs, hs->status, in_stride, out_stride, hs->nonce, hs->ctx_bytes, len, hs->hl, hs->n};
-    hipLaunchKernelGGL(hs_build_recs, hs_grid(hs->n), dim3(HS_BLOCK), 0, s, b);
-    rc = hip_rc(hipGetLastError());
+    rc = launch_items(hs_build_recs, hs->n, HS_BLOCK, s, b);
     if (rc) return rc;
     NoiseAeadRagged job = {};
     job.ctx_base = cipher == NOISE_CIPHER_AESGCM ? hs->ctx : hs->k;
@@ -335,11 +307,7 @@ int run_message(Hs *hs, const HsMessage &m, bool write, uint8_t *msg, uint64_t m
                 if (!rc && st.mix_key) rc = mix_key(hs, hs->le_pub, hs->le_pub_stride, false, false, s);
             } else {
                 rc = mix_hash(hs, at, msg_stride, HS_DH_LEN, hs->re, HS_DH_LEN, nullptr, s);
-                if (!rc) {
-                    hipLaunchKernelGGL(hs_null_check, hs_grid(hs->n), dim3(HS_BLOCK), 0, s, (const uint8_t *)hs->re,
-                                       hs->status, hs->n);
-                    rc = hip_rc(hipGetLastError());
-                }
+                if (!rc) rc = launch_items(hs_null_check, hs->n, HS_BLOCK, s, hs->re, hs->status, hs->n);
                 if (!rc && st.mix_key) rc = mix_key(hs, hs->re, HS_DH_LEN, false, false, s);
             }
             off += HS_DH_LEN;
@@ -376,19 +344,12 @@ void advance(Hs *hs, const HsMessage &m)
     ++hs->index;
 }
 
-size_t carve(size_t &off, size_t bytes)
-{
-    const size_t at = off;
-    off += (bytes + 63) & ~(size_t)63;
-    return at;
-}
-
 /* everything _new launches, after the allocation */
 int start(Hs *hs, const NoiseAeadHandshakeConfig *cfg, hipStream_t s)
 {
     const HsPattern &p = pattern_of(hs);
     const HsNeeds need = hs_needs(p, hs->role);
-    int rc = hip_rc(hipMemsetAsync(hs->mem, 0, hs->mem_bytes, s));
+    int rc = hs->dev.zero(s);
     /* the local public keys: one ladder launch each, one lane for a shared key */
     if (!rc && need.local_static)
         rc = noise_aead_dev_dh_public(NOISE_DH_CURVE25519, hs->ls_priv, hs->ls_stride, hs->ls_stride ? hs->n : 1,
@@ -396,11 +357,9 @@ int start(Hs *hs, const NoiseAeadHandshakeConfig *cfg, hipStream_t s)
     if (!rc && need.local_ephemeral)
         rc = noise_aead_dev_dh_public(NOISE_DH_CURVE25519, hs->le_priv, hs->le_stride, hs->le_stride ? hs->n : 1,
                                       hs->le_pub, s);
-    if (!rc && need.remote_static) {
-        hipLaunchKernelGGL(hs_copy32, hs_grid(hs->n), dim3(HS_BLOCK), 0, s, cfg->d_remote_static_pub,
-                           cfg->remote_static_stride, hs->rs, hs->n);
-        rc = hip_rc(hipGetLastError());
-    }
+    if (!rc && need.remote_static)
+        rc = launch_items(hs_copy32, hs->n, HS_BLOCK, s, cfg->d_remote_static_pub, cfg->remote_static_stride, hs->rs,
+                          hs->n);
     if (rc) return rc;
     InitArgs ia = {};
     ia.hash_id = hs->name.hash_id;
@@ -410,8 +369,7 @@ int start(Hs *hs, const NoiseAeadHandshakeConfig *cfg, hipStream_t s)
     ia.h = hs->h;
     ia.ck = hs->ck;
     memcpy(ia.name, cfg->protocol_name, ia.name_len);
-    hipLaunchKernelGGL(hs_init, hs_grid(hs->n), dim3(HS_BLOCK), 0, s, ia);
-    rc = hip_rc(hipGetLastError());
+    rc = launch_items(hs_init, hs->n, HS_BLOCK, s, ia);
     /* handshakestate.c:822-877 */
     if (!rc)
         rc = mix_hash(hs, cfg->prologue_len ? cfg->d_prologue : hs->arena, cfg->prologue_stride, cfg->prologue_len,
@@ -445,7 +403,7 @@ int noise_aead_dev_handshake_new(NoiseAeadDevHandshake **out, const NoiseAeadHan
     hs->role = cfg->role;
     hs->action = hs_first_action(cfg->role);
     hs->n = cfg->n;
-    hs->hl = hs_hash_len(name.hash_id);
+    hs->hl = hash_len(name.hash_id);
     hs->ctx_bytes = noise_aead_dev_ctx_bytes(name.cipher_id);
     hs->ls_priv = cfg->d_local_static_priv;
     hs->ls_stride = cfg->local_static_stride;
@@ -455,21 +413,20 @@ int noise_aead_dev_handshake_new(NoiseAeadDevHandshake **out, const NoiseAeadHan
     hs->le_pub_stride = hs->le_stride ? HS_DH_LEN : 0;
     if (hs->n) {
         const size_t n = hs->n;
-        size_t off = 0;
-        const size_t o_ck = carve(off, n * hs->hl), o_h = carve(off, n * hs->hl), o_k = carve(off, n * 32);
-        const size_t o_ctx = carve(off, name.cipher_id == NOISE_CIPHER_AESGCM ? n * hs->ctx_bytes : 0);
-        const size_t o_arena = carve(off, n * 32), o_status = carve(off, n), o_step = carve(off, n);
-        const size_t o_ls = carve(off, n * 32), o_le = carve(off, n * 32), o_re = carve(off, n * 32);
-        const size_t o_rs = carve(off, n * 32), o_recs = carve(off, n * sizeof(RecDesc));
-        if (hipMalloc((void **)&hs->mem, off) != hipSuccess) {
+        DevArena &d = hs->dev;
+        d.align = HS_ALIGN;
+        const size_t o_ck = d.carve(n * hs->hl), o_h = d.carve(n * hs->hl), o_k = d.carve(n * 32);
+        const size_t o_ctx = d.carve(name.cipher_id == NOISE_CIPHER_AESGCM ? n * hs->ctx_bytes : 0);
+        const size_t o_arena = d.carve(n * 32), o_status = d.carve(n), o_step = d.carve(n);
+        const size_t o_ls = d.carve(n * 32), o_le = d.carve(n * 32), o_re = d.carve(n * 32);
+        const size_t o_rs = d.carve(n * 32), o_recs = d.carve(n * sizeof(RecDesc));
+        if (!d.alloc()) {
             delete hs;
             return NOISE_ERROR_NO_MEMORY;
         }
-        hs->mem_bytes = off;
-        uint8_t *m = hs->mem;
-        hs->ck = m + o_ck; hs->h = m + o_h; hs->k = m + o_k; hs->ctx = m + o_ctx; hs->arena = m + o_arena;
-        hs->status = m + o_status; hs->step = m + o_step; hs->ls_pub = m + o_ls; hs->le_pub = m + o_le;
-        hs->re = m + o_re; hs->rs = m + o_rs; hs->recs = (RecDesc *)(m + o_recs);
+        hs->ck = d.at(o_ck); hs->h = d.at(o_h); hs->k = d.at(o_k); hs->ctx = d.at(o_ctx); hs->arena = d.at(o_arena);
+        hs->status = d.at(o_status); hs->step = d.at(o_step); hs->ls_pub = d.at(o_ls); hs->le_pub = d.at(o_le);
+        hs->re = d.at(o_re); hs->rs = d.at(o_rs); hs->recs = d.at<RecDesc>(o_recs);
         rc = start(hs, cfg, (hipStream_t)stream);
         if (rc) {
             noise_aead_dev_handshake_free(hs);
@@ -483,14 +440,7 @@ int noise_aead_dev_handshake_new(NoiseAeadDevHandshake **out, const NoiseAeadHan
 int noise_aead_dev_handshake_free(NoiseAeadDevHandshake *hs)
 {
     if (!hs) return NOISE_ERROR_INVALID_PARAM;
-    int rc = NOISE_ERROR_NONE;
-    if (hs->mem) {
-        /* work of this object may still be in flight on the caller's streams */
-        rc = hip_rc(hipDeviceSynchronize());
-        const int rc2 = hip_rc(hipMemset(hs->mem, 0, hs->mem_bytes));
-        const int rc3 = hip_rc(hipFree(hs->mem));
-        rc = rc ? rc : (rc2 ? rc2 : rc3);
-    }
+    const int rc = hs->dev.release();
     memset((void *)hs, 0, sizeof(*hs));
     delete hs;
     return rc;
@@ -544,8 +494,7 @@ int noise_aead_dev_handshake_split(NoiseAeadDevHandshake *hs, uint8_t *d_k1, uin
     if (rc) return rc;
     if (hs->n) {
         const SplitArgs a = {hs->name.hash_id, hs->hl, hs->n, hs->ck, hs->h, hs->status, d_k1, d_k2, d_handshake_hash};
-        hipLaunchKernelGGL(hs_split, hs_grid(hs->n), dim3(HS_BLOCK), 0, (hipStream_t)stream, a);
-        rc = hip_rc(hipGetLastError());
+        rc = launch_items(hs_split, hs->n, HS_BLOCK, (hipStream_t)stream, a);
     }
     hs->action = NOISE_ACTION_COMPLETE;
     return rc;

@@ -152,11 +152,6 @@ inline int hs_parse_name(const char *name, HsName *out)
     return NOISE_ERROR_NONE;
 }
 
-inline uint32_t hs_hash_len(int hash_id)
-{
-    return hash_id == NOISE_HASH_BLAKE2b || hash_id == NOISE_HASH_SHA512 ? 64 : 32;
-}
-
 /* ------------------------------------------------------------------ steps */
 
 enum HsStepKind : uint8_t {

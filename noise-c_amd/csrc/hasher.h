@@ -2,7 +2,8 @@
  * hasher.h — the four Noise hashes (constants.h:43-46) and HMAC as one lane
  * runs them: SHA-256 / SHA-512 (FIPS 180-4; src/crypto/sha2), BLAKE2s /
  * BLAKE2b (RFC 7693, unkeyed; src/crypto/blake2), HMAC as
- * noise_hashstate_hmac (hashstate.c:407-448).  Shared by the key fan-out
+ * noise_hashstate_hmac (hashstate.c:407-448), and over them the HKDF and the
+ * MixHash of a SymmetricState (kdf_hkdf, kdf_mix_hash).  Shared by the key fan-out
  * kernels (kdf.hip) and the batched handshakes (handshake.hip); the tables
  * are per translation unit.
  */
@@ -270,6 +271,46 @@ NA_DEV void kdf_hmac(int hid, const uint8_t *key, uint32_t key_len, const uint8_
     H.update(kb, H.blen);
     H.update(inner, H.hlen);
     H.final(out);
+}
+
+/* The SymmetricState arithmetic of one lane, written once for the key fan-out
+   (kdf.hip) and the handshakes (handshake.hip).
+
+   noise_hashstate_hkdf (hashstate.c:476-516): both outputs whole, hl bytes
+   each (hl: the hash's length); its temporary is zeroed (:512-513), the
+   outputs are the caller's to clean. */
+NA_DEV void kdf_hkdf(int hid, uint32_t hl, const uint8_t *key, uint32_t key_len, const uint8_t *data,
+                     uint32_t data_len, uint8_t *o1, uint8_t *o2)
+{
+    uint8_t tk[64];
+    const uint8_t one = 0x01, two = 0x02;
+    kdf_hmac(hid, key, key_len, data, data_len, nullptr, 0, tk);
+    kdf_hmac(hid, tk, hl, &one, 1, nullptr, 0, o1);
+    kdf_hmac(hid, tk, hl, o1, hl, &two, 1, o2);
+    for (int j = 0; j < 64; ++j) tk[j] = 0;
+}
+
+/* noise_symmetricstate_mix_hash (symmetricstate.c:244-258) on a lane's own
+   h: h = HASH(h || p[0..n)) */
+NA_DEV void kdf_mix_hash(int hid, uint32_t hl, uint8_t *h, const uint8_t *p, uint32_t n)
+{
+    Hasher H;
+    H.init(hid);
+    H.update(h, hl);
+    H.update(p, n);
+    H.final(h);
+}
+
+/* row i of a batch's h or ck (hl bytes a row), into and out of a lane */
+NA_DEV void load_row(uint8_t *dst, const uint8_t *rows, uint32_t i, uint32_t hl)
+{
+    const uint8_t *row = rows + (size_t)i * hl;
+    for (uint32_t j = 0; j < hl; ++j) dst[j] = row[j];
+}
+
+NA_DEV void store_row(uint8_t *rows, uint32_t i, uint32_t hl, const uint8_t *src)
+{
+    for (uint32_t j = 0; j < hl; ++j) rows[(size_t)i * hl + j] = src[j];
 }
 
 } // namespace na

@@ -15,6 +15,10 @@
  * contexts, so a batch of finished handshakes becomes a batch of transport
  * CipherStates without leaving the device.
  *
+ * The arithmetic itself — HMAC, HKDF, MixHash — is hasher.h's, shared with
+ * the batched handshakes (handshake.hip); the kernels here are the batch
+ * loads and stores around it.
+ *
  * This is scalar per-lane work (a split is 6 compressions), not a hot loop;
  * it is written for clarity and checked byte for byte against the oracle
  * and the reference's own HKDF outputs (tests/golden/hkdf.json).
@@ -25,30 +29,29 @@
 
 namespace na {
 
+/* workgroup sizes: one lane per session or record; commit_hash, one per byte of h */
+constexpr uint32_t KDF_BLOCK = 64, KDF_COMMIT_BLOCK = 256;
+
 struct KdfArgs {
     int hash_id;
     const uint8_t *keys;
     const uint8_t *data;
     uint8_t *out1, *out2;
-    uint32_t key_len, data_len, out1_len, out2_len, n;
+    uint32_t hlen, key_len, data_len, out1_len, out2_len, n;
 };
 
-/* noise_hashstate_hkdf (hashstate.c:476-516), one lane per session */
-__global__ __launch_bounds__(64) void hkdf_batch(KdfArgs a)
+/* kdf_hkdf (hasher.h), one lane per session; the outputs are stored truncated
+   to out1_len and out2_len (hashstate.c:496-497 allows up to the hash's length) */
+__global__ __launch_bounds__(KDF_BLOCK) void hkdf_batch(KdfArgs a)
 {
-    const uint32_t i = blockIdx.x * 64u + threadIdx.x;
+    const uint32_t i = blockIdx.x * KDF_BLOCK + threadIdx.x;
     if (i >= a.n) return;
     const uint8_t *key = a.keys + (size_t)i * a.key_len;
     const uint8_t *data = a.data ? a.data + (size_t)i * a.data_len : nullptr;
-    uint8_t tk[64], t[65];
-    const uint32_t hl = (a.hash_id == H_SHA512 || a.hash_id == H_BLAKE2B) ? 64 : 32;
-    kdf_hmac(a.hash_id, key, a.key_len, data, a.data_len, nullptr, 0, tk);
-    const uint8_t one = 0x01, two = 0x02;
-    kdf_hmac(a.hash_id, tk, hl, &one, 1, nullptr, 0, t);
-    for (uint32_t j = 0; j < a.out1_len; ++j) a.out1[(size_t)i * a.out1_len + j] = t[j];
-    kdf_hmac(a.hash_id, tk, hl, t, hl, &two, 1, t);
-    for (uint32_t j = 0; j < a.out2_len; ++j) a.out2[(size_t)i * a.out2_len + j] = t[j];
-    for (int j = 0; j < 64; ++j) tk[j] = 0; /* hashstate.c:512-513 cleans its temporaries */
+    uint8_t o1[64], o2[64];
+    kdf_hkdf(a.hash_id, a.hlen, key, a.key_len, data, a.data_len, o1, o2);
+    for (uint32_t j = 0; j < a.out1_len; ++j) a.out1[(size_t)i * a.out1_len + j] = o1[j];
+    for (uint32_t j = 0; j < a.out2_len; ++j) a.out2[(size_t)i * a.out2_len + j] = o2[j];
 }
 
 /* ------------------------------------------------ handshake-payload MixHash
@@ -67,26 +70,22 @@ struct MixHashArgs {
     int use_out_off;
 };
 
-__global__ __launch_bounds__(64) void mix_hash_batch(MixHashArgs a)
+__global__ __launch_bounds__(KDF_BLOCK) void mix_hash_batch(MixHashArgs a)
 {
-    const uint32_t i = blockIdx.x * 64u + threadIdx.x;
+    const uint32_t i = blockIdx.x * KDF_BLOCK + threadIdx.x;
     if (i >= a.n) return;
     const RecDesc d = a.recs[i];
-    Hasher H;
-    H.init(a.hash_id);
     uint8_t h[64];
-    for (uint32_t j = 0; j < a.hlen; ++j) h[j] = a.h_in[(size_t)i * a.hlen + j];
-    H.update(h, a.hlen);
-    H.update(a.base + (a.use_out_off ? d.out_off : d.in_off), d.len + 16);
-    H.final(h);
-    for (uint32_t j = 0; j < a.hlen; ++j) a.h_out[(size_t)i * a.hlen + j] = h[j];
+    load_row(h, a.h_in, i, a.hlen);
+    kdf_mix_hash(a.hash_id, a.hlen, h, a.base + (a.use_out_off ? d.out_off : d.in_off), d.len + 16);
+    store_row(a.h_out, i, a.hlen, h);
 }
 
 /* decrypt_and_hash keeps the new hash only when the tag verified (:436-443) */
-__global__ __launch_bounds__(256) void commit_hash(uint8_t *h, const uint8_t *h_new,
-                                                   const uint8_t *status, uint32_t hlen, uint32_t n)
+__global__ __launch_bounds__(KDF_COMMIT_BLOCK) void commit_hash(uint8_t *h, const uint8_t *h_new,
+                                                                const uint8_t *status, uint32_t hlen, uint32_t n)
 {
-    const uint64_t t = (uint64_t)blockIdx.x * 256u + threadIdx.x;
+    const uint64_t t = (uint64_t)blockIdx.x * KDF_COMMIT_BLOCK + threadIdx.x;
     if (t >= (uint64_t)n * hlen) return;
     if (status[t / hlen] == 0) h[t] = h_new[t];
 }

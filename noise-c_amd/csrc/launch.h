@@ -2,7 +2,9 @@
  * launch.h — the kernel launchers of each translation unit, as seen by the
  * C-ABI layer (aead_api.hip).  launch_chacha.hip holds the ChaChaPoly
  * kernels, launch_aes.hip the AES-GCM ones; they compile in parallel.  Each
- * launches the Plan that dispatch.h made of a job.
+ * launches the Plan that dispatch.h made of a job.  Also what every device
+ * unit outside the AEAD kernels shares: the one-lane-per-item launch
+ * (launch_items) and the allocation of a device object (DevArena).
  * Internal (hidden visibility); the public ABI is include/noise_aead_hip.h.
  */
 #pragma once
@@ -32,6 +34,48 @@ int launch(const Plan &p, void (*fn)(A...), hipStream_t s, const A &...args)
     hipLaunchKernelGGL(fn, dim3(p.grid), dim3(p.block), 0, s, args...);
     return hip_rc(hipGetLastError());
 }
+
+/* The other launch: one lane per item, `items` of them in workgroups of
+   `block` lanes; the grid is counted in 64 bits, so an item count near 2^32
+   does not wrap.  Whether zero items launch at all is the caller's to say. */
+template <typename... P, typename... A>
+int launch_items(void (*fn)(P...), uint64_t items, uint32_t block, hipStream_t s, const A &...args)
+{
+    hipLaunchKernelGGL(fn, dim3((uint32_t)((items + block - 1) / block)), dim3(block), 0, s, args...);
+    return hip_rc(hipGetLastError());
+}
+
+/* The one device allocation of a device object (handshake.hip,
+   transport.hip).  carve() lays the parts out one after another, each padded
+   to `align` (a power of two); alloc() makes the block, at() gives a part.
+   What it holds is key material: zero() clears it on a stream before first
+   use, and release() is the only way it goes. */
+struct DevArena {
+    uint8_t *mem;
+    size_t bytes, align;
+
+    size_t carve(size_t part)
+    {
+        const size_t at = bytes;
+        bytes += (part + align - 1) & ~(align - 1);
+        return at;
+    }
+    bool alloc() { return hipMalloc((void **)&mem, bytes) == hipSuccess; }
+    template <typename T = uint8_t>
+    T *at(size_t off) const { return (T *)(mem + off); }
+    int zero(hipStream_t s) const { return hip_rc(hipMemsetAsync(mem, 0, bytes, s)); }
+    /* Work of the object may still be in flight on the caller's streams, so
+       wait, then zero, then free; the first error wins. */
+    int release()
+    {
+        if (!mem) return NOISE_ERROR_NONE;
+        const int rc = hip_rc(hipDeviceSynchronize());
+        const int rc2 = hip_rc(hipMemset(mem, 0, bytes));
+        const int rc3 = hip_rc(hipFree(mem));
+        mem = nullptr;
+        return rc ? rc : (rc2 ? rc2 : rc3);
+    }
+};
 
 /* The arguments of a plan's kernel: a and b the (seal and open) jobs of a
    uniform or duplex plan, r the job of a ragged one, r and ro the seal and

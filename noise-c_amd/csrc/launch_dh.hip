@@ -42,12 +42,7 @@ int run_dh(int dh_id, const uint8_t *d_priv, uint64_t priv_stride, bool has_pub,
     const int rc = check_dh(dh_id, d_priv, priv_stride, has_pub, d_pub, pub_stride, n, d_out);
     if (rc || !n) return rc;
     const DhArgs a = {d_priv, d_pub, d_out, priv_stride, pub_stride, n};
-    const dim3 grid((uint32_t)(((uint64_t)n + DH_BLOCK - 1) / DH_BLOCK)), block(DH_BLOCK);
-    if (has_pub)
-        hipLaunchKernelGGL(x25519_batch<false>, grid, block, 0, (hipStream_t)stream, a);
-    else
-        hipLaunchKernelGGL(x25519_batch<true>, grid, block, 0, (hipStream_t)stream, a);
-    return hip_rc(hipGetLastError());
+    return launch_items(has_pub ? x25519_batch<false> : x25519_batch<true>, n, DH_BLOCK, (hipStream_t)stream, a);
 }
 
 } // namespace

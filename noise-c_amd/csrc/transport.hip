@@ -5,9 +5,14 @@
  * The object holds, for n sessions, a send and a receive key context and a
  * send and a receive nonce on the device, and what a call needs: descriptors
  * and statuses for max_frames records, per-session counts and bases, scan
- * scratch.  A call is handed every session's bytes in the echo wire format
- * and does per session what noise_wire_seal / _open / _echo do (wire.c), with
- * nothing coming back to the host:
+ * scratch — all of it one DevArena (launch.h), zeroed before use and zeroed
+ * again before it is freed.  The per-session and per-entry kernels go out
+ * through launch_items (launch.h); a descriptor nothing may be done for is
+ * refused_rec() (aead_kernels.h).
+ *
+ * A call is handed every session's bytes in the echo wire format and does per
+ * session what noise_wire_seal / _open / _echo do (wire.c), with nothing
+ * coming back to the host:
  *   tr_count   one lane per session walks its headers (transport_plan.h
  *              tr_walk, no budget) and leaves its frame count;
  *   the scan   rocprim's exclusive scan of the 64-bit counts: the number of
@@ -59,7 +64,7 @@ namespace {
 
 constexpr uint32_t TR_BLOCK = 64;
 constexpr uint32_t TR_WIDE_BLOCK = 256;
-constexpr uint32_t TR_REFUSED_LEN = MAX_RECORD_LEN + 1; /* aead_kernels.h reject_len */
+constexpr size_t TR_ALIGN = 256; /* of the parts of the object's device allocation */
 
 enum TrMode : uint32_t { TR_SEAL = 0, TR_OPEN = 1, TR_ECHO = 2 };
 
@@ -94,13 +99,6 @@ TR_DEV uint64_t tr_start_nonce(const TrArgs &a, uint32_t i)
     return a.send[i] > a.recv[i] ? a.send[i] : a.recv[i];
 }
 
-TR_DEV RecDesc tr_refused()
-{
-    RecDesc d = {};
-    d.len = TR_REFUSED_LEN;
-    return d;
-}
-
 __global__ __launch_bounds__(TR_BLOCK) void tr_count(TrArgs a)
 {
     const uint32_t j = blockIdx.x * TR_BLOCK + threadIdx.x;
@@ -130,7 +128,7 @@ __global__ __launch_bounds__(TR_BLOCK) void tr_build(TrArgs a)
     const uint64_t t = (uint64_t)blockIdx.x * TR_BLOCK + threadIdx.x;
     const uint64_t all = a.base[a.m - 1] + a.count[a.m - 1];
     const uint64_t total = all < a.max_frames ? all : a.max_frames;
-    if (t >= total && t < a.max_frames) a.recs[t] = tr_refused();
+    if (t >= total && t < a.max_frames) a.recs[t] = refused_rec();
     if (t >= a.m) return;
     const uint32_t j = (uint32_t)t;
     uint32_t i;
@@ -166,7 +164,7 @@ __global__ __launch_bounds__(TR_BLOCK) void tr_commit(TrArgs a)
     if (echo) {
         const uint64_t all = a.base[a.m - 1] + a.count[a.m - 1];
         const uint64_t total = all < a.max_frames ? all : a.max_frames;
-        if (t >= total && t < a.max_frames) a.seal_recs[t] = tr_refused();
+        if (t >= total && t < a.max_frames) a.seal_recs[t] = refused_rec();
     }
     if (t >= a.m) return;
     const uint32_t j = (uint32_t)t;
@@ -184,7 +182,7 @@ __global__ __launch_bounds__(TR_BLOCK) void tr_commit(TrArgs a)
     if (echo) {
         const uint64_t send = a.send[i];
         for (uint32_t k = 0; k < frames; ++k) {
-            RecDesc d = tr_refused();
+            RecDesc d = refused_rec();
             if (k < prefix) {
                 d = a.recs[base + k];
                 d.nonce = send + k;
@@ -276,23 +274,14 @@ __global__ __launch_bounds__(TR_WIDE_BLOCK) void tr_clear_wide(TrKeyArgs a)
     for (uint64_t w = threadIdx.x, words = a.ctx_bytes / 16; w < words; w += TR_WIDE_BLOCK) c[w] = make_uint4(0, 0, 0, 0);
 }
 
-size_t carve(size_t &off, size_t bytes)
-{
-    const size_t at = off;
-    off += (bytes + 255) & ~(size_t)255;
-    return at;
-}
-
 } // namespace
 
 struct NoiseAeadDevTransport {
     int cipher_id, role;
     uint32_t n, max_frames;
     size_t ctx_bytes;
-    /* one device allocation, carved */
-    uint8_t *mem;
-    size_t mem_bytes;
-    uint8_t *ctx;             /* n send contexts, then n receive contexts */
+    DevArena dev;             /* the one device allocation; the pointers below are its parts */
+    uint8_t *ctx;            /* n send contexts, then n receive contexts */
     uint64_t *send, *recv, *count, *base;
     uint32_t *frames, *consumed;
     int32_t *stop;
@@ -328,14 +317,10 @@ int run(Tr *tr, TrMode mode, const uint32_t *slots, uint32_t m, uint32_t cap, ui
     }
     const TrArgs a = {d_wire, d_off, d_len, d_result, tr->send, tr->recv, tr->count, tr->base, tr->frames, tr->consumed,
                       tr->stop, tr->recs, tr->seal_recs, tr->status, tr->ctx_bytes, cap, tr->n, mode, slots, tr->keyed, m};
-    const uint32_t most = m > cap ? m : cap;
-    const dim3 per_session((m + TR_BLOCK - 1) / TR_BLOCK), padded((uint32_t)(((uint64_t)most + TR_BLOCK - 1) / TR_BLOCK));
-    hipLaunchKernelGGL(tr_count, per_session, dim3(TR_BLOCK), 0, s, a);
-    int rc = hip_rc(hipGetLastError());
+    const uint32_t most = m > cap ? m : cap; /* tr_build and an echo's tr_commit also pad the descriptors up to the cap */
+    int rc = launch_items(tr_count, m, TR_BLOCK, s, a);
     if (!rc) rc = scan_counts(tr, tr->scan_tmp, bytes, m, s);
-    if (rc) return rc;
-    hipLaunchKernelGGL(tr_build, padded, dim3(TR_BLOCK), 0, s, a);
-    rc = hip_rc(hipGetLastError());
+    if (!rc) rc = launch_items(tr_build, most, TR_BLOCK, s, a);
     if (rc) return rc;
     NoiseAeadRagged job = {};
     job.ctx_base = tr->ctx;
@@ -347,8 +332,7 @@ int run(Tr *tr, TrMode mode, const uint32_t *slots, uint32_t m, uint32_t cap, ui
     if (mode == TR_SEAL) return noise_aead_dev_seal_ragged(tr->cipher_id, &job, s);
     rc = noise_aead_dev_open_ragged(tr->cipher_id, &job, s);
     if (rc) return rc;
-    hipLaunchKernelGGL(tr_commit, mode == TR_ECHO ? padded : per_session, dim3(TR_BLOCK), 0, s, a);
-    rc = hip_rc(hipGetLastError());
+    rc = launch_items(tr_commit, mode == TR_ECHO ? most : m, TR_BLOCK, s, a);
     if (rc || mode == TR_OPEN) return rc;
     job.recs = (const NoiseAeadRecord *)tr->seal_recs;
     job.status = nullptr;
@@ -394,24 +378,23 @@ int make(Tr **out, int cipher_id, int role, uint32_t n, uint32_t max_frames, hip
             return rc;
         }
         const size_t ns = n, nf = max_frames;
-        size_t off = 0;
-        const size_t o_ctx = carve(off, 2 * ns * tr->ctx_bytes), o_send = carve(off, ns * 8), o_recv = carve(off, ns * 8);
-        const size_t o_count = carve(off, ns * 8), o_base = carve(off, ns * 8), o_frames = carve(off, ns * 4);
-        const size_t o_consumed = carve(off, ns * 4), o_stop = carve(off, ns * 4);
-        const size_t o_recs = carve(off, nf * sizeof(RecDesc)), o_seal = carve(off, nf * sizeof(RecDesc));
-        const size_t o_status = carve(off, nf), o_keyed = carve(off, ns), o_scan = carve(off, tr->scan_bytes);
-        if (hipMalloc((void **)&tr->mem, off) != hipSuccess) {
+        DevArena &d = tr->dev;
+        d.align = TR_ALIGN;
+        const size_t o_ctx = d.carve(2 * ns * tr->ctx_bytes), o_send = d.carve(ns * 8), o_recv = d.carve(ns * 8);
+        const size_t o_count = d.carve(ns * 8), o_base = d.carve(ns * 8), o_frames = d.carve(ns * 4);
+        const size_t o_consumed = d.carve(ns * 4), o_stop = d.carve(ns * 4);
+        const size_t o_recs = d.carve(nf * sizeof(RecDesc)), o_seal = d.carve(nf * sizeof(RecDesc));
+        const size_t o_status = d.carve(nf), o_keyed = d.carve(ns), o_scan = d.carve(tr->scan_bytes);
+        if (!d.alloc()) {
             delete tr;
             return NOISE_ERROR_NO_MEMORY;
         }
-        tr->mem_bytes = off;
-        uint8_t *m = tr->mem;
-        tr->ctx = m + o_ctx; tr->send = (uint64_t *)(m + o_send); tr->recv = (uint64_t *)(m + o_recv);
-        tr->count = (uint64_t *)(m + o_count); tr->base = (uint64_t *)(m + o_base);
-        tr->frames = (uint32_t *)(m + o_frames); tr->consumed = (uint32_t *)(m + o_consumed);
-        tr->stop = (int32_t *)(m + o_stop); tr->recs = (RecDesc *)(m + o_recs); tr->seal_recs = (RecDesc *)(m + o_seal);
-        tr->status = m + o_status; tr->keyed = m + o_keyed; tr->scan_tmp = m + o_scan;
-        rc = hip_rc(hipMemsetAsync(tr->mem, 0, tr->mem_bytes, s));
+        tr->ctx = d.at(o_ctx); tr->send = d.at<uint64_t>(o_send); tr->recv = d.at<uint64_t>(o_recv);
+        tr->count = d.at<uint64_t>(o_count); tr->base = d.at<uint64_t>(o_base);
+        tr->frames = d.at<uint32_t>(o_frames); tr->consumed = d.at<uint32_t>(o_consumed);
+        tr->stop = d.at<int32_t>(o_stop); tr->recs = d.at<RecDesc>(o_recs); tr->seal_recs = d.at<RecDesc>(o_seal);
+        tr->status = d.at(o_status); tr->keyed = d.at(o_keyed); tr->scan_tmp = d.at(o_scan);
+        rc = d.zero(s);
         if (rc) {
             noise_aead_dev_transport_free(tr);
             return rc;
@@ -439,12 +422,9 @@ TrKeyArgs key_args(const Tr *tr, const uint32_t *d_slots, uint32_t m)
 /* zero and un-key (set: after gcm_prepare_slots, the failed entries only; the rest are marked keyed) */
 int launch_clear(const Tr *tr, const TrKeyArgs &a, hipStream_t s)
 {
-    if (tr->ctx_bytes <= 64)
-        hipLaunchKernelGGL(tr_clear_lane, dim3((a.m + TR_BLOCK - 1) / TR_BLOCK), dim3(TR_BLOCK), 0, s, a);
-    else if (a.m > 0x7fffffffu / 2) /* 2m workgroups in one grid */
-        return NOISE_ERROR_INVALID_PARAM;
-    else
-        hipLaunchKernelGGL(tr_clear_wide, dim3(2 * a.m), dim3(TR_WIDE_BLOCK), 0, s, a);
+    if (tr->ctx_bytes <= 64) return launch_items(tr_clear_lane, a.m, TR_BLOCK, s, a);
+    if (a.m > 0x7fffffffu / 2) return NOISE_ERROR_INVALID_PARAM; /* 2m workgroups in one grid */
+    hipLaunchKernelGGL(tr_clear_wide, dim3(2 * a.m), dim3(TR_WIDE_BLOCK), 0, s, a);
     return hip_rc(hipGetLastError());
 }
 
@@ -497,10 +477,7 @@ int noise_aead_dev_transport_set_keys(NoiseAeadDevTransport *tr, const uint32_t 
     a.k2 = d_k2;
     a.status = d_status;
     a.set = 1;
-    if (tr->cipher_id == NOISE_CIPHER_CHACHAPOLY) {
-        hipLaunchKernelGGL(tr_set_keys, dim3((m + TR_BLOCK - 1) / TR_BLOCK), dim3(TR_BLOCK), 0, s, a);
-        return hip_rc(hipGetLastError());
-    }
+    if (tr->cipher_id == NOISE_CIPHER_CHACHAPOLY) return launch_items(tr_set_keys, m, TR_BLOCK, s, a);
     rc = aes_prepare_slots(d_slots, m, tr->n, d_k1, d_k2, d_status, a.initiator != 0, tr->ctx, s);
     return rc ? rc : launch_clear(tr, a, s);
 }
@@ -527,14 +504,7 @@ const uint8_t *noise_aead_debug_transport_ctx(const NoiseAeadDevTransport *tr, i
 int noise_aead_dev_transport_free(NoiseAeadDevTransport *tr)
 {
     if (!tr) return NOISE_ERROR_INVALID_PARAM;
-    int rc = NOISE_ERROR_NONE;
-    if (tr->mem) {
-        /* work of this object may still be in flight on the caller's streams */
-        rc = hip_rc(hipDeviceSynchronize());
-        const int rc2 = hip_rc(hipMemset(tr->mem, 0, tr->mem_bytes));
-        const int rc3 = hip_rc(hipFree(tr->mem));
-        rc = rc ? rc : (rc2 ? rc2 : rc3);
-    }
+    const int rc = tr->dev.release();
     memset((void *)tr, 0, sizeof(*tr));
     delete tr;
     return rc;

@@ -1,8 +1,8 @@
 """The C-ABI library: it loads, exports every symbol include/*.h declares, its
 structs have the documented layout, and the CipherState front end's host-side
 rules (validation, nonce bookkeeping, error codes — src/protocol/cipherstate.c)
-hold.  Nothing here launches a kernel: paths that would reach the GPU are not
-called on CPU."""
+hold.  Nothing here launches a kernel, with or without a GPU in the machine:
+every job handed to a device entry point is one it refuses, or is empty."""
 import ctypes as C
 import glob
 import os
@@ -202,7 +202,12 @@ def test_default_lane_policy(aead_built):
 def test_device_api_argument_rules(aead_built):
     """The device-resident entry points reject bad jobs before any HIP call
     (dispatch.h check_uniform / check_ragged), so these run without a GPU.
-    The pointers are never dereferenced: every case fails validation."""
+    Every case here is refused or has n_records == 0, and must be: the
+    pointers are invented, and an accepted job is launched — where there is
+    a GPU, a kernel would run on addresses nobody allocated.  The accepted
+    jobs of the same rules (the sound job, the interleaved layouts) are
+    checked where nothing is launched, in asan/dispatch_check.cpp
+    (check_argument_rules; tests/test_dispatch_host.py)."""
     A = aead_built
     fake = 1 << 20  # aligned, non-null, never touched
     ok = dict(ctx=fake, nonce_base=fake, inp=fake, out=fake + (1 << 30), in_stride=1408,
@@ -232,13 +237,12 @@ def test_device_api_argument_rules(aead_built):
             assert A.dev_uniform(open_, cid, **{**ok, "out": fake + 4 * 1408 - 16}) \
                 == A.ERROR_INVALID_PARAM
             # one stride, input and output slots alternating in one buffer
-            # (ADVICE r3): accepted while no two records meet, refused once
-            # an output record reaches into an input record
+            # (ADVICE r3): refused once an output record reaches into an
+            # input record — for an open that holds the tag, 1408 bytes up
+            # already.  The layouts that are accepted: dispatch_check.
             inter = {**ok, "in_stride": 2848, "out_stride": 2848}
-            assert A.dev_uniform(open_, cid, **{**inter, "out": fake + 1424}) != A.ERROR_INVALID_PARAM
-            assert A.dev_uniform(open_, cid, **{**inter, "out": fake - 1424}) != A.ERROR_INVALID_PARAM
-            assert A.dev_uniform(open_, cid, **{**inter, "out": fake + 1408}) \
-                == (A.ERROR_INVALID_PARAM if open_ else A.dev_uniform(open_, cid, **{**inter, "out": fake + 1424}))
+            if open_:
+                assert A.dev_uniform(open_, cid, **{**inter, "out": fake + 1408}) == A.ERROR_INVALID_PARAM
             assert A.dev_uniform(open_, cid, **{**inter, "out": fake + 1000}) == A.ERROR_INVALID_PARAM
 
 
