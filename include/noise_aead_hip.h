@@ -513,7 +513,9 @@ int noise_aead_dev_dh_public(int dh_id, const uint8_t *d_priv, uint64_t priv_str
  * payload for all); any other key stride must be at least 32, any other
  * prologue, payload or message stride at least the length; an output stride
  * must be at least the bytes written (never 0).  Nothing needs alignment.
- * Payload and message lengths are uniform over the batch.
+ * Payload and message lengths are uniform over the batch in
+ * _write_message / _read_message; the _ragged calls below take both the place
+ * and the length per session.
  *
  * _new consumes the prologue, the PSK and the remote static public keys; the
  * private keys (d_local_static_priv, d_local_ephemeral_priv) are read by
@@ -557,9 +559,46 @@ int noise_aead_dev_dh_public(int dh_id, const uint8_t *d_priv, uint64_t priv_str
  * n == 0 gives a valid object whose calls check the state and the lengths,
  * launch nothing and advance the action.
  *
+ * Per-session offsets and lengths: _write_message_ragged and
+ * _read_message_ragged are _write_message and _read_message done for session
+ * i with its own place and length — the same tokens, bytes, nonce and status
+ * rules.  Session i's payload is the d_payload_len[i] bytes at d_payload +
+ * d_payload_off[i], its message lies at d_msg + d_msg_off[i]; the offset and
+ * length arrays are device arrays of n entries, as in section 9.  Nothing
+ * needs alignment and the offsets may come in any order.  On write
+ * d_payload, d_payload_off and d_payload_len may be NULL all three together:
+ * every payload is then empty.  Write sets d_msg_len[i] = d_payload_len[i] +
+ * overhead, read sets d_payload_len[i] = d_msg_len[i] - overhead; either is
+ * 0 for every session whose status is non-zero after the call.  The spans
+ * are the caller's guarantee, unchecked, as for the ragged calls of section
+ * 4 and the transport: each output span has room (payload length + overhead
+ * on write, message length - overhead on read) and no output span meets any
+ * span of the same call.  _get_action and _overhead stay host values, the
+ * action advances for the batch regardless, and uniform and ragged calls may
+ * be mixed freely within one handshake.  What the uniform calls refuse for
+ * the whole batch as NOISE_ERROR_INVALID_LENGTH becomes status 4 of the one
+ * session: a write with payload length + overhead > 65535, a read with
+ * message length < overhead or > 65535.  The length is checked before any
+ * token (the reference gives the same code at the token it reaches,
+ * :1454, :1489, :1320-1324, symmetricstate.c:419-422, and is
+ * NOISE_ACTION_FAILED afterwards), so such a session is a failed session
+ * from the start of the call.  The order of causes within one call for one
+ * session: already failed, then the length (4), then a null ephemeral (3),
+ * then a tag (1).  Checked on the host before any launch, in this order:
+ *   - hs == NULL: NOISE_ERROR_INVALID_PARAM;
+ *   - the wrong call for _get_action: NOISE_ERROR_INVALID_STATE;
+ *   - n == 0: NOISE_ERROR_NONE, nothing is launched, the action advances;
+ *   - a NULL pointer other than the write's payload triple all together, or
+ *     only part of that triple NULL: NOISE_ERROR_INVALID_PARAM;
+ *   - the output length array [out, out + 4n) meeting an input offset array
+ *     [p, p + 8n) or the input length array [p, p + 4n):
+ *     NOISE_ERROR_INVALID_PARAM.
+ * A refused call leaves the object as it was.
+ *
  * Per-session failures stay on the device: status[i] is 0 (ok), 1 (a tag
- * failed: NOISE_ERROR_MAC_FAILURE) or 3 (the received ephemeral was all-zero:
- * NOISE_ERROR_INVALID_PUBLIC_KEY, :1464-1470); 2 stays reserved as in the
+ * failed: NOISE_ERROR_MAC_FAILURE), 3 (the received ephemeral was all-zero:
+ * NOISE_ERROR_INVALID_PUBLIC_KEY, :1464-1470) or 4 (a length a ragged call
+ * refuses: NOISE_ERROR_INVALID_LENGTH); 2 stays reserved as in the
  * ragged calls.  The first failure is sticky.  A failed session writes only
  * inside its own slots and its later output bytes are unspecified; its opens
  * never write unauthenticated plaintext (the verify-first order) and nothing
@@ -594,6 +633,14 @@ int noise_aead_dev_handshake_write_message(NoiseAeadDevHandshake *hs, const uint
 int noise_aead_dev_handshake_read_message(NoiseAeadDevHandshake *hs, const uint8_t *d_msg, uint64_t msg_stride,
                                           uint32_t msg_len, uint8_t *d_payload, uint64_t payload_stride,
                                           void *stream);
+int noise_aead_dev_handshake_write_message_ragged(NoiseAeadDevHandshake *hs, const uint8_t *d_payload,
+                                                  const uint64_t *d_payload_off, const uint32_t *d_payload_len,
+                                                  uint8_t *d_msg, const uint64_t *d_msg_off,
+                                                  uint32_t *d_msg_len /* out */, void *stream);
+int noise_aead_dev_handshake_read_message_ragged(NoiseAeadDevHandshake *hs, const uint8_t *d_msg,
+                                                 const uint64_t *d_msg_off, const uint32_t *d_msg_len,
+                                                 uint8_t *d_payload, const uint64_t *d_payload_off,
+                                                 uint32_t *d_payload_len /* out */, void *stream);
 int noise_aead_dev_handshake_split(NoiseAeadDevHandshake *hs, uint8_t *d_k1, uint8_t *d_k2,
                                    uint8_t *d_handshake_hash, void *stream);
 const uint8_t *noise_aead_dev_handshake_status(const NoiseAeadDevHandshake *hs);

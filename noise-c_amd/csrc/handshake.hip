@@ -15,18 +15,25 @@
  * of it is restated here:
  *   hs_init       h = the protocol name padded or hashed, ck = h
  *                 (symmetricstate.c:97-108);
- *   hs_mix_hash   h = HASH(h || bytes) over strided bytes, with an optional
- *                 copy of the bytes (the pass-through of an unkeyed
- *                 encrypt/decrypt_and_hash, an `e` into or out of a message),
- *                 and, after an open, the sticky status merge: a session
- *                 whose tag failed keeps its h and takes status 1;
+ *   hs_mix_hash   h = HASH(h || bytes), with an optional copy of the bytes (the
+ *                 pass-through of an unkeyed encrypt/decrypt_and_hash, an `e`
+ *                 into or out of a message), and, after an open, the sticky
+ *                 status merge: a session whose tag failed keeps its h and
+ *                 takes status 1.  Session i's bytes lie i * stride from the
+ *                 base or at a per-session offset (HsRows) and have a fixed
+ *                 or a per-session length (HsLens): the uniform and the
+ *                 ragged message calls run this one body.  As the payload
+ *                 step of a ragged call it also writes the out-length array;
+ *   hs_check_len  the front step of a ragged call: a session whose length
+ *                 hs_session_len (handshake_plan.h) refuses takes status 4
+ *                 before any token;
  *   hs_mix_key    ck, k = HKDF(ck, ikm) in place, zeroing the shared secret
  *                 it consumed (noise_clean(shared), handshakestate.c:1136);
  *                 for the PSK start-up step ck, temp = HKDF(ck, psk) and
  *                 MixHash(temp) (:833-842);
  *   hs_null_check the all-zero received ephemeral (:1464-1470) -> status 3;
- *   hs_build_recs the NoiseAeadRecord array of one AEAD step from (stride,
- *                 length, nonce, i * ctx_bytes, i * hash_len); a failed
+ *   hs_build_recs the NoiseAeadRecord array of one AEAD step from (rows,
+ *                 lengths, nonce, i * ctx_bytes, i * hash_len); a failed
  *                 session gets the length the ragged kernels refuse (REFUSED_LEN,
  *                 aead_kernels.h), so nothing more is sealed or opened for it;
  *   hs_split      k1, k2 = HKDF(ck, ""), zeros for a failed session, and h.
@@ -75,36 +82,83 @@ __global__ __launch_bounds__(HS_BLOCK) void hs_init(InitArgs a)
     for (uint32_t j = 0; j < a.hl; ++j) a.h[(size_t)i * a.hl + j] = a.ck[(size_t)i * a.hl + j] = h[j]; /* one pass, two rows */
 }
 
-struct MixHashStrided {
-    int hash_id;
-    uint32_t hl, n, len;
-    uint8_t *h;
-    const uint8_t *src;   /* session i hashes src + i * src_stride, len bytes */
-    uint64_t src_stride;
-    uint8_t *dst;         /* not NULL: the bytes are also copied to dst + i * dst_stride */
-    uint64_t dst_stride;
-    uint8_t *status;      /* the sticky statuses: a failed session does nothing */
-    const uint8_t *step;  /* not NULL: the statuses of the open just done */
+/* Where session i's bytes lie from a base pointer: i * stride (0: one value
+   for all), or off[i] — any order, any alignment.  The ragged calls put the
+   token's offset inside the message into the base pointer. */
+struct HsRows {
+    const uint64_t *off;
+    uint64_t stride;
+    __device__ __forceinline__ uint64_t at(uint32_t i) const { return off ? off[i] : (uint64_t)i * stride; }
 };
 
-__global__ __launch_bounds__(HS_BLOCK) void hs_mix_hash(MixHashStrided a)
+/* Session i's length in a step: `fixed` (a key token, a uniform call), or
+   from the per-session array of a ragged call through hs_session_len
+   (handshake_plan.h), the one statement of the length rule. */
+struct HsLens {
+    const uint32_t *per; /* write: payload lengths; read: message lengths */
+    uint32_t fixed, overhead, write;
+    __device__ __forceinline__ bool refused(uint32_t i) const
+    {
+        return hs_session_len(overhead, per ? per[i] : fixed, write).refused;
+    }
+    __device__ __forceinline__ uint32_t payload(uint32_t i) const
+    {
+        if (!per) return fixed;
+        return write ? per[i] : hs_session_len(overhead, per[i], false).other;
+    }
+    /* what the call reports: the message length of a write, the payload length of a read */
+    __device__ __forceinline__ uint32_t reported(uint32_t i) const
+    {
+        const uint32_t p = payload(i);
+        return write ? hs_session_len(overhead, p, true).other : p;
+    }
+};
+
+struct MixHashArgs {
+    int hash_id;
+    uint32_t hl, n;
+    uint8_t *h;
+    const uint8_t *src;   /* session i hashes src + src_rows.at(i), lens.payload(i) + extra bytes */
+    HsRows src_rows;
+    uint8_t *dst;         /* not NULL: the bytes are also copied to dst + dst_rows.at(i) */
+    HsRows dst_rows;
+    HsLens lens;
+    uint32_t extra;       /* the tag after a sealed or opened payload */
+    uint8_t *status;      /* the sticky statuses: a failed session does nothing */
+    const uint8_t *step;  /* not NULL: the statuses of the open just done */
+    uint32_t *out_len;    /* not NULL (the payload step of a ragged call): lens.reported(i), 0 for a failed session */
+};
+
+__global__ __launch_bounds__(HS_BLOCK) void hs_mix_hash(MixHashArgs a)
 {
     const uint32_t i = blockIdx.x * HS_BLOCK + threadIdx.x;
     if (i >= a.n) return;
-    if (a.status[i]) return;
-    if (a.step && a.step[i]) { /* the reference leaves h as it was (symmetricstate.c:436-443) */
-        a.status[i] = HS_STATUS_MAC;
+    uint8_t st = a.status[i];
+    if (!st && a.step && a.step[i]) /* the reference leaves h as it was (symmetricstate.c:436-443) */
+        a.status[i] = st = HS_STATUS_MAC;
+    if (st) {
+        if (a.out_len) a.out_len[i] = 0;
         return;
     }
-    const uint8_t *src = a.src + (uint64_t)i * a.src_stride;
+    const uint32_t len = a.lens.payload(i) + a.extra;
+    const uint8_t *src = a.src + a.src_rows.at(i);
     if (a.dst) {
-        uint8_t *dst = a.dst + (uint64_t)i * a.dst_stride;
-        for (uint32_t j = 0; j < a.len; ++j) dst[j] = src[j];
+        uint8_t *dst = a.dst + a.dst_rows.at(i);
+        for (uint32_t j = 0; j < len; ++j) dst[j] = src[j];
     }
     uint8_t h[64];
     load_row(h, a.h, i, a.hl);
-    kdf_mix_hash(a.hash_id, a.hl, h, src, a.len);
+    kdf_mix_hash(a.hash_id, a.hl, h, src, len);
     store_row(a.h, i, a.hl, h);
+    if (a.out_len) a.out_len[i] = a.lens.reported(i);
+}
+
+/* the front step of a ragged call: the length rule before any token */
+__global__ __launch_bounds__(HS_BLOCK) void hs_check_len(HsLens lens, uint8_t *status, uint32_t n)
+{
+    const uint32_t i = blockIdx.x * HS_BLOCK + threadIdx.x;
+    if (i >= n || status[i]) return;
+    if (lens.refused(i)) status[i] = HS_STATUS_LENGTH;
 }
 
 struct MixKeyArgs {
@@ -160,8 +214,10 @@ __global__ __launch_bounds__(HS_BLOCK) void hs_copy32(const uint8_t *src, uint64
 struct BuildRecs {
     RecDesc *recs;
     const uint8_t *status;
-    uint64_t in_stride, out_stride, nonce, ctx_bytes;
-    uint32_t len, hl, n;
+    HsRows in_rows, out_rows;
+    HsLens lens;
+    uint64_t nonce, ctx_bytes;
+    uint32_t hl, n;
 };
 
 __global__ __launch_bounds__(HS_BLOCK) void hs_build_recs(BuildRecs a)
@@ -169,12 +225,12 @@ __global__ __launch_bounds__(HS_BLOCK) void hs_build_recs(BuildRecs a)
     const uint32_t i = blockIdx.x * HS_BLOCK + threadIdx.x;
     if (i >= a.n) return;
     RecDesc d;
-    d.in_off = (uint64_t)i * a.in_stride;
-    d.out_off = (uint64_t)i * a.out_stride;
+    d.in_off = a.in_rows.at(i);
+    d.out_off = a.out_rows.at(i);
     d.nonce = a.nonce;
     d.ctx_off = (uint64_t)i * a.ctx_bytes;
     d.ad_off = (uint64_t)i * a.hl;
-    d.len = a.status[i] ? REFUSED_LEN : a.len;
+    d.len = a.status[i] ? REFUSED_LEN : a.lens.payload(i);
     d.ad_len = a.hl;
     a.recs[i] = d;
 }
@@ -230,13 +286,32 @@ const HsPattern &pattern_of(const Hs *hs) { return HS_PATTERNS[hs->name.pattern]
 
 HsMessage next_message(const Hs *hs) { return hs_message(pattern_of(hs), hs->role, hs->name.psk, hs->index, hs->keyed); }
 
-int mix_hash(Hs *hs, const uint8_t *src, uint64_t src_stride, uint32_t len, uint8_t *dst, uint64_t dst_stride,
-             const uint8_t *step, hipStream_t s)
+/* One side of a message call: where the sessions' bytes are */
+struct HsSpan {
+    uint8_t *base;
+    HsRows rows;
+    HsSpan from(uint64_t off) const { return {base + off, rows}; } /* a token's bytes inside a message */
+};
+
+HsSpan strided(const uint8_t *base, uint64_t stride) { return {(uint8_t *)base, {nullptr, stride}}; }
+
+HsLens fixed_len(uint32_t len) { return {nullptr, len, 0, 0}; }
+
+int mix_hash(Hs *hs, HsSpan src, HsLens lens, uint32_t extra, HsSpan dst, const uint8_t *step, uint32_t *out_len,
+             hipStream_t s)
 {
-    const MixHashStrided a = {hs->name.hash_id, hs->hl, hs->n, len, hs->h, src, src_stride, dst, dst_stride,
-                              hs->status, step};
+    const MixHashArgs a = {hs->name.hash_id, hs->hl, hs->n, hs->h, src.base, src.rows, dst.base, dst.rows,
+                           lens, extra, hs->status, step, out_len};
     return launch_items(hs_mix_hash, hs->n, HS_BLOCK, s, a);
 }
+
+/* MixHash of `len` bytes per session, with an optional copy */
+int mix_hash(Hs *hs, HsSpan src, uint32_t len, HsSpan dst, hipStream_t s)
+{
+    return mix_hash(hs, src, fixed_len(len), 0, dst, nullptr, nullptr, s);
+}
+
+const HsSpan NO_COPY = {nullptr, {nullptr, 0}};
 
 int mix_key(Hs *hs, const uint8_t *ikm, uint64_t ikm_stride, bool zero_ikm, bool psk, hipStream_t s)
 {
@@ -251,11 +326,10 @@ int mix_key(Hs *hs, const uint8_t *ikm, uint64_t ikm_stride, bool zero_ikm, bool
     return rc;
 }
 
-/* encrypt_and_hash / decrypt_and_hash of `len` bytes for every session once
-   a key is set: seal or open under AD = h, then h = HASH(h || CT || tag) —
-   after an open only where the tag verified */
-int aead_step(Hs *hs, bool open, const uint8_t *in, uint64_t in_stride, uint8_t *out, uint64_t out_stride,
-              uint32_t len, hipStream_t s)
+/* encrypt_and_hash / decrypt_and_hash of each session's lens.payload(i) bytes
+   once a key is set: seal or open under AD = h, then h = HASH(h || CT || tag)
+   — after an open only where the tag verified */
+int aead_step(Hs *hs, bool open, HsSpan in, HsSpan out, HsLens lens, uint32_t *out_len, hipStream_t s)
 {
     const int cipher = hs->name.cipher_id;
     int rc = NOISE_ERROR_NONE;
@@ -263,23 +337,25 @@ int aead_step(Hs *hs, bool open, const uint8_t *in, uint64_t in_stride, uint8_t 
         rc = noise_aead_dev_prepare(cipher, hs->k, hs->n, hs->ctx, s);
     hs->ctx_stale = false;
     if (rc) return rc;
-    const BuildRecs b = {hs->recs, hs->status, in_stride, out_stride, hs->nonce, hs->ctx_bytes, len, hs->hl, hs->n};
+    /* an empty payload may come without a pointer; the ragged job wants one */
+    if (!in.base) in = strided(hs->arena, 0);
+    if (!out.base) out = strided(hs->arena, 0);
+    const BuildRecs b = {hs->recs, hs->status, in.rows, out.rows, lens, hs->nonce, hs->ctx_bytes, hs->hl, hs->n};
     rc = launch_items(hs_build_recs, hs->n, HS_BLOCK, s, b);
     if (rc) return rc;
     NoiseAeadRagged job = {};
     job.ctx_base = cipher == NOISE_CIPHER_AESGCM ? hs->ctx : hs->k;
     job.recs = (const NoiseAeadRecord *)hs->recs;
-    /* an empty payload may come without a pointer; the ragged job wants one */
-    job.in = in ? in : hs->arena;
-    job.out = out ? out : hs->arena;
+    job.in = in.base;
+    job.out = out.base;
     job.ad = hs->h;
     job.status = hs->step;
     job.n_records = hs->n;
     rc = open ? noise_aead_dev_open_ragged(cipher, &job, s) : noise_aead_dev_seal_ragged(cipher, &job, s);
     if (rc) return rc;
     ++hs->nonce;
-    return open ? mix_hash(hs, job.in, in_stride, len + HS_MAC_LEN, nullptr, 0, hs->step, s)
-                : mix_hash(hs, job.out, out_stride, len + HS_MAC_LEN, nullptr, 0, nullptr, s);
+    return open ? mix_hash(hs, in, lens, HS_MAC_LEN, NO_COPY, hs->step, out_len, s)
+                : mix_hash(hs, out, lens, HS_MAC_LEN, NO_COPY, nullptr, out_len, s);
 }
 
 int dh_step(Hs *hs, const HsStep &st, hipStream_t s)
@@ -291,22 +367,27 @@ int dh_step(Hs *hs, const HsStep &st, hipStream_t s)
     return rc ? rc : mix_key(hs, hs->arena, HS_DH_LEN, true, false, s);
 }
 
-/* the tokens and the payload of the next message; write: payload -> msg */
-int run_message(Hs *hs, const HsMessage &m, bool write, uint8_t *msg, uint64_t msg_stride, uint8_t *payload,
-                uint64_t payload_stride, uint32_t payload_len, hipStream_t s)
+/* The tokens and the payload of the next message; write: payload -> msg.
+   lens.per (a ragged call): the length rule first, and out_len with the
+   payload step, the last launch, where the statuses of this call are final. */
+int run_message(Hs *hs, const HsMessage &m, bool write, HsSpan msg, HsSpan payload, HsLens lens, uint32_t *out_len,
+                hipStream_t s)
 {
     uint64_t off = 0;
     int rc = NOISE_ERROR_NONE;
+    if (lens.per) rc = launch_items(hs_check_len, hs->n, HS_BLOCK, s, lens, hs->status, hs->n);
+    const HsSpan ls_pub = strided(hs->ls_pub, hs->ls_pub_stride), le_pub = strided(hs->le_pub, hs->le_pub_stride);
+    const HsSpan re = strided(hs->re, HS_DH_LEN), rs = strided(hs->rs, HS_DH_LEN);
     for (int t = 0; t < m.n_steps && !rc; ++t) {
         const HsStep &st = m.steps[t];
-        uint8_t *at = msg + off;
+        const HsSpan at = msg.from(off);
         switch (st.kind) {
         case HS_STEP_E:
             if (write) {
-                rc = mix_hash(hs, hs->le_pub, hs->le_pub_stride, HS_DH_LEN, at, msg_stride, nullptr, s);
+                rc = mix_hash(hs, le_pub, HS_DH_LEN, at, s);
                 if (!rc && st.mix_key) rc = mix_key(hs, hs->le_pub, hs->le_pub_stride, false, false, s);
             } else {
-                rc = mix_hash(hs, at, msg_stride, HS_DH_LEN, hs->re, HS_DH_LEN, nullptr, s);
+                rc = mix_hash(hs, at, HS_DH_LEN, re, s);
                 if (!rc) rc = launch_items(hs_null_check, hs->n, HS_BLOCK, s, hs->re, hs->status, hs->n);
                 if (!rc && st.mix_key) rc = mix_key(hs, hs->re, HS_DH_LEN, false, false, s);
             }
@@ -314,11 +395,11 @@ int run_message(Hs *hs, const HsMessage &m, bool write, uint8_t *msg, uint64_t m
             break;
         case HS_STEP_S:
             if (write)
-                rc = st.keyed ? aead_step(hs, false, hs->ls_pub, hs->ls_pub_stride, at, msg_stride, HS_DH_LEN, s)
-                              : mix_hash(hs, hs->ls_pub, hs->ls_pub_stride, HS_DH_LEN, at, msg_stride, nullptr, s);
+                rc = st.keyed ? aead_step(hs, false, ls_pub, at, fixed_len(HS_DH_LEN), nullptr, s)
+                              : mix_hash(hs, ls_pub, HS_DH_LEN, at, s);
             else
-                rc = st.keyed ? aead_step(hs, true, at, msg_stride, hs->rs, HS_DH_LEN, HS_DH_LEN, s)
-                              : mix_hash(hs, at, msg_stride, HS_DH_LEN, hs->rs, HS_DH_LEN, nullptr, s);
+                rc = st.keyed ? aead_step(hs, true, at, rs, fixed_len(HS_DH_LEN), nullptr, s)
+                              : mix_hash(hs, at, HS_DH_LEN, rs, s);
             off += HS_DH_LEN + (st.keyed ? HS_MAC_LEN : 0);
             break;
         case HS_STEP_DH:
@@ -326,11 +407,11 @@ int run_message(Hs *hs, const HsMessage &m, bool write, uint8_t *msg, uint64_t m
             break;
         case HS_STEP_PAYLOAD:
             if (write)
-                rc = st.keyed ? aead_step(hs, false, payload, payload_stride, at, msg_stride, payload_len, s)
-                              : mix_hash(hs, payload, payload_stride, payload_len, at, msg_stride, nullptr, s);
+                rc = st.keyed ? aead_step(hs, false, payload, at, lens, out_len, s)
+                              : mix_hash(hs, payload, lens, 0, at, nullptr, out_len, s);
             else
-                rc = st.keyed ? aead_step(hs, true, at, msg_stride, payload, payload_stride, payload_len, s)
-                              : mix_hash(hs, at, msg_stride, payload_len, payload, payload_stride, nullptr, s);
+                rc = st.keyed ? aead_step(hs, true, at, payload, lens, out_len, s)
+                              : mix_hash(hs, at, lens, 0, payload, nullptr, out_len, s);
             break;
         }
     }
@@ -372,16 +453,13 @@ int start(Hs *hs, const NoiseAeadHandshakeConfig *cfg, hipStream_t s)
     rc = launch_items(hs_init, hs->n, HS_BLOCK, s, ia);
     /* handshakestate.c:822-877 */
     if (!rc)
-        rc = mix_hash(hs, cfg->prologue_len ? cfg->d_prologue : hs->arena, cfg->prologue_stride, cfg->prologue_len,
-                      nullptr, 0, nullptr, s);
+        rc = mix_hash(hs, strided(cfg->prologue_len ? cfg->d_prologue : hs->arena, cfg->prologue_stride),
+                      cfg->prologue_len, NO_COPY, s);
     if (!rc && hs->name.psk) rc = mix_key(hs, cfg->d_psk, cfg->psk_stride, false, true, s);
     const bool init = hs_is_initiator(hs->role);
-    if (!rc && p.pre_i_s)
-        rc = init ? mix_hash(hs, hs->ls_pub, hs->ls_pub_stride, HS_DH_LEN, nullptr, 0, nullptr, s)
-                  : mix_hash(hs, hs->rs, HS_DH_LEN, HS_DH_LEN, nullptr, 0, nullptr, s);
-    if (!rc && p.pre_r_s)
-        rc = init ? mix_hash(hs, hs->rs, HS_DH_LEN, HS_DH_LEN, nullptr, 0, nullptr, s)
-                  : mix_hash(hs, hs->ls_pub, hs->ls_pub_stride, HS_DH_LEN, nullptr, 0, nullptr, s);
+    const HsSpan ls_pub = strided(hs->ls_pub, hs->ls_pub_stride), rs = strided(hs->rs, HS_DH_LEN);
+    if (!rc && p.pre_i_s) rc = mix_hash(hs, init ? ls_pub : rs, HS_DH_LEN, NO_COPY, s);
+    if (!rc && p.pre_r_s) rc = mix_hash(hs, init ? rs : ls_pub, HS_DH_LEN, NO_COPY, s);
     return rc;
 }
 
@@ -464,8 +542,45 @@ int noise_aead_dev_handshake_write_message(NoiseAeadDevHandshake *hs, const uint
     int rc = hs_check_write(hs->action, hs->n, m.overhead, d_payload, payload_stride, payload_len, d_msg, msg_stride);
     if (rc) return rc;
     if (hs->n)
-        rc = run_message(hs, m, true, d_msg, msg_stride, (uint8_t *)d_payload, payload_stride, payload_len,
-                         (hipStream_t)stream);
+        rc = run_message(hs, m, true, strided(d_msg, msg_stride), strided(d_payload, payload_stride),
+                         fixed_len(payload_len), nullptr, (hipStream_t)stream);
+    advance(hs, m);
+    return rc;
+}
+
+int noise_aead_dev_handshake_write_message_ragged(NoiseAeadDevHandshake *hs, const uint8_t *d_payload,
+                                                  const uint64_t *d_payload_off, const uint32_t *d_payload_len,
+                                                  uint8_t *d_msg, const uint64_t *d_msg_off, uint32_t *d_msg_len,
+                                                  void *stream)
+{
+    int rc = hs_check_write_ragged(hs, hs ? hs->action : NOISE_ACTION_NONE, hs ? hs->n : 0, d_payload, d_payload_off,
+                                   d_payload_len, d_msg, d_msg_off, d_msg_len);
+    if (rc) return rc;
+    const HsMessage m = next_message(hs);
+    if (hs->n) {
+        /* without the payload triple every payload is empty: the fixed length 0 */
+        const HsLens lens = {d_payload_len, 0, m.overhead, 1};
+        rc = run_message(hs, m, true, HsSpan{d_msg, {d_msg_off, 0}}, HsSpan{(uint8_t *)d_payload, {d_payload_off, 0}}, lens,
+                         d_msg_len, (hipStream_t)stream);
+    }
+    advance(hs, m);
+    return rc;
+}
+
+int noise_aead_dev_handshake_read_message_ragged(NoiseAeadDevHandshake *hs, const uint8_t *d_msg,
+                                                 const uint64_t *d_msg_off, const uint32_t *d_msg_len,
+                                                 uint8_t *d_payload, const uint64_t *d_payload_off,
+                                                 uint32_t *d_payload_len, void *stream)
+{
+    int rc = hs_check_read_ragged(hs, hs ? hs->action : NOISE_ACTION_NONE, hs ? hs->n : 0, d_msg, d_msg_off, d_msg_len,
+                                  d_payload, d_payload_off, d_payload_len);
+    if (rc) return rc;
+    const HsMessage m = next_message(hs);
+    if (hs->n) {
+        const HsLens lens = {d_msg_len, 0, m.overhead, 0};
+        rc = run_message(hs, m, false, HsSpan{(uint8_t *)d_msg, {d_msg_off, 0}}, HsSpan{d_payload, {d_payload_off, 0}}, lens,
+                         d_payload_len, (hipStream_t)stream);
+    }
     advance(hs, m);
     return rc;
 }
@@ -480,8 +595,8 @@ int noise_aead_dev_handshake_read_message(NoiseAeadDevHandshake *hs, const uint8
     int rc = hs_check_read(hs->action, hs->n, m.overhead, d_msg, msg_stride, msg_len, d_payload, payload_stride);
     if (rc) return rc;
     if (hs->n)
-        rc = run_message(hs, m, false, (uint8_t *)d_msg, msg_stride, d_payload, payload_stride, msg_len - m.overhead,
-                         (hipStream_t)stream);
+        rc = run_message(hs, m, false, strided(d_msg, msg_stride), strided(d_payload, payload_stride),
+                         fixed_len(msg_len - m.overhead), nullptr, (hipStream_t)stream);
     advance(hs, m);
     return rc;
 }

@@ -3,12 +3,14 @@
  * (include/noise_aead_hip.h section 8): the protocol-name parser, the token
  * table of the fifteen one-way and interactive patterns, the ordered steps and
  * the overhead of every message for (pattern, role, prefix, message index),
- * and the argument checks of the entry points.
+ * the argument checks of the entry points, and the length rule of one session
+ * of a ragged call (hs_session_len, which the kernels run too).
  *
  * No HIP header is included and no device pointer is dereferenced, so all of
  * it compiles with a host compiler alone and runs under ASan/UBSan
- * (asan/handshake_check.cpp, tests/test_handshake_host.py) — in the manner of
- * dispatch.h.  handshake.hip turns the steps into launches.
+ * (asan/handshake_check.cpp, tests/test_handshake_host.py;
+ * asan/handshake_ragged_check.cpp, tests/test_handshake_ragged_host.py) — in
+ * the manner of dispatch.h.  handshake.hip turns the steps into launches.
  *
  * The table is the Noise specification's (section 7); the parser follows the
  * name grammar prefix_pattern_dh_cipher_hash.  The old-style "NoisePSK" prefix
@@ -326,6 +328,93 @@ inline int hs_check_read(int action, uint32_t n, uint32_t overhead, const void *
     if (msg_stride && msg_stride < msg_len) return NOISE_ERROR_INVALID_PARAM;
     if (payload_len && payload_stride < payload_len) return NOISE_ERROR_INVALID_PARAM;
     if (hs_spans_meet(d_msg, msg_stride, msg_len, d_payload, payload_stride, payload_len, n)) return NOISE_ERROR_INVALID_PARAM;
+    return NOISE_ERROR_NONE;
+}
+
+/* ------------------------------------------------- per-session lengths
+   The ragged calls (_write_message_ragged, _read_message_ragged) give every
+   session its own length.  One source for both compilers, as tr_walk is
+   (transport_plan.h): hipcc's device pass builds the kernels of handshake.hip
+   from hs_session_len, plain g++ builds asan/handshake_ragged_check.cpp from
+   it. */
+
+#if defined(__HIPCC__)
+#define HS_FN __host__ __device__ __forceinline__
+#else
+#define HS_FN static inline __attribute__((always_inline))
+#endif
+
+constexpr uint8_t HS_STATUS_LENGTH = 4; /* NOISE_ERROR_INVALID_LENGTH of one session */
+
+struct HsLen {
+    bool refused;   /* the session takes status 4 and nothing of it is read or written */
+    uint32_t other; /* write: the message length; read: the payload length; 0 when refused */
+};
+
+/* What hs_check_write / hs_check_read refuse for a whole batch, for one
+   session: write takes the payload length and refuses a message over 65535
+   bytes; read takes the message length and refuses one over 65535 bytes or
+   below the overhead (handshakestate.c:1320-1324, :1454, :1489;
+   symmetricstate.c:419-422). */
+HS_FN HsLen hs_session_len(uint32_t overhead, uint32_t len, bool write)
+{
+    HsLen r = {true, 0};
+    if (write) {
+        if ((uint64_t)len + overhead > NOISE_MAX_PAYLOAD_LEN) return r;
+        r.other = len + overhead;
+    } else {
+        if (len > NOISE_MAX_PAYLOAD_LEN || len < overhead) return r;
+        r.other = len - overhead;
+    }
+    r.refused = false;
+    return r;
+}
+
+/* [a, a + a_bytes) meets [b, b + b_bytes) */
+inline bool hs_ranges_meet(const void *a, hs_u128 a_bytes, const void *b, hs_u128 b_bytes)
+{
+    if (!a_bytes || !b_bytes) return false;
+    const hs_u128 x = (uintptr_t)a, y = (uintptr_t)b;
+    return x < y + b_bytes && y < x + a_bytes;
+}
+
+/* the output length array of a ragged call against the arrays the call reads */
+inline bool hs_out_len_meets(const void *d_out_len, const void *d_off_a, const void *d_off_b, const void *d_in_len,
+                             uint32_t n)
+{
+    const hs_u128 lb = (hs_u128)4 * n, ob = (hs_u128)8 * n;
+    return hs_ranges_meet(d_out_len, lb, d_off_a, d_off_a ? ob : 0) ||
+           hs_ranges_meet(d_out_len, lb, d_off_b, d_off_b ? ob : 0) ||
+           hs_ranges_meet(d_out_len, lb, d_in_len, d_in_len ? lb : 0);
+}
+
+/* noise_aead_dev_handshake_write_message_ragged, in the order of the header;
+   the payload triple may be NULL all three together (every payload empty) */
+inline int hs_check_write_ragged(const void *hs, int action, uint32_t n, const void *d_payload,
+                                 const void *d_payload_off, const void *d_payload_len, const void *d_msg,
+                                 const void *d_msg_off, const void *d_msg_len)
+{
+    if (!hs) return NOISE_ERROR_INVALID_PARAM;
+    if (action != NOISE_ACTION_WRITE_MESSAGE) return NOISE_ERROR_INVALID_STATE;
+    if (!n) return NOISE_ERROR_NONE;
+    if (!d_msg || !d_msg_off || !d_msg_len) return NOISE_ERROR_INVALID_PARAM;
+    const int given = (d_payload != nullptr) + (d_payload_off != nullptr) + (d_payload_len != nullptr);
+    if (given != 0 && given != 3) return NOISE_ERROR_INVALID_PARAM;
+    if (hs_out_len_meets(d_msg_len, d_payload_off, d_msg_off, d_payload_len, n)) return NOISE_ERROR_INVALID_PARAM;
+    return NOISE_ERROR_NONE;
+}
+
+/* noise_aead_dev_handshake_read_message_ragged */
+inline int hs_check_read_ragged(const void *hs, int action, uint32_t n, const void *d_msg, const void *d_msg_off,
+                                const void *d_msg_len, const void *d_payload, const void *d_payload_off,
+                                const void *d_payload_len)
+{
+    if (!hs) return NOISE_ERROR_INVALID_PARAM;
+    if (action != NOISE_ACTION_READ_MESSAGE) return NOISE_ERROR_INVALID_STATE;
+    if (!n) return NOISE_ERROR_NONE;
+    if (!d_msg || !d_msg_off || !d_msg_len || !d_payload || !d_payload_off || !d_payload_len)
+        return NOISE_ERROR_INVALID_PARAM;
+    if (hs_out_len_meets(d_payload_len, d_msg_off, d_payload_off, d_msg_len, n)) return NOISE_ERROR_INVALID_PARAM;
     return NOISE_ERROR_NONE;
 }
 

@@ -182,6 +182,8 @@ def lib() -> C.CDLL:
         "noise_aead_dev_handshake_overhead": (sz, [vp]),
         "noise_aead_dev_handshake_write_message": (i, [vp, vp, C.c_uint64, C.c_uint32, vp, C.c_uint64, vp]),
         "noise_aead_dev_handshake_read_message": (i, [vp, vp, C.c_uint64, C.c_uint32, vp, C.c_uint64, vp]),
+        "noise_aead_dev_handshake_write_message_ragged": (i, [vp, vp, vp, vp, vp, vp, vp, vp]),
+        "noise_aead_dev_handshake_read_message_ragged": (i, [vp, vp, vp, vp, vp, vp, vp, vp]),
         "noise_aead_dev_handshake_split": (i, [vp, vp, vp, vp, vp]),
         "noise_aead_dev_handshake_status": (vp, [vp]),
         "noise_aead_dev_handshake_remote_static": (vp, [vp]),
@@ -549,13 +551,31 @@ def dev_handshake_read_message(hs: int, *, msg: int, msg_stride: int, msg_len: i
                                                        payload_stride, stream or None)
 
 
+def dev_handshake_write_message_ragged(hs: int, *, payload: int = 0, payload_off: int = 0, payload_len: int = 0,
+                                       msg: int, msg_off: int, msg_len: int, stream: int = 0) -> int:
+    """payload_off / msg_off: n uint64 on the device; payload_len: n uint32;
+    msg_len: n uint32 the call writes.  The payload triple may be 0 all three."""
+    return lib().noise_aead_dev_handshake_write_message_ragged(hs, payload or None, payload_off or None,
+                                                               payload_len or None, msg or None, msg_off or None,
+                                                               msg_len or None, stream or None)
+
+
+def dev_handshake_read_message_ragged(hs: int, *, msg: int, msg_off: int, msg_len: int, payload: int,
+                                      payload_off: int, payload_len: int, stream: int = 0) -> int:
+    """msg_off / payload_off: n uint64 on the device; msg_len: n uint32;
+    payload_len: n uint32 the call writes."""
+    return lib().noise_aead_dev_handshake_read_message_ragged(hs, msg or None, msg_off or None, msg_len or None,
+                                                              payload or None, payload_off or None,
+                                                              payload_len or None, stream or None)
+
+
 def dev_handshake_split(hs: int, *, k1: int, k2: int, handshake_hash: int = 0, stream: int = 0) -> int:
     return lib().noise_aead_dev_handshake_split(hs, k1 or None, k2 or None, handshake_hash or None,
                                                 stream or None)
 
 
 def dev_handshake_status(hs: int) -> int:
-    """device pointer of the n status bytes (0 ok, 1 MAC failure, 3 null ephemeral)"""
+    """device pointer of the n status bytes (0 ok, 1 MAC failure, 3 null ephemeral, 4 a refused length)"""
     return lib().noise_aead_dev_handshake_status(hs) or 0
 
 
