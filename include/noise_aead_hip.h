@@ -833,6 +833,114 @@ int noise_aead_dev_transport_echo_frames_of(NoiseAeadDevTransport *tr, const uin
                                             uint32_t max_frames, uint8_t *d_wire, const uint64_t *d_off,
                                             const uint32_t *d_len, NoiseAeadTransportResult *d_result, void *stream);
 
+/* ------------------------------------------------ 11. datagram transport
+ *
+ * The session table (section 10) for traffic that is lost, duplicated and
+ * reordered: the Noise specification's "out-of-order transport messages".
+ * The sender puts the 64-bit nonce on the wire, the receiver uses it for that
+ * one message, and an anti-replay window per slot, kept on the device, refuses
+ * a counter it has accepted before.  The reference has only the primitive,
+ * noise_cipherstate_set_nonce (cipherstate.c:518-535), which refuses to go
+ * backwards.  Nothing of sections 9 and 10 changes: the stream calls never
+ * read or write a window, and the datagram open never reads or writes a
+ * receive nonce.
+ *
+ * Wire format.  A session's bytes lie as in sections 9 and 10: entry j's
+ * stream is the d_len[j] bytes at d_wire + d_off[j], frames of a 2-byte
+ * big-endian L and L bytes.  In a datagram frame the L bytes are an 8-byte
+ * little-endian counter, then CT || tag: L >= 24, and the payload is L - 24
+ * bytes.  The walk is that of section 9 with 24 in place of 16: a partial
+ * frame ends it with NOISE_ERROR_NONE, a complete frame with L < 24 ends it
+ * with NOISE_ERROR_INVALID_LENGTH and is left untouched (a packer knows its
+ * datagrams' lengths and packs no runt); frames are numbered across the call
+ * in list order and the cap cuts as in section 9; an unkeyed entry gives
+ * NOISE_ERROR_INVALID_STATE and an out-of-range one NOISE_ERROR_INVALID_PARAM,
+ * with no frames and nothing read or written, as in section 10.  d_slots ==
+ * NULL means entry j is slot j; max_frames == 0 means the object's own cap.
+ *
+ * The replay state of a slot: top, the highest accepted counter + 1 (0 when
+ * nothing has been accepted), and a bitmap of 1024 bits; bit c % 1024 stands
+ * for counter c.  For a counter c:
+ *   - c == 2^64 - 1 is refused: the CipherState never uses that nonce;
+ *   - c >= top is fresh.  On acceptance the bits of the counters top .. c - 1
+ *     are cleared (the whole bitmap if c - top >= 1024), bit c is set and top
+ *     becomes c + 1;
+ *   - c < top with top - c > 1024 is refused as too old;
+ *   - otherwise c is refused if its bit is set, else it is fresh, and on
+ *     acceptance its bit is set.
+ * _set_keys and _clear_keys reset a slot's state to all zero, as init_key
+ * resets n; an object starts with every window zero.  _replay returns the
+ * object's device array of n x {uint64 top; uint64 seen[16]} (136 bytes per
+ * slot), which a caller may read or write in stream order, and the window
+ * size in *bits (bits may be NULL); NULL for a NULL tr and for n == 0.
+ *
+ * _seal_datagrams is _seal_frames_of on frames with 8 bytes of room in front:
+ * frame k of the entry gets the counter send + k written into those 8 bytes,
+ * and its L - 24 plaintext bytes and 16 bytes of room become CT || tag under
+ * that counter.  send advances by the frames taken; the walk stops with
+ * NOISE_ERROR_INVALID_NONCE where send + k == 2^64 - 1.  Result and cap as in
+ * section 10.
+ *
+ * _open_datagrams judges every walked frame alone; nothing is sticky, and a
+ * forged frame costs its session nothing.  d_frame_status[first + k] is the
+ * status of the entry's frame k:
+ *   0  accepted: the plaintext is in place at body + 8, the tag bytes are left
+ *      as they were;
+ *   1  the tag failed: the frame is byte for byte untouched;
+ *   5  refused by the window (NOISE_ERROR_INVALID_NONCE, what set_nonce
+ *      answers for a counter behind the state).
+ * Statuses 2 to 4 do not occur.  Bytes of d_frame_status at or past the
+ * call's total of walked frames are not written.  The statuses and the window
+ * after the call are those of processing the entry's frames one by one in
+ * stream order: the window refuses the counter -> 5; else the tag is verified
+ * under the receive key with nonce = counter, and a failed tag -> 1; else the
+ * counter is accepted -> 0.  A forged frame never moves the window.  In the
+ * result, frames, consumed and error are the walk's; accepted counts the
+ * entry's frames with status 0; first is the number of its first frame (for
+ * an entry after the cut, which has no frames, the number it would have had;
+ * 0 for an entry that is not live).
+ * A frame with status 5 holds its bytes as given, with one exception: a
+ * frame that only an earlier frame of the same call made a replay (a
+ * duplicate inside the call, or a counter that a jump of top inside the call
+ * left behind) was opened before the window moved, so if its own tag verified
+ * it may hold its plaintext (tag bytes as they were) — never anything else
+ * and never unauthenticated plaintext.  A frame the window refused as it
+ * stood before the call is never touched and costs no AEAD work.
+ *
+ * Both calls are asynchronous on `stream`, allocate nothing, copy nothing to
+ * the host and never synchronise.  The listed slots must be distinct and the
+ * streams disjoint: the caller's guarantee.
+ *
+ * Checked on the host before any launch, in this order:
+ *   1. a NULL tr gives NOISE_ERROR_INVALID_PARAM;
+ *   2. m == 0 gives NOISE_ERROR_NONE, and nothing is launched;
+ *   3. m > n gives NOISE_ERROR_INVALID_PARAM;
+ *   4. a NULL d_wire, d_off, d_len or d_result, and for the open a NULL
+ *      d_frame_status, give NOISE_ERROR_INVALID_PARAM;
+ *   5. a max_frames above the object's gives NOISE_ERROR_INVALID_PARAM;
+ *   6. d_result (16 m bytes for the seal, 24 m for the open) meeting
+ *      [d_off, + 8 m), [d_len, + 4 m) or a given [d_slots, + 4 m), and for
+ *      the open [d_frame_status, + the call's cap) meeting any of those or
+ *      d_result, give NOISE_ERROR_INVALID_PARAM.
+ * A call whose scan of m items would need more scratch than _new carved for n
+ * gives NOISE_ERROR_SYSTEM (nothing is launched). */
+typedef struct NoiseAeadDatagramResult {
+    uint32_t frames;    /* frames of this entry walked by the call */
+    uint32_t consumed;  /* bytes they span, headers included */
+    int32_t  error;     /* the walk's stop: NOISE_ERROR_NONE / _INVALID_LENGTH; _INVALID_STATE / _INVALID_PARAM for an entry that is not live */
+    uint32_t accepted;  /* frames of this entry whose status is 0 */
+    uint64_t first;     /* number of this entry's first frame in d_frame_status */
+} NoiseAeadDatagramResult;
+
+int noise_aead_dev_transport_seal_datagrams(NoiseAeadDevTransport *tr, const uint32_t *d_slots /* may be NULL */,
+                                            uint32_t m, uint32_t max_frames, uint8_t *d_wire, const uint64_t *d_off,
+                                            const uint32_t *d_len, NoiseAeadTransportResult *d_result, void *stream);
+int noise_aead_dev_transport_open_datagrams(NoiseAeadDevTransport *tr, const uint32_t *d_slots /* may be NULL */,
+                                            uint32_t m, uint32_t max_frames, uint8_t *d_wire, const uint64_t *d_off,
+                                            const uint32_t *d_len, NoiseAeadDatagramResult *d_result,
+                                            uint8_t *d_frame_status, void *stream);
+uint64_t *noise_aead_dev_transport_replay(const NoiseAeadDevTransport *tr, uint32_t *bits);
+
 /* ------------------------------------------------ error reports
  * include/noise/protocol/errors.h; src/protocol/errors.c:92-127. */
 void noise_perror(const char *s, int err);

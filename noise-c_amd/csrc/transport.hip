@@ -1,6 +1,6 @@
 /*
  * transport.hip — device-resident transport sessions:
- * noise_aead_dev_transport_* (include/noise_aead_hip.h sections 9 and 10).
+ * noise_aead_dev_transport_* (include/noise_aead_hip.h sections 9 to 11).
  *
  * The object holds, for n sessions, a send and a receive key context and a
  * send and a receive nonce on the device, and what a call needs: descriptors
@@ -48,6 +48,21 @@
  *                stores, both nonces and the state; a lane per entry for the
  *                32-byte ChaChaPoly contexts, a workgroup per (entry,
  *                direction) for the 41 344-byte AES-GCM ones.
+ *
+ * Datagram transport (section 11): every frame carries its counter, every
+ * frame is judged alone, and each slot has an anti-replay window (TrReplay,
+ * transport_plan.h) that tr_mark zeroes with the nonces.  A call is
+ *   tr_count<24>, the scan, then
+ *   tr_build_datagrams   one lane per entry.  Seal: writes frame k's counter
+ *                send + k and its descriptor (in place behind the counter),
+ *                and commits as tr_build does.  Open: reads each frame's
+ *                counter, asks tr_replay_check of the window as it stands, and
+ *                writes the descriptor under that counter or refused_rec(): a
+ *                replay costs no AEAD work;
+ *   the AEAD     as above, the open verify-first;
+ *   tr_commit_datagrams  open: one lane per entry walks its frames in order
+ *                with the window evolving: refused before (status 2) or by
+ *                now -> 5, tag failed -> 1, else tr_replay_accept -> 0.
  */
 #include "launch.h"
 
@@ -99,12 +114,19 @@ TR_DEV uint64_t tr_start_nonce(const TrArgs &a, uint32_t i)
     return a.send[i] > a.recv[i] ? a.send[i] : a.recv[i];
 }
 
+/* MIN_L: the smallest L of a frame, 16, or 24 for the datagram calls, whose open walks under no nonce */
+template <uint32_t MIN_L>
 __global__ __launch_bounds__(TR_BLOCK) void tr_count(TrArgs a)
 {
     const uint32_t j = blockIdx.x * TR_BLOCK + threadIdx.x;
     if (j >= a.m) return;
     uint32_t i;
-    a.count[j] = tr_live(a, j, &i) ? tr_walk(a.wire + a.off[j], a.len[j], tr_start_nonce(a, i), TR_NO_BUDGET).frames : 0;
+    uint64_t count = 0;
+    if (tr_live(a, j, &i)) {
+        const uint64_t nonce = MIN_L == TR_DATAGRAM_MIN && a.mode == TR_OPEN ? 0 : tr_start_nonce(a, i);
+        count = tr_walk(a.wire + a.off[j], a.len[j], nonce, TR_NO_BUDGET, TrNoEmit(), MIN_L).frames;
+    }
+    a.count[j] = count;
 }
 
 struct TrEmit {
@@ -196,6 +218,134 @@ __global__ __launch_bounds__(TR_BLOCK) void tr_commit(TrArgs a)
     a.result[j] = r;
 }
 
+/* ---- datagram transport (section 11) */
+
+struct TrDatagramArgs {
+    TrArgs a;                    /* a.result: the seal's; a.mode: TR_SEAL or TR_OPEN */
+    uint8_t *wire;               /* a.wire, to write the seal's counters through */
+    TrReplay *replay;            /* per slot */
+    NoiseAeadDatagramResult *result; /* the open's */
+    uint8_t *frame_status;       /* the open's, one byte per walked frame of the call */
+};
+
+constexpr uint8_t TR_FRAME_REPLAY = 5;
+
+/* nothing of a stream is aligned */
+TR_DEV uint64_t tr_load_counter(const uint8_t *p)
+{
+    uint64_t c = 0;
+    for (int b = 0; b < 8; ++b) c |= (uint64_t)p[b] << (8 * b);
+    return c;
+}
+
+/* frame k's descriptor: in place behind the counter, under that counter; the
+   seal writes send + k there first, the open refuses what the window refuses */
+struct TrDatagramEmit {
+    RecDesc *recs;
+    uint8_t *stream;             /* the entry's */
+    uint64_t wire_off, send, ctx_off;
+    const TrReplay *window;      /* null: a seal */
+    TR_DEV void operator()(uint64_t k, uint64_t body, uint32_t L) const
+    {
+        uint64_t c = send + k;
+        if (window)
+            c = tr_load_counter(stream + body);
+        else
+            for (int b = 0; b < 8; ++b) stream[body + b] = (uint8_t)(c >> (8 * b));
+        RecDesc d = refused_rec();
+        if (!window || tr_replay_check(window, c)) {
+            d.in_off = d.out_off = wire_off + body + TR_COUNTER_LEN;
+            d.nonce = c;
+            d.ctx_off = ctx_off;
+            d.ad_off = 0;
+            d.len = L - TR_DATAGRAM_MIN;
+            d.ad_len = 0;
+        }
+        recs[k] = d;
+    }
+};
+
+__global__ __launch_bounds__(TR_BLOCK) void tr_build_datagrams(TrDatagramArgs g)
+{
+    const TrArgs &a = g.a;
+    const uint64_t t = (uint64_t)blockIdx.x * TR_BLOCK + threadIdx.x;
+    const uint64_t all = a.base[a.m - 1] + a.count[a.m - 1];
+    const uint64_t total = all < a.max_frames ? all : a.max_frames;
+    if (t >= total && t < a.max_frames) a.recs[t] = refused_rec();
+    if (t >= a.m) return;
+    const uint32_t j = (uint32_t)t;
+    const bool seal = a.mode == TR_SEAL;
+    uint32_t i;
+    if (!tr_live(a, j, &i)) {
+        const int32_t error = i < a.n ? NOISE_ERROR_INVALID_STATE : NOISE_ERROR_INVALID_PARAM;
+        if (seal) {
+            const NoiseAeadTransportResult r = {0, 0, error, 0};
+            a.result[j] = r;
+        } else {
+            const NoiseAeadDatagramResult r = {0, 0, error, 0, 0};
+            g.result[j] = r;
+        }
+        return;
+    }
+    bool cut;
+    const uint64_t base = a.base[j], budget = tr_cap(base, a.count[j], a.max_frames, &cut);
+    const uint64_t send = seal ? a.send[i] : 0;
+    const TrDatagramEmit emit = {a.recs + base, g.wire + a.off[j], a.off[j], send,
+                                 (seal ? (uint64_t)i : (uint64_t)a.n + i) * a.ctx_bytes, seal ? nullptr : g.replay + i};
+    TrWalk w = {0, 0, NOISE_ERROR_NONE};
+    if (budget || !cut) w = tr_walk(a.wire + a.off[j], a.len[j], send, budget, emit, TR_DATAGRAM_MIN);
+    if (cut) w.stop = NOISE_ERROR_NONE;
+    if (seal) {
+        a.send[i] = send + w.frames;
+        const NoiseAeadTransportResult r = {(uint32_t)w.frames, (uint32_t)w.consumed, w.stop, 0};
+        a.result[j] = r;
+        return;
+    }
+    a.frames[j] = (uint32_t)w.frames;
+    a.consumed[j] = (uint32_t)w.consumed;
+    a.stop[j] = w.stop;
+}
+
+/* frame k of the entry, in stream order, against the window as the frames before it left it */
+struct TrDatagramJudge {
+    const uint8_t *stream, *status; /* the entry's; the AEAD's statuses from the entry's first frame on */
+    uint8_t *frame_status;
+    TrReplay *window;
+    uint32_t *accepted;
+    TR_DEV void operator()(uint64_t k, uint64_t body, uint32_t) const
+    {
+        const uint64_t c = tr_load_counter(stream + body);
+        const uint8_t s = status[k];
+        uint8_t out = TR_FRAME_REPLAY;
+        if (s != STATUS_BAD_LENGTH && tr_replay_check(window, c)) {
+            out = s;
+            if (s == 0) {
+                tr_replay_accept(window, c);
+                ++*accepted;
+            }
+        }
+        frame_status[k] = out;
+    }
+};
+
+__global__ __launch_bounds__(TR_BLOCK) void tr_commit_datagrams(TrDatagramArgs g)
+{
+    const TrArgs &a = g.a;
+    const uint32_t j = blockIdx.x * TR_BLOCK + threadIdx.x;
+    if (j >= a.m) return;
+    uint32_t i;
+    if (!tr_live(a, j, &i)) return; /* tr_build_datagrams wrote its result; it has no frames */
+    const uint32_t frames = a.frames[j];
+    const uint64_t base = a.base[j]; /* base + frames <= max_frames (tr_cap) */
+    uint32_t accepted = 0;
+    if (frames) { /* the headers and counters are as tr_build_datagrams read them: the same frames again */
+        const TrDatagramJudge judge = {a.wire + a.off[j], a.status + base, g.frame_status + base, g.replay + i, &accepted};
+        tr_walk(a.wire + a.off[j], a.len[j], 0, frames, judge, TR_DATAGRAM_MIN);
+    }
+    const NoiseAeadDatagramResult r = {frames, a.consumed[j], a.stop[j], accepted, base};
+    g.result[j] = r;
+}
+
 /* ---- keying and un-keying slots (section 10) */
 
 struct TrKeyArgs {
@@ -204,6 +354,7 @@ struct TrKeyArgs {
     const uint8_t *status;       /* may be null; set: an entry whose byte is not 0 is cleared instead */
     uint8_t *ctx;                /* n send contexts, then n receive contexts */
     uint64_t *send, *recv;
+    TrReplay *replay;
     uint8_t *keyed;
     uint64_t ctx_bytes;          /* a multiple of 16; the contexts are 16-byte aligned */
     uint32_t m, n;
@@ -219,9 +370,13 @@ TR_DEV uint4 tr_load_key16(const uint8_t *p)
     return make_uint4(w[0], w[1], w[2], w[3]);
 }
 
-/* both nonces and the state of slot i */
-TR_DEV void tr_mark(const TrKeyArgs &a, uint32_t i, bool keyed)
+/* both nonces, the anti-replay window and the state of slot i, shared among
+   the caller's `lanes` lanes (lane 0 .. lanes - 1 each call it once) */
+TR_DEV void tr_mark(const TrKeyArgs &a, uint32_t i, bool keyed, uint32_t lane = 0, uint32_t lanes = 1)
 {
+    uint64_t *window = (uint64_t *)(a.replay + i); /* top, then the bitmap */
+    for (uint32_t q = lane; q < 1 + TR_REPLAY_WORDS; q += lanes) window[q] = 0;
+    if (lane) return;
     a.send[i] = 0;
     a.recv[i] = 0;
     a.keyed[i] = keyed ? 1 : 0;
@@ -268,7 +423,7 @@ __global__ __launch_bounds__(TR_WIDE_BLOCK) void tr_clear_wide(TrKeyArgs a)
     uint32_t i;
     if (!tr_slot(a.slots, j, a.n, &i)) return;
     const bool keep = a.set && !(a.status && a.status[j]);
-    if (!receive && threadIdx.x == 0) tr_mark(a, i, keep);
+    if (!receive && threadIdx.x < 1 + TR_REPLAY_WORDS) tr_mark(a, i, keep, threadIdx.x, 1 + TR_REPLAY_WORDS);
     if (keep) return;
     uint4 *c = (uint4 *)(a.ctx + ((uint64_t)receive * a.n + i) * a.ctx_bytes);
     for (uint64_t w = threadIdx.x, words = a.ctx_bytes / 16; w < words; w += TR_WIDE_BLOCK) c[w] = make_uint4(0, 0, 0, 0);
@@ -288,6 +443,7 @@ struct NoiseAeadDevTransport {
     RecDesc *recs, *seal_recs;
     uint8_t *status;
     uint8_t *keyed;           /* per slot: 1 keyed, 0 not */
+    TrReplay *replay;         /* per slot: the datagram calls' anti-replay window */
     void *scan_tmp;
     size_t scan_bytes;
 };
@@ -318,7 +474,7 @@ int run(Tr *tr, TrMode mode, const uint32_t *slots, uint32_t m, uint32_t cap, ui
     const TrArgs a = {d_wire, d_off, d_len, d_result, tr->send, tr->recv, tr->count, tr->base, tr->frames, tr->consumed,
                       tr->stop, tr->recs, tr->seal_recs, tr->status, tr->ctx_bytes, cap, tr->n, mode, slots, tr->keyed, m};
     const uint32_t most = m > cap ? m : cap; /* tr_build and an echo's tr_commit also pad the descriptors up to the cap */
-    int rc = launch_items(tr_count, m, TR_BLOCK, s, a);
+    int rc = launch_items(tr_count<TR_MAC_LEN>, m, TR_BLOCK, s, a);
     if (!rc) rc = scan_counts(tr, tr->scan_tmp, bytes, m, s);
     if (!rc) rc = launch_items(tr_build, most, TR_BLOCK, s, a);
     if (rc) return rc;
@@ -359,6 +515,47 @@ int run_of(Tr *tr, TrMode mode, const uint32_t *d_slots, uint32_t m, uint32_t ma
                (hipStream_t)stream);
 }
 
+/* the calls of section 11: the listed slots (null: entry j is slot j), the
+   call's cap; d_result is the seal's, d_datagram_result and d_frame_status the open's */
+int run_datagrams(Tr *tr, TrMode mode, const uint32_t *d_slots, uint32_t m, uint32_t max_frames, uint8_t *d_wire,
+                  const uint64_t *d_off, const uint32_t *d_len, NoiseAeadTransportResult *d_result,
+                  NoiseAeadDatagramResult *d_datagram_result, uint8_t *d_frame_status, void *stream)
+{
+    const bool open = mode == TR_OPEN;
+    int rc = tr_check_datagrams(tr, tr ? tr->n : 0, tr ? tr->max_frames : 0, d_slots, m, max_frames, d_wire, d_off, d_len,
+                                open ? (const void *)d_datagram_result : (const void *)d_result,
+                                open ? sizeof(NoiseAeadDatagramResult) : sizeof(NoiseAeadTransportResult), open,
+                                d_frame_status);
+    if (rc || !m) return rc;
+    hipStream_t s = (hipStream_t)stream;
+    size_t bytes = tr->scan_bytes;
+    if (m != tr->n) { /* _new carved the scan's scratch for n items */
+        size_t need = 0;
+        rc = scan_counts(tr, nullptr, need, m, s);
+        if (rc) return rc;
+        if (need > tr->scan_bytes) return NOISE_ERROR_SYSTEM;
+    }
+    const uint32_t cap = max_frames ? max_frames : tr->max_frames;
+    const TrDatagramArgs g = {{d_wire, d_off, d_len, d_result, tr->send, tr->recv, tr->count, tr->base, tr->frames,
+                               tr->consumed, tr->stop, tr->recs, tr->seal_recs, tr->status, tr->ctx_bytes, cap, tr->n,
+                               mode, d_slots, tr->keyed, m},
+                              d_wire, tr->replay, d_datagram_result, d_frame_status};
+    rc = launch_items(tr_count<TR_DATAGRAM_MIN>, m, TR_BLOCK, s, g.a);
+    if (!rc) rc = scan_counts(tr, tr->scan_tmp, bytes, m, s);
+    if (!rc) rc = launch_items(tr_build_datagrams, m > cap ? m : cap, TR_BLOCK, s, g); /* it pads the descriptors up to the cap */
+    if (rc) return rc;
+    NoiseAeadRagged job = {};
+    job.ctx_base = tr->ctx;
+    job.recs = (const NoiseAeadRecord *)tr->recs;
+    job.in = job.out = d_wire;
+    job.ad = d_wire; /* never read: every ad_len is 0 */
+    job.status = tr->status;
+    job.n_records = cap;
+    if (!open) return noise_aead_dev_seal_ragged(tr->cipher_id, &job, s);
+    rc = noise_aead_dev_open_ragged(tr->cipher_id, &job, s);
+    return rc ? rc : launch_items(tr_commit_datagrams, m, TR_BLOCK, s, g);
+}
+
 /* The object and its one device allocation, zeroed on s: every slot unkeyed,
    every nonce 0.  The arguments are checked. */
 int make(Tr **out, int cipher_id, int role, uint32_t n, uint32_t max_frames, hipStream_t s)
@@ -385,6 +582,7 @@ int make(Tr **out, int cipher_id, int role, uint32_t n, uint32_t max_frames, hip
         const size_t o_consumed = d.carve(ns * 4), o_stop = d.carve(ns * 4);
         const size_t o_recs = d.carve(nf * sizeof(RecDesc)), o_seal = d.carve(nf * sizeof(RecDesc));
         const size_t o_status = d.carve(nf), o_keyed = d.carve(ns), o_scan = d.carve(tr->scan_bytes);
+        const size_t o_replay = d.carve(ns * sizeof(TrReplay));
         if (!d.alloc()) {
             delete tr;
             return NOISE_ERROR_NO_MEMORY;
@@ -394,6 +592,7 @@ int make(Tr **out, int cipher_id, int role, uint32_t n, uint32_t max_frames, hip
         tr->frames = d.at<uint32_t>(o_frames); tr->consumed = d.at<uint32_t>(o_consumed);
         tr->stop = d.at<int32_t>(o_stop); tr->recs = d.at<RecDesc>(o_recs); tr->seal_recs = d.at<RecDesc>(o_seal);
         tr->status = d.at(o_status); tr->keyed = d.at(o_keyed); tr->scan_tmp = d.at(o_scan);
+        tr->replay = d.at<TrReplay>(o_replay);
         rc = d.zero(s);
         if (rc) {
             noise_aead_dev_transport_free(tr);
@@ -411,6 +610,7 @@ TrKeyArgs key_args(const Tr *tr, const uint32_t *d_slots, uint32_t m)
     a.ctx = tr->ctx;
     a.send = tr->send;
     a.recv = tr->recv;
+    a.replay = tr->replay;
     a.keyed = tr->keyed;
     a.ctx_bytes = tr->ctx_bytes;
     a.m = m;
@@ -553,6 +753,27 @@ int noise_aead_dev_transport_echo_frames_of(NoiseAeadDevTransport *tr, const uin
                                             const uint32_t *d_len, NoiseAeadTransportResult *d_result, void *stream)
 {
     return run_of(tr, TR_ECHO, d_slots, m, max_frames, d_wire, d_off, d_len, d_result, stream);
+}
+
+int noise_aead_dev_transport_seal_datagrams(NoiseAeadDevTransport *tr, const uint32_t *d_slots, uint32_t m,
+                                            uint32_t max_frames, uint8_t *d_wire, const uint64_t *d_off,
+                                            const uint32_t *d_len, NoiseAeadTransportResult *d_result, void *stream)
+{
+    return run_datagrams(tr, TR_SEAL, d_slots, m, max_frames, d_wire, d_off, d_len, d_result, nullptr, nullptr, stream);
+}
+
+int noise_aead_dev_transport_open_datagrams(NoiseAeadDevTransport *tr, const uint32_t *d_slots, uint32_t m,
+                                            uint32_t max_frames, uint8_t *d_wire, const uint64_t *d_off,
+                                            const uint32_t *d_len, NoiseAeadDatagramResult *d_result,
+                                            uint8_t *d_frame_status, void *stream)
+{
+    return run_datagrams(tr, TR_OPEN, d_slots, m, max_frames, d_wire, d_off, d_len, nullptr, d_result, d_frame_status, stream);
+}
+
+uint64_t *noise_aead_dev_transport_replay(const NoiseAeadDevTransport *tr, uint32_t *bits)
+{
+    if (bits) *bits = TR_REPLAY_BITS;
+    return tr && tr->n ? (uint64_t *)tr->replay : nullptr;
 }
 
 } // extern "C"

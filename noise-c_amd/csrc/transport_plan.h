@@ -2,14 +2,16 @@
  * transport_plan.h — the host-only half of the device-resident transport
  * sessions (noise_aead_dev_transport_*, include/noise_aead_hip.h section 9):
  * the frame walk of one session, the cap rule across sessions, the slot of a
- * call's entry (section 10, the session table), and the argument checks.  One source for both compilers, as fe25519.h is: hipcc's
+ * call's entry (section 10, the session table), the anti-replay window of the
+ * datagram calls (section 11), and the argument checks.  One source for both compilers, as fe25519.h is: hipcc's
  * device pass builds the kernels of transport.hip from tr_walk and tr_cap,
- * plain g++ builds asan/transport_check.cpp and asan/transport_table_check.cpp
- * from them, so the CPU check under
- * ASan/UBSan runs the walk the GPU runs.
+ * plain g++ builds asan/transport_check.cpp, asan/transport_table_check.cpp
+ * and asan/transport_datagram_check.cpp from them, so the CPU check under
+ * ASan/UBSan runs the walk and the window rule the GPU runs.
  *
  * The wire format is that of csrc/wire.c (echo-common.c:643-688): a 2-byte
- * big-endian length L, then L bytes of CT || tag.
+ * big-endian length L, then L bytes of CT || tag; in a datagram frame the L
+ * bytes start with the frame's 8-byte little-endian counter.
  */
 #pragma once
 #include "noise_aead_hip.h"
@@ -29,6 +31,10 @@ constexpr uint64_t TR_NONCE_LIMIT = ~0ull;     /* cipherstate.c: n == 2^64 - 1 i
 constexpr uint32_t TR_MAC_LEN = 16;
 constexpr uint32_t TR_MAX_FRAMES = 1u << 31;   /* the most records one call may describe */
 constexpr uint64_t TR_NO_BUDGET = ~0ull;
+constexpr uint32_t TR_COUNTER_LEN = 8;                             /* a datagram frame's counter */
+constexpr uint32_t TR_DATAGRAM_MIN = TR_COUNTER_LEN + TR_MAC_LEN;  /* its smallest L */
+constexpr uint32_t TR_REPLAY_BITS = 1024;                          /* the anti-replay window */
+constexpr uint32_t TR_REPLAY_WORDS = TR_REPLAY_BITS / 64;
 
 struct TrWalk {
     uint64_t frames;    /* frames taken */
@@ -44,7 +50,8 @@ struct TrNoEmit {
 /* The walk of one session's stream, in the order of wire.c scan_frames: the
    frames from the start of p[0..len), frame k under nonce + k.  It ends with
    NOISE_ERROR_NONE at a partial (or absent) frame, with _INVALID_LENGTH at a
-   complete frame with L < 16, with _INVALID_NONCE where nonce + k is
+   complete frame with L < min_len (16: a tag; 24 for a datagram frame, which
+   carries its counter), with _INVALID_NONCE where nonce + k is
    2^64 - 1; the stopping frame is not taken.  A frame that would be taken as
    number `budget` is left for the next call instead: the walk ends there with
    NOISE_ERROR_NONE, having taken `budget` frames — so a stop that comes
@@ -52,7 +59,8 @@ struct TrNoEmit {
    is the larger of the two directions' (the first to run out).  Reads only
    p[0..len). */
 template <class Emit>
-TR_FN TrWalk tr_walk(const uint8_t *p, uint64_t len, uint64_t nonce, uint64_t budget, Emit emit)
+TR_FN TrWalk tr_walk(const uint8_t *p, uint64_t len, uint64_t nonce, uint64_t budget, Emit emit,
+                     uint32_t min_len = TR_MAC_LEN)
 {
     TrWalk w = {0, 0, NOISE_ERROR_NONE};
     uint64_t off = 0;
@@ -60,7 +68,7 @@ TR_FN TrWalk tr_walk(const uint8_t *p, uint64_t len, uint64_t nonce, uint64_t bu
         const uint32_t L = ((uint32_t)p[off] << 8) | p[off + 1];
         if (len - off - 2 < L) break;
         /* both the tag of seal and the MAC of open need L >= 16 (cipherstate.c:305-318 / :379-390) */
-        if (L < TR_MAC_LEN) {
+        if (L < min_len) {
             w.stop = NOISE_ERROR_INVALID_LENGTH;
             break;
         }
@@ -106,6 +114,48 @@ TR_FN bool tr_slot(const uint32_t *slots, uint32_t j, uint32_t n, uint32_t *i)
 {
     *i = slots ? slots[j] : j;
     return *i < n;
+}
+
+/* ------------------------------------------------- the anti-replay window
+   Section 11.  The state of one slot: top is the highest accepted counter
+   + 1 (0: nothing accepted yet); bit c % 1024 of seen says counter c was
+   accepted, for the 1024 counters top - 1024 .. top - 1.  The layout is what
+   noise_aead_dev_transport_replay hands out. */
+struct TrReplay {
+    uint64_t top;
+    uint64_t seen[TR_REPLAY_WORDS];
+};
+
+/* Whether counter c is fresh against the window: not 2^64 - 1 (the CipherState
+   never uses that nonce), not older than the window, not seen.  Reads only. */
+TR_FN bool tr_replay_check(const TrReplay *w, uint64_t c)
+{
+    if (c == TR_NONCE_LIMIT) return false;
+    if (c >= w->top) return true;
+    if (w->top - c > TR_REPLAY_BITS) return false;
+    return !((w->seen[(c / 64) % TR_REPLAY_WORDS] >> (c % 64)) & 1);
+}
+
+/* Counter c, which tr_replay_check found fresh, is accepted.  At or above top
+   the window moves: the bits of the counters top .. c - 1, which nobody has
+   seen, are cleared (all of them when the jump is a window or more), and top
+   becomes c + 1.  Then c's bit is set. */
+TR_FN void tr_replay_accept(TrReplay *w, uint64_t c)
+{
+    if (c >= w->top) {
+        if (c - w->top >= TR_REPLAY_BITS) {
+            for (uint32_t q = 0; q < TR_REPLAY_WORDS; ++q) w->seen[q] = 0;
+        } else {
+            for (uint64_t x = w->top; x < c;) { /* a word's share of top .. c - 1 at a time; c <= 2^64 - 2 */
+                const uint64_t bit = x % 64, span = c - x < 64 - bit ? c - x : 64 - bit;
+                const uint64_t mask = (span == 64 ? ~0ull : (1ull << span) - 1) << bit;
+                w->seen[(x / 64) % TR_REPLAY_WORDS] &= ~mask;
+                x += span;
+            }
+        }
+        w->top = c + 1;
+    }
+    w->seen[(c / 64) % TR_REPLAY_WORDS] |= 1ull << (c % 64);
 }
 
 /* --------------------------------------------------------- argument checks
@@ -187,6 +237,31 @@ inline int tr_check_call_of(const void *tr, uint32_t n, uint32_t object_max_fram
     if (tr_ranges_meet(d_result, rb, d_off, (tr_u128)8 * m) || tr_ranges_meet(d_result, rb, d_len, (tr_u128)4 * m) ||
         tr_ranges_meet(d_result, rb, d_slots, (tr_u128)4 * m))
         return NOISE_ERROR_INVALID_PARAM;
+    return NOISE_ERROR_NONE;
+}
+
+/* ---- datagram transport (section 11), in the order of the header.
+   result_bytes: of one entry's result (16 for the seal, 24 for the open);
+   open: d_frame_status is an argument too, [d_frame_status, + the call's cap). */
+inline int tr_check_datagrams(const void *tr, uint32_t n, uint32_t object_max_frames, const void *d_slots, uint32_t m,
+                              uint32_t max_frames, const void *d_wire, const void *d_off, const void *d_len,
+                              const void *d_result, uint32_t result_bytes, bool open, const void *d_frame_status)
+{
+    if (!tr) return NOISE_ERROR_INVALID_PARAM;
+    if (!m) return NOISE_ERROR_NONE;
+    if (m > n) return NOISE_ERROR_INVALID_PARAM;
+    if (!d_wire || !d_off || !d_len || !d_result || (open && !d_frame_status)) return NOISE_ERROR_INVALID_PARAM;
+    if (max_frames > object_max_frames) return NOISE_ERROR_INVALID_PARAM;
+    const tr_u128 rb = (tr_u128)result_bytes * m, ob = (tr_u128)8 * m, lb = (tr_u128)4 * m, sb = d_slots ? lb : 0;
+    if (tr_ranges_meet(d_result, rb, d_off, ob) || tr_ranges_meet(d_result, rb, d_len, lb) ||
+        tr_ranges_meet(d_result, rb, d_slots, sb))
+        return NOISE_ERROR_INVALID_PARAM;
+    if (open) {
+        const tr_u128 fb = max_frames ? max_frames : object_max_frames;
+        if (tr_ranges_meet(d_frame_status, fb, d_off, ob) || tr_ranges_meet(d_frame_status, fb, d_len, lb) ||
+            tr_ranges_meet(d_frame_status, fb, d_slots, sb) || tr_ranges_meet(d_frame_status, fb, d_result, rb))
+            return NOISE_ERROR_INVALID_PARAM;
+    }
     return NOISE_ERROR_NONE;
 }
 

@@ -200,6 +200,9 @@ def lib() -> C.CDLL:
         "noise_aead_dev_transport_seal_frames_of": (i, [vp, vp, C.c_uint32, C.c_uint32, vp, vp, vp, vp, vp]),
         "noise_aead_dev_transport_open_frames_of": (i, [vp, vp, C.c_uint32, C.c_uint32, vp, vp, vp, vp, vp]),
         "noise_aead_dev_transport_echo_frames_of": (i, [vp, vp, C.c_uint32, C.c_uint32, vp, vp, vp, vp, vp]),
+        "noise_aead_dev_transport_seal_datagrams": (i, [vp, vp, C.c_uint32, C.c_uint32, vp, vp, vp, vp, vp]),
+        "noise_aead_dev_transport_open_datagrams": (i, [vp, vp, C.c_uint32, C.c_uint32, vp, vp, vp, vp, vp, vp]),
+        "noise_aead_dev_transport_replay": (vp, [vp, P(C.c_uint32)]),
         "noise_aead_debug_transport_ctx": (vp, [vp, i, P(sz)]),
         "noise_strerror": (i, [i, C.c_char_p, sz]),
         "noise_perror": (None, [C.c_char_p, i]),
@@ -665,6 +668,29 @@ def dev_transport_echo_frames_of(tr: int, *, slots: int, m: int, max_frames: int
                                  result: int, stream: int = 0) -> int:
     return _transport_call_of(lib().noise_aead_dev_transport_echo_frames_of, tr, slots, m, max_frames, wire, off, length,
                               result, stream)
+
+
+# ---- datagram transport (section 11): every frame carries its counter; a
+# slot list of 0 means entry j is slot j.  The open's result is m
+# NoiseAeadDatagramResult (frames, consumed, error, accepted, 64-bit first)
+
+def dev_transport_seal_datagrams(tr: int, *, slots: int = 0, m: int, max_frames: int = 0, wire: int, off: int, length: int,
+                                 result: int, stream: int = 0) -> int:
+    return lib().noise_aead_dev_transport_seal_datagrams(tr, slots or None, m, max_frames, wire or None, off or None,
+                                                         length or None, result or None, stream or None)
+
+
+def dev_transport_open_datagrams(tr: int, *, slots: int = 0, m: int, max_frames: int = 0, wire: int, off: int, length: int,
+                                 result: int, frame_status: int, stream: int = 0) -> int:
+    return lib().noise_aead_dev_transport_open_datagrams(tr, slots or None, m, max_frames, wire or None, off or None,
+                                                         length or None, result or None, frame_status or None,
+                                                         stream or None)
+
+
+def dev_transport_replay(tr: int):
+    """(device pointer of the n windows {uint64 top; uint64 seen[16]}, or 0; the window size in bits)"""
+    bits = C.c_uint32(0)
+    return lib().noise_aead_dev_transport_replay(tr, C.byref(bits)) or 0, bits.value
 
 
 def debug_transport_ctx(tr: int, direction: int):
