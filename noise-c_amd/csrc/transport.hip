@@ -51,11 +51,11 @@
  *
  * Datagram transport (section 11): every frame carries its counter, every
  * frame is judged alone, and each slot has an anti-replay window (TrReplay,
- * transport_plan.h) that tr_mark zeroes with the nonces.  A call is
- *   tr_count<24>, the scan, then
- *   tr_build_datagrams   one lane per entry.  Seal: writes frame k's counter
- *                send + k and its descriptor (in place behind the counter),
- *                and commits as tr_build does.  Open: reads each frame's
+ * transport_plan.h) that tr_mark zeroes with the nonces.  A call is the same
+ * run (run(), below) under the other framing: tr_count<TR_DATAGRAM>, the scan,
+ *   tr_build<TR_DATAGRAM>  the one build kernel with the datagram emitter.
+ *                Seal: writes frame k's counter send + k and its descriptor
+ *                (in place behind the counter).  Open: reads each frame's
  *                counter, asks tr_replay_check of the window as it stands, and
  *                writes the descriptor under that counter or refused_rec(): a
  *                replay costs no AEAD work;
@@ -82,12 +82,15 @@ constexpr uint32_t TR_WIDE_BLOCK = 256;
 constexpr size_t TR_ALIGN = 256; /* of the parts of the object's device allocation */
 
 enum TrMode : uint32_t { TR_SEAL = 0, TR_OPEN = 1, TR_ECHO = 2 };
+/* how a session's frames are laid out, named by the smallest L of a frame;
+   the datagram calls are TR_SEAL or TR_OPEN only */
+enum TrFraming : uint32_t { TR_STREAM = TR_MAC_LEN, TR_DATAGRAM = TR_DATAGRAM_MIN };
 
 struct TrArgs {
-    const uint8_t *wire;
+    uint8_t *wire;               /* written only by the datagram seal: its counters */
     const uint64_t *off;
     const uint32_t *len;
-    NoiseAeadTransportResult *result;
+    NoiseAeadTransportResult *result; /* not the datagram open's */
     uint64_t *send, *recv;       /* the nonces */
     uint64_t *count, *base;      /* per session: frames of the uncapped walk, their exclusive sum */
     uint32_t *frames, *consumed; /* per session, after the cap */
@@ -99,6 +102,10 @@ struct TrArgs {
     const uint32_t *slots;       /* the call's list (null: entry j is slot j) of m entries */
     const uint8_t *keyed;        /* per slot: 1 keyed, 0 not */
     uint32_t m;
+    /* the datagram calls'; null for the stream calls */
+    TrReplay *replay;            /* per slot */
+    NoiseAeadDatagramResult *datagram_result; /* the open's */
+    uint8_t *frame_status;       /* the open's, one byte per walked frame of the call */
 };
 
 /* entry j's slot; false (nothing of a slot may be touched) when it is out of range or unkeyed */
@@ -107,6 +114,7 @@ TR_DEV bool tr_live(const TrArgs &a, uint32_t j, uint32_t *i)
     return tr_slot(a.slots, j, a.n, i) && a.keyed[*i];
 }
 
+/* the nonce the walk of a stream starts under */
 TR_DEV uint64_t tr_start_nonce(const TrArgs &a, uint32_t i)
 {
     if (a.mode == TR_SEAL) return a.send[i];
@@ -114,8 +122,7 @@ TR_DEV uint64_t tr_start_nonce(const TrArgs &a, uint32_t i)
     return a.send[i] > a.recv[i] ? a.send[i] : a.recv[i];
 }
 
-/* MIN_L: the smallest L of a frame, 16, or 24 for the datagram calls, whose open walks under no nonce */
-template <uint32_t MIN_L>
+template <TrFraming F>
 __global__ __launch_bounds__(TR_BLOCK) void tr_count(TrArgs a)
 {
     const uint32_t j = blockIdx.x * TR_BLOCK + threadIdx.x;
@@ -123,50 +130,108 @@ __global__ __launch_bounds__(TR_BLOCK) void tr_count(TrArgs a)
     uint32_t i;
     uint64_t count = 0;
     if (tr_live(a, j, &i)) {
-        const uint64_t nonce = MIN_L == TR_DATAGRAM_MIN && a.mode == TR_OPEN ? 0 : tr_start_nonce(a, i);
-        count = tr_walk(a.wire + a.off[j], a.len[j], nonce, TR_NO_BUDGET, TrNoEmit(), MIN_L).frames;
+        const uint64_t nonce = F == TR_DATAGRAM && a.mode == TR_OPEN ? 0 : tr_start_nonce(a, i); /* a datagram open walks under none */
+        count = tr_walk(a.wire + a.off[j], a.len[j], nonce, TR_NO_BUDGET, TrNoEmit(), F).frames;
     }
     a.count[j] = count;
 }
 
+/* lane t's share of the padding: the descriptors from the call's last frame
+   up to its cap are ones the ragged kernels refuse */
+TR_DEV void tr_pad(const TrArgs &a, RecDesc *recs, uint64_t t)
+{
+    const uint64_t all = a.base[a.m - 1] + a.count[a.m - 1];
+    const uint64_t total = all < a.max_frames ? all : a.max_frames;
+    if (t >= total && t < a.max_frames) recs[t] = refused_rec();
+}
+
+/* a frame's descriptor: len bytes in place at `at` of the wire, no AD */
+TR_DEV RecDesc tr_rec(uint64_t at, uint64_t nonce, uint64_t ctx_off, uint32_t len)
+{
+    RecDesc d;
+    d.in_off = d.out_off = at;
+    d.nonce = nonce;
+    d.ctx_off = ctx_off;
+    d.ad_off = 0;
+    d.len = len;
+    d.ad_len = 0;
+    return d;
+}
+
+/* a stream frame k: under nonce + k */
 struct TrEmit {
     RecDesc *recs;
     uint64_t wire_off, nonce, ctx_off;
     TR_DEV void operator()(uint64_t k, uint64_t body, uint32_t L) const
     {
-        RecDesc d;
-        d.in_off = d.out_off = wire_off + body;
-        d.nonce = nonce + k;
-        d.ctx_off = ctx_off;
-        d.ad_off = 0;
-        d.len = L - TR_MAC_LEN;
-        d.ad_len = 0;
-        recs[k] = d;
+        recs[k] = tr_rec(wire_off + body, nonce + k, ctx_off, L - TR_MAC_LEN);
     }
 };
 
+constexpr uint8_t TR_FRAME_REPLAY = 5;
+
+/* nothing of a stream is aligned */
+TR_DEV uint64_t tr_load_counter(const uint8_t *p)
+{
+    uint64_t c = 0;
+    for (int b = 0; b < 8; ++b) c |= (uint64_t)p[b] << (8 * b);
+    return c;
+}
+
+/* a datagram frame k: behind the counter, under that counter; the seal writes
+   send + k there first, the open refuses what the window refuses */
+struct TrDatagramEmit {
+    RecDesc *recs;
+    uint8_t *stream;             /* the entry's */
+    uint64_t wire_off, send, ctx_off;
+    const TrReplay *window;      /* null: a seal */
+    TR_DEV void operator()(uint64_t k, uint64_t body, uint32_t L) const
+    {
+        uint64_t c = send + k;
+        if (window)
+            c = tr_load_counter(stream + body);
+        else
+            for (int b = 0; b < 8; ++b) stream[body + b] = (uint8_t)(c >> (8 * b));
+        const bool fresh = !window || tr_replay_check(window, c);
+        recs[k] = fresh ? tr_rec(wire_off + body + TR_COUNTER_LEN, c, ctx_off, L - TR_DATAGRAM_MIN) : refused_rec();
+    }
+};
+
+template <TrFraming F>
 __global__ __launch_bounds__(TR_BLOCK) void tr_build(TrArgs a)
 {
     const uint64_t t = (uint64_t)blockIdx.x * TR_BLOCK + threadIdx.x;
-    const uint64_t all = a.base[a.m - 1] + a.count[a.m - 1];
-    const uint64_t total = all < a.max_frames ? all : a.max_frames;
-    if (t >= total && t < a.max_frames) a.recs[t] = refused_rec();
+    tr_pad(a, a.recs, t);
     if (t >= a.m) return;
     const uint32_t j = (uint32_t)t;
+    const bool seal = a.mode == TR_SEAL;
     uint32_t i;
-    if (!tr_live(a, j, &i)) { /* before anything else, cut or not (wire.c:199); tr_commit leaves the entry alone */
-        const NoiseAeadTransportResult r = {0, 0, i < a.n ? NOISE_ERROR_INVALID_STATE : NOISE_ERROR_INVALID_PARAM, 0};
-        a.result[j] = r;
+    if (!tr_live(a, j, &i)) { /* before anything else, cut or not (wire.c:199); the commit leaves the entry alone */
+        const int32_t error = i < a.n ? NOISE_ERROR_INVALID_STATE : NOISE_ERROR_INVALID_PARAM;
+        if (F == TR_DATAGRAM && !seal) {
+            const NoiseAeadDatagramResult r = {0, 0, error, 0, 0};
+            a.datagram_result[j] = r;
+        } else {
+            const NoiseAeadTransportResult r = {0, 0, error, 0};
+            a.result[j] = r;
+        }
         return;
     }
     bool cut;
     const uint64_t base = a.base[j], budget = tr_cap(base, a.count[j], a.max_frames, &cut);
+    const bool walk = budget || !cut;
     /* the session's context: send contexts first, then the receive ones */
-    const bool seal = a.mode == TR_SEAL;
-    const TrEmit emit = {a.recs + base, a.off[j], seal ? a.send[i] : a.recv[i],
-                         (seal ? (uint64_t)i : (uint64_t)a.n + i) * a.ctx_bytes};
+    const uint64_t ctx_off = (seal ? (uint64_t)i : (uint64_t)a.n + i) * a.ctx_bytes;
+    uint8_t *stream = a.wire + a.off[j];
     TrWalk w = {0, 0, NOISE_ERROR_NONE};
-    if (budget || !cut) w = tr_walk(a.wire + a.off[j], a.len[j], tr_start_nonce(a, i), budget, emit);
+    if constexpr (F == TR_STREAM) {
+        const TrEmit emit = {a.recs + base, a.off[j], seal ? a.send[i] : a.recv[i], ctx_off};
+        if (walk) w = tr_walk(stream, a.len[j], tr_start_nonce(a, i), budget, emit, F);
+    } else {
+        const uint64_t send = seal ? a.send[i] : 0; /* the open neither walks under a nonce nor reads one */
+        const TrDatagramEmit emit = {a.recs + base, stream, a.off[j], send, ctx_off, seal ? nullptr : a.replay + i};
+        if (walk) w = tr_walk(stream, a.len[j], send, budget, emit, F);
+    }
     if (cut) w.stop = NOISE_ERROR_NONE;
     if (seal) {
         a.send[i] += w.frames;
@@ -183,11 +248,7 @@ __global__ __launch_bounds__(TR_BLOCK) void tr_commit(TrArgs a)
 {
     const uint64_t t = (uint64_t)blockIdx.x * TR_BLOCK + threadIdx.x;
     const bool echo = a.mode == TR_ECHO;
-    if (echo) {
-        const uint64_t all = a.base[a.m - 1] + a.count[a.m - 1];
-        const uint64_t total = all < a.max_frames ? all : a.max_frames;
-        if (t >= total && t < a.max_frames) a.seal_recs[t] = refused_rec();
-    }
+    if (echo) tr_pad(a, a.seal_recs, t);
     if (t >= a.m) return;
     const uint32_t j = (uint32_t)t;
     uint32_t i;
@@ -218,94 +279,6 @@ __global__ __launch_bounds__(TR_BLOCK) void tr_commit(TrArgs a)
     a.result[j] = r;
 }
 
-/* ---- datagram transport (section 11) */
-
-struct TrDatagramArgs {
-    TrArgs a;                    /* a.result: the seal's; a.mode: TR_SEAL or TR_OPEN */
-    uint8_t *wire;               /* a.wire, to write the seal's counters through */
-    TrReplay *replay;            /* per slot */
-    NoiseAeadDatagramResult *result; /* the open's */
-    uint8_t *frame_status;       /* the open's, one byte per walked frame of the call */
-};
-
-constexpr uint8_t TR_FRAME_REPLAY = 5;
-
-/* nothing of a stream is aligned */
-TR_DEV uint64_t tr_load_counter(const uint8_t *p)
-{
-    uint64_t c = 0;
-    for (int b = 0; b < 8; ++b) c |= (uint64_t)p[b] << (8 * b);
-    return c;
-}
-
-/* frame k's descriptor: in place behind the counter, under that counter; the
-   seal writes send + k there first, the open refuses what the window refuses */
-struct TrDatagramEmit {
-    RecDesc *recs;
-    uint8_t *stream;             /* the entry's */
-    uint64_t wire_off, send, ctx_off;
-    const TrReplay *window;      /* null: a seal */
-    TR_DEV void operator()(uint64_t k, uint64_t body, uint32_t L) const
-    {
-        uint64_t c = send + k;
-        if (window)
-            c = tr_load_counter(stream + body);
-        else
-            for (int b = 0; b < 8; ++b) stream[body + b] = (uint8_t)(c >> (8 * b));
-        RecDesc d = refused_rec();
-        if (!window || tr_replay_check(window, c)) {
-            d.in_off = d.out_off = wire_off + body + TR_COUNTER_LEN;
-            d.nonce = c;
-            d.ctx_off = ctx_off;
-            d.ad_off = 0;
-            d.len = L - TR_DATAGRAM_MIN;
-            d.ad_len = 0;
-        }
-        recs[k] = d;
-    }
-};
-
-__global__ __launch_bounds__(TR_BLOCK) void tr_build_datagrams(TrDatagramArgs g)
-{
-    const TrArgs &a = g.a;
-    const uint64_t t = (uint64_t)blockIdx.x * TR_BLOCK + threadIdx.x;
-    const uint64_t all = a.base[a.m - 1] + a.count[a.m - 1];
-    const uint64_t total = all < a.max_frames ? all : a.max_frames;
-    if (t >= total && t < a.max_frames) a.recs[t] = refused_rec();
-    if (t >= a.m) return;
-    const uint32_t j = (uint32_t)t;
-    const bool seal = a.mode == TR_SEAL;
-    uint32_t i;
-    if (!tr_live(a, j, &i)) {
-        const int32_t error = i < a.n ? NOISE_ERROR_INVALID_STATE : NOISE_ERROR_INVALID_PARAM;
-        if (seal) {
-            const NoiseAeadTransportResult r = {0, 0, error, 0};
-            a.result[j] = r;
-        } else {
-            const NoiseAeadDatagramResult r = {0, 0, error, 0, 0};
-            g.result[j] = r;
-        }
-        return;
-    }
-    bool cut;
-    const uint64_t base = a.base[j], budget = tr_cap(base, a.count[j], a.max_frames, &cut);
-    const uint64_t send = seal ? a.send[i] : 0;
-    const TrDatagramEmit emit = {a.recs + base, g.wire + a.off[j], a.off[j], send,
-                                 (seal ? (uint64_t)i : (uint64_t)a.n + i) * a.ctx_bytes, seal ? nullptr : g.replay + i};
-    TrWalk w = {0, 0, NOISE_ERROR_NONE};
-    if (budget || !cut) w = tr_walk(a.wire + a.off[j], a.len[j], send, budget, emit, TR_DATAGRAM_MIN);
-    if (cut) w.stop = NOISE_ERROR_NONE;
-    if (seal) {
-        a.send[i] = send + w.frames;
-        const NoiseAeadTransportResult r = {(uint32_t)w.frames, (uint32_t)w.consumed, w.stop, 0};
-        a.result[j] = r;
-        return;
-    }
-    a.frames[j] = (uint32_t)w.frames;
-    a.consumed[j] = (uint32_t)w.consumed;
-    a.stop[j] = w.stop;
-}
-
 /* frame k of the entry, in stream order, against the window as the frames before it left it */
 struct TrDatagramJudge {
     const uint8_t *stream, *status; /* the entry's; the AEAD's statuses from the entry's first frame on */
@@ -328,22 +301,21 @@ struct TrDatagramJudge {
     }
 };
 
-__global__ __launch_bounds__(TR_BLOCK) void tr_commit_datagrams(TrDatagramArgs g)
+__global__ __launch_bounds__(TR_BLOCK) void tr_commit_datagrams(TrArgs a)
 {
-    const TrArgs &a = g.a;
     const uint32_t j = blockIdx.x * TR_BLOCK + threadIdx.x;
     if (j >= a.m) return;
     uint32_t i;
-    if (!tr_live(a, j, &i)) return; /* tr_build_datagrams wrote its result; it has no frames */
+    if (!tr_live(a, j, &i)) return; /* tr_build wrote its result; it has no frames */
     const uint32_t frames = a.frames[j];
     const uint64_t base = a.base[j]; /* base + frames <= max_frames (tr_cap) */
     uint32_t accepted = 0;
-    if (frames) { /* the headers and counters are as tr_build_datagrams read them: the same frames again */
-        const TrDatagramJudge judge = {a.wire + a.off[j], a.status + base, g.frame_status + base, g.replay + i, &accepted};
+    if (frames) { /* the headers and counters are as tr_build read them: the same frames again */
+        const TrDatagramJudge judge = {a.wire + a.off[j], a.status + base, a.frame_status + base, a.replay + i, &accepted};
         tr_walk(a.wire + a.off[j], a.len[j], 0, frames, judge, TR_DATAGRAM_MIN);
     }
     const NoiseAeadDatagramResult r = {frames, a.consumed[j], a.stop[j], accepted, base};
-    g.result[j] = r;
+    a.datagram_result[j] = r;
 }
 
 /* ---- keying and un-keying slots (section 10) */
@@ -460,10 +432,14 @@ int scan_counts(const Tr *tr, void *tmp, size_t &bytes, uint32_t m, hipStream_t 
 }
 
 /* One call over the m entries of `slots` (null: the n slots in order) under
-   the cap `cap`; the arguments are checked. */
-int run(Tr *tr, TrMode mode, const uint32_t *slots, uint32_t m, uint32_t cap, uint8_t *d_wire, const uint64_t *d_off,
-        const uint32_t *d_len, NoiseAeadTransportResult *d_result, hipStream_t s)
+   the cap max_frames (0: the object's); the arguments are checked.  d_result
+   is the stream calls' and the datagram seal's, d_datagram_result and
+   d_frame_status are the datagram open's. */
+int run(Tr *tr, TrFraming framing, TrMode mode, const uint32_t *slots, uint32_t m, uint32_t max_frames, uint8_t *d_wire,
+        const uint64_t *d_off, const uint32_t *d_len, NoiseAeadTransportResult *d_result,
+        NoiseAeadDatagramResult *d_datagram_result, uint8_t *d_frame_status, void *stream)
 {
+    hipStream_t s = (hipStream_t)stream;
     size_t bytes = tr->scan_bytes;
     if (m != tr->n) { /* _new carved the scan's scratch for n items */
         size_t need = 0;
@@ -471,12 +447,23 @@ int run(Tr *tr, TrMode mode, const uint32_t *slots, uint32_t m, uint32_t cap, ui
         if (rc1) return rc1;
         if (need > tr->scan_bytes) return NOISE_ERROR_SYSTEM;
     }
-    const TrArgs a = {d_wire, d_off, d_len, d_result, tr->send, tr->recv, tr->count, tr->base, tr->frames, tr->consumed,
-                      tr->stop, tr->recs, tr->seal_recs, tr->status, tr->ctx_bytes, cap, tr->n, mode, slots, tr->keyed, m};
+    const bool datagram = framing == TR_DATAGRAM;
+    const uint32_t cap = max_frames ? max_frames : tr->max_frames;
     const uint32_t most = m > cap ? m : cap; /* tr_build and an echo's tr_commit also pad the descriptors up to the cap */
-    int rc = launch_items(tr_count<TR_MAC_LEN>, m, TR_BLOCK, s, a);
+    TrArgs a = {};
+    a.wire = d_wire; a.off = d_off; a.len = d_len; a.result = d_result;
+    a.send = tr->send; a.recv = tr->recv;
+    a.count = tr->count; a.base = tr->base;
+    a.frames = tr->frames; a.consumed = tr->consumed; a.stop = tr->stop;
+    a.recs = tr->recs; a.seal_recs = tr->seal_recs; a.status = tr->status;
+    a.ctx_bytes = tr->ctx_bytes; a.max_frames = cap;
+    a.n = tr->n; a.mode = mode;
+    a.slots = slots; a.keyed = tr->keyed; a.m = m;
+    a.replay = datagram ? tr->replay : nullptr; /* a stream call has no window to touch */
+    a.datagram_result = d_datagram_result; a.frame_status = d_frame_status;
+    int rc = launch_items(datagram ? tr_count<TR_DATAGRAM> : tr_count<TR_STREAM>, m, TR_BLOCK, s, a);
     if (!rc) rc = scan_counts(tr, tr->scan_tmp, bytes, m, s);
-    if (!rc) rc = launch_items(tr_build, most, TR_BLOCK, s, a);
+    if (!rc) rc = launch_items(datagram ? tr_build<TR_DATAGRAM> : tr_build<TR_STREAM>, most, TR_BLOCK, s, a);
     if (rc) return rc;
     NoiseAeadRagged job = {};
     job.ctx_base = tr->ctx;
@@ -488,6 +475,7 @@ int run(Tr *tr, TrMode mode, const uint32_t *slots, uint32_t m, uint32_t cap, ui
     if (mode == TR_SEAL) return noise_aead_dev_seal_ragged(tr->cipher_id, &job, s);
     rc = noise_aead_dev_open_ragged(tr->cipher_id, &job, s);
     if (rc) return rc;
+    if (datagram) return launch_items(tr_commit_datagrams, m, TR_BLOCK, s, a);
     rc = launch_items(tr_commit, mode == TR_ECHO ? most : m, TR_BLOCK, s, a);
     if (rc || mode == TR_OPEN) return rc;
     job.recs = (const NoiseAeadRecord *)tr->seal_recs;
@@ -501,7 +489,7 @@ int run_all(Tr *tr, TrMode mode, uint8_t *d_wire, const uint64_t *d_off, const u
 {
     const int rc = tr_check_call(tr, tr ? tr->n : 0, d_wire, d_off, d_len, d_result);
     if (rc || !tr->n) return rc;
-    return run(tr, mode, nullptr, tr->n, tr->max_frames, d_wire, d_off, d_len, d_result, (hipStream_t)stream);
+    return run(tr, TR_STREAM, mode, nullptr, tr->n, 0, d_wire, d_off, d_len, d_result, nullptr, nullptr, stream);
 }
 
 /* the calls of section 10: the listed slots, the call's cap */
@@ -511,49 +499,22 @@ int run_of(Tr *tr, TrMode mode, const uint32_t *d_slots, uint32_t m, uint32_t ma
     const int rc = tr_check_call_of(tr, tr ? tr->n : 0, tr ? tr->max_frames : 0, d_slots, m, max_frames, d_wire, d_off,
                                     d_len, d_result);
     if (rc || !m) return rc;
-    return run(tr, mode, d_slots, m, max_frames ? max_frames : tr->max_frames, d_wire, d_off, d_len, d_result,
-               (hipStream_t)stream);
+    return run(tr, TR_STREAM, mode, d_slots, m, max_frames, d_wire, d_off, d_len, d_result, nullptr, nullptr, stream);
 }
 
-/* the calls of section 11: the listed slots (null: entry j is slot j), the
-   call's cap; d_result is the seal's, d_datagram_result and d_frame_status the open's */
+/* the calls of section 11: the listed slots (null: entry j is slot j), the call's cap */
 int run_datagrams(Tr *tr, TrMode mode, const uint32_t *d_slots, uint32_t m, uint32_t max_frames, uint8_t *d_wire,
                   const uint64_t *d_off, const uint32_t *d_len, NoiseAeadTransportResult *d_result,
                   NoiseAeadDatagramResult *d_datagram_result, uint8_t *d_frame_status, void *stream)
 {
     const bool open = mode == TR_OPEN;
-    int rc = tr_check_datagrams(tr, tr ? tr->n : 0, tr ? tr->max_frames : 0, d_slots, m, max_frames, d_wire, d_off, d_len,
-                                open ? (const void *)d_datagram_result : (const void *)d_result,
-                                open ? sizeof(NoiseAeadDatagramResult) : sizeof(NoiseAeadTransportResult), open,
-                                d_frame_status);
+    const int rc = tr_check_datagrams(tr, tr ? tr->n : 0, tr ? tr->max_frames : 0, d_slots, m, max_frames, d_wire, d_off,
+                                      d_len, open ? (const void *)d_datagram_result : (const void *)d_result,
+                                      open ? sizeof(NoiseAeadDatagramResult) : sizeof(NoiseAeadTransportResult), open,
+                                      d_frame_status);
     if (rc || !m) return rc;
-    hipStream_t s = (hipStream_t)stream;
-    size_t bytes = tr->scan_bytes;
-    if (m != tr->n) { /* _new carved the scan's scratch for n items */
-        size_t need = 0;
-        rc = scan_counts(tr, nullptr, need, m, s);
-        if (rc) return rc;
-        if (need > tr->scan_bytes) return NOISE_ERROR_SYSTEM;
-    }
-    const uint32_t cap = max_frames ? max_frames : tr->max_frames;
-    const TrDatagramArgs g = {{d_wire, d_off, d_len, d_result, tr->send, tr->recv, tr->count, tr->base, tr->frames,
-                               tr->consumed, tr->stop, tr->recs, tr->seal_recs, tr->status, tr->ctx_bytes, cap, tr->n,
-                               mode, d_slots, tr->keyed, m},
-                              d_wire, tr->replay, d_datagram_result, d_frame_status};
-    rc = launch_items(tr_count<TR_DATAGRAM_MIN>, m, TR_BLOCK, s, g.a);
-    if (!rc) rc = scan_counts(tr, tr->scan_tmp, bytes, m, s);
-    if (!rc) rc = launch_items(tr_build_datagrams, m > cap ? m : cap, TR_BLOCK, s, g); /* it pads the descriptors up to the cap */
-    if (rc) return rc;
-    NoiseAeadRagged job = {};
-    job.ctx_base = tr->ctx;
-    job.recs = (const NoiseAeadRecord *)tr->recs;
-    job.in = job.out = d_wire;
-    job.ad = d_wire; /* never read: every ad_len is 0 */
-    job.status = tr->status;
-    job.n_records = cap;
-    if (!open) return noise_aead_dev_seal_ragged(tr->cipher_id, &job, s);
-    rc = noise_aead_dev_open_ragged(tr->cipher_id, &job, s);
-    return rc ? rc : launch_items(tr_commit_datagrams, m, TR_BLOCK, s, g);
+    return run(tr, TR_DATAGRAM, mode, d_slots, m, max_frames, d_wire, d_off, d_len, d_result, d_datagram_result,
+               d_frame_status, stream);
 }
 
 /* The object and its one device allocation, zeroed on s: every slot unkeyed,

@@ -182,17 +182,6 @@ inline int tr_check_new(const void *out, int cipher_id, int role, uint32_t n, co
     return NOISE_ERROR_NONE;
 }
 
-/* noise_aead_dev_transport_{seal,open,echo}_frames of an object of n sessions */
-inline int tr_check_call(const void *tr, uint32_t n, const void *d_wire, const void *d_off, const void *d_len,
-                         const void *d_result)
-{
-    if (!tr || !d_wire || !d_off || !d_len || !d_result) return NOISE_ERROR_INVALID_PARAM;
-    const tr_u128 rb = (tr_u128)sizeof(NoiseAeadTransportResult) * n;
-    if (tr_ranges_meet(d_result, rb, d_off, (tr_u128)8 * n) || tr_ranges_meet(d_result, rb, d_len, (tr_u128)4 * n))
-        return NOISE_ERROR_INVALID_PARAM;
-    return NOISE_ERROR_NONE;
-}
-
 /* ---- the session table (section 10), each in the order of the header.  A
    check that returns NOISE_ERROR_NONE with m == 0 means: nothing to launch. */
 
@@ -222,47 +211,64 @@ inline int tr_check_clear_keys(const void *tr, uint32_t n, const void *d_slots, 
     return NOISE_ERROR_NONE;
 }
 
-/* noise_aead_dev_transport_{seal,open,echo}_frames_of on an object of n slots
-   made for object_max_frames records */
-inline int tr_check_call_of(const void *tr, uint32_t n, uint32_t object_max_frames, const void *d_slots, uint32_t m,
-                            uint32_t max_frames, const void *d_wire, const void *d_off, const void *d_len,
-                            const void *d_result)
-{
-    if (!tr) return NOISE_ERROR_INVALID_PARAM;
-    if (!m) return NOISE_ERROR_NONE;
-    if (m > n) return NOISE_ERROR_INVALID_PARAM;
-    if (!d_slots || !d_wire || !d_off || !d_len || !d_result) return NOISE_ERROR_INVALID_PARAM;
-    if (max_frames > object_max_frames) return NOISE_ERROR_INVALID_PARAM;
-    const tr_u128 rb = (tr_u128)sizeof(NoiseAeadTransportResult) * m;
-    if (tr_ranges_meet(d_result, rb, d_off, (tr_u128)8 * m) || tr_ranges_meet(d_result, rb, d_len, (tr_u128)4 * m) ||
-        tr_ranges_meet(d_result, rb, d_slots, (tr_u128)4 * m))
-        return NOISE_ERROR_INVALID_PARAM;
-    return NOISE_ERROR_NONE;
-}
+/* ---- the frame calls of sections 9 to 11: one set of rules, in the order of
+   the header.  The form says what a call takes: TR_FORM_ALL (section 9) has no
+   list and is about all n slots, and looks at its pointers even when n == 0;
+   TR_FORM_OF (section 10) needs its list; TR_FORM_DATAGRAM (section 11) may
+   have one.  For the last two m == 0 means: nothing to launch.
+   result_bytes: of one entry's result; d_frame_status, the datagram open's,
+   is an argument when frame_status is set: [d_frame_status, + the call's cap). */
+enum TrForm { TR_FORM_ALL, TR_FORM_OF, TR_FORM_DATAGRAM };
 
-/* ---- datagram transport (section 11), in the order of the header.
-   result_bytes: of one entry's result (16 for the seal, 24 for the open);
-   open: d_frame_status is an argument too, [d_frame_status, + the call's cap). */
-inline int tr_check_datagrams(const void *tr, uint32_t n, uint32_t object_max_frames, const void *d_slots, uint32_t m,
-                              uint32_t max_frames, const void *d_wire, const void *d_off, const void *d_len,
-                              const void *d_result, uint32_t result_bytes, bool open, const void *d_frame_status)
+inline int tr_check_frames(TrForm form, const void *tr, uint32_t n, uint32_t object_max_frames, const void *d_slots,
+                           uint32_t m, uint32_t max_frames, const void *d_wire, const void *d_off, const void *d_len,
+                           const void *d_result, uint32_t result_bytes, bool frame_status, const void *d_frame_status)
 {
     if (!tr) return NOISE_ERROR_INVALID_PARAM;
-    if (!m) return NOISE_ERROR_NONE;
+    if (!m && form != TR_FORM_ALL) return NOISE_ERROR_NONE;
     if (m > n) return NOISE_ERROR_INVALID_PARAM;
-    if (!d_wire || !d_off || !d_len || !d_result || (open && !d_frame_status)) return NOISE_ERROR_INVALID_PARAM;
+    if ((form == TR_FORM_OF && !d_slots) || !d_wire || !d_off || !d_len || !d_result || (frame_status && !d_frame_status))
+        return NOISE_ERROR_INVALID_PARAM;
     if (max_frames > object_max_frames) return NOISE_ERROR_INVALID_PARAM;
     const tr_u128 rb = (tr_u128)result_bytes * m, ob = (tr_u128)8 * m, lb = (tr_u128)4 * m, sb = d_slots ? lb : 0;
     if (tr_ranges_meet(d_result, rb, d_off, ob) || tr_ranges_meet(d_result, rb, d_len, lb) ||
         tr_ranges_meet(d_result, rb, d_slots, sb))
         return NOISE_ERROR_INVALID_PARAM;
-    if (open) {
+    if (frame_status) {
         const tr_u128 fb = max_frames ? max_frames : object_max_frames;
         if (tr_ranges_meet(d_frame_status, fb, d_off, ob) || tr_ranges_meet(d_frame_status, fb, d_len, lb) ||
             tr_ranges_meet(d_frame_status, fb, d_slots, sb) || tr_ranges_meet(d_frame_status, fb, d_result, rb))
             return NOISE_ERROR_INVALID_PARAM;
     }
     return NOISE_ERROR_NONE;
+}
+
+/* noise_aead_dev_transport_{seal,open,echo}_frames of an object of n sessions */
+inline int tr_check_call(const void *tr, uint32_t n, const void *d_wire, const void *d_off, const void *d_len,
+                         const void *d_result)
+{
+    return tr_check_frames(TR_FORM_ALL, tr, n, 0, nullptr, n, 0, d_wire, d_off, d_len, d_result,
+                           sizeof(NoiseAeadTransportResult), false, nullptr);
+}
+
+/* noise_aead_dev_transport_{seal,open,echo}_frames_of on an object of n slots
+   made for object_max_frames records */
+inline int tr_check_call_of(const void *tr, uint32_t n, uint32_t object_max_frames, const void *d_slots, uint32_t m,
+                            uint32_t max_frames, const void *d_wire, const void *d_off, const void *d_len,
+                            const void *d_result)
+{
+    return tr_check_frames(TR_FORM_OF, tr, n, object_max_frames, d_slots, m, max_frames, d_wire, d_off, d_len, d_result,
+                           sizeof(NoiseAeadTransportResult), false, nullptr);
+}
+
+/* noise_aead_dev_transport_{seal,open}_datagrams: result_bytes is 16 for the
+   seal, 24 for the open, which also takes d_frame_status */
+inline int tr_check_datagrams(const void *tr, uint32_t n, uint32_t object_max_frames, const void *d_slots, uint32_t m,
+                              uint32_t max_frames, const void *d_wire, const void *d_off, const void *d_len,
+                              const void *d_result, uint32_t result_bytes, bool open, const void *d_frame_status)
+{
+    return tr_check_frames(TR_FORM_DATAGRAM, tr, n, object_max_frames, d_slots, m, max_frames, d_wire, d_off, d_len,
+                           d_result, result_bytes, open, d_frame_status);
 }
 
 } // namespace na
