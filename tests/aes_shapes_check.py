@@ -26,11 +26,9 @@ import torch  # noqa: E402
 
 import noise_aead as aead  # noqa: E402
 import oracle as O  # noqa: E402
-from test_gpu_parity import (AES, FLAG_CT_GHASH, dev, duplex_cases_check, prepare,  # noqa: E402
-                             stream, sync)
+from aead_gpu import duplex_cases_check  # noqa: E402
+from gpu_support import AES, FLAG_CT_GHASH, REC_DT, dev, prepare, stream, sync  # noqa: E402
 
-REC_DT = [("in_off", "<u8"), ("out_off", "<u8"), ("nonce", "<u8"), ("ctx_off", "<u8"),
-          ("ad_off", "<u8"), ("len", "<u4"), ("ad_len", "<u4")]
 FIXED_LENS = [0, 15, 16, 17, 1400, 4096]
 AD_SLOT = 32
 # NOISE_AEAD_GCM_SHAPE: threads per workgroup, records per group, lanes per record

@@ -28,10 +28,7 @@ import subprocess
 
 import f25_cases as F
 import x25519_ref as X
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-LIB = os.path.join(ROOT, "noise-c_amd")
-CHECK = os.path.join(LIB, "asan", "dh_check")
+from host_check import LIB, run_check
 ROCM = os.environ.get("ROCM", "/opt/rocm")
 
 
@@ -54,19 +51,14 @@ def test_checker_equals_the_reference_fixture():
 
 
 def test_shared_ladder_and_argument_rules_under_sanitizers():
-    subprocess.run(["make", "-s", "-C", LIB, "dh_check"], check=True)
     cases = X.fixture_cases()
     feed = "".join(f"{c['priv']} {c['pub']} {c['shared']} {c['public']}\n" for c in cases)
-    r = subprocess.run([CHECK], input=feed, capture_output=True, text=True, timeout=120)
-    out = r.stdout[-4000:] + r.stderr[-4000:]
-    assert r.returncode == 0, out
-    assert "AddressSanitizer" not in out and "runtime error" not in out, out
+    r = run_check("dh_check", feed=feed)
     line = [l for l in r.stdout.splitlines() if l.startswith("dh_check:")][-1].split()
     assert int(line[1]) == len(cases) and int(line[3]) > 50000 and line[5] == "0", line
     # a wrong expected value is noticed: the program does compare
     bad = cases[0]["shared"][:-1] + ("0" if cases[0]["shared"][-1] != "0" else "1")
-    r = subprocess.run([CHECK], input=f"{cases[0]['priv']} {cases[0]['pub']} {bad} {cases[0]['public']}\n",
-                       capture_output=True, text=True, timeout=120)
+    r = run_check("dh_check", feed=f"{cases[0]['priv']} {cases[0]['pub']} {bad} {cases[0]['public']}\n", checked=False)
     assert r.returncode == 1 and "FAIL calculate" in r.stderr, r.stdout + r.stderr
 
 
@@ -102,13 +94,9 @@ def test_f25_edge_set_takes_every_named_path():
 
 def test_f25_field_operations_under_sanitizers():
     """Every vector of every operation through the header on the CPU."""
-    subprocess.run(["make", "-s", "-C", LIB, "dh_check"], check=True)
     feed = "".join(F.check_lines(op) for op in F.OPS)
     total = sum(len(F.vectors(op)) for op in F.OPS)
-    r = subprocess.run([CHECK], input=feed, capture_output=True, text=True, timeout=120)
-    out = r.stdout[-4000:] + r.stderr[-4000:]
-    assert r.returncode == 0, out
-    assert "AddressSanitizer" not in out and "runtime error" not in out, out
+    r = run_check("dh_check", feed=feed)
     lines = r.stdout.splitlines()
     f25 = [l for l in lines if l.startswith("dh_check f25:")][-1].split()
     assert int(f25[2]) == total and f25[4] == "0", f25
@@ -119,12 +107,11 @@ def test_f25_field_operations_under_sanitizers():
     for op in ("sub", "freeze"):
         a, b = F.vectors(op)[5]
         wrong = (F.expected(op, a, b) + 1) % F.P
-        r = subprocess.run([CHECK], input=f"f25 {op} {F.le32(a).hex()} {F.le32(b).hex()} {F.le32(wrong).hex()}\n",
-                           capture_output=True, text=True, timeout=120)
+        r = run_check("dh_check", feed=f"f25 {op} {F.le32(a).hex()} {F.le32(b).hex()} {F.le32(wrong).hex()}\n", checked=False)
         assert r.returncode == 1 and f"FAIL f25 {op}" in r.stderr, r.stdout + r.stderr
         assert "dh_check f25: 1 vectors 1 failures" in r.stdout
     # and a line it cannot read is a failure, not a skipped vector
-    r = subprocess.run([CHECK], input="f25 cube 00 00 00\n", capture_output=True, text=True, timeout=120)
+    r = run_check("dh_check", feed="f25 cube 00 00 00\n", checked=False)
     assert r.returncode == 1 and "FAIL input" in r.stderr, r.stdout + r.stderr
 
 

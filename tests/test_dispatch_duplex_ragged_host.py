@@ -19,10 +19,10 @@ have run since before the duplex existed:
  - check_duplex_ragged at the span edges: status arrays that touch, that meet
    by one byte, at the top of the address space.
 """
-from test_dispatch_host import run_check
+from host_check import run_check
 
 
 def test_duplex_ragged_plans_under_sanitizers():
-    line = [l for l in run_check("--duplex-ragged").splitlines() if l.startswith("dispatch_check:")][-1].split()
+    line = [l for l in run_check("dispatch_check", "--duplex-ragged").stdout.splitlines() if l.startswith("dispatch_check:")][-1].split()
     assert int(line[1]) > 10000 and line[3].rstrip(",") == "0", line
     assert int(line[5]) > 1000, line  # and the enumeration reached shared plans

@@ -17,32 +17,21 @@ before dispatch.h (the launchers' own choices, printed where they launched).
 """
 import gzip
 import os
-import subprocess
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-LIB = os.path.join(ROOT, "noise-c_amd")
-CHECK = os.path.join(LIB, "asan", "dispatch_check")
+from host_check import ROOT, run_check
+
 GOLDEN = os.path.join(ROOT, "tests", "golden", "dispatch_plans.txt.gz")
 
 
-def run_check(*args):
-    subprocess.run(["make", "-s", "-C", LIB, "dispatch_check"], check=True)
-    r = subprocess.run([CHECK, *args], capture_output=True, text=True, timeout=120)
-    out = r.stdout[-4000:] + r.stderr[-4000:]
-    assert r.returncode == 0, out
-    assert "AddressSanitizer" not in out and "runtime error" not in out, out
-    return r.stdout
-
-
 def test_job_checks_under_sanitizers():
-    line = [l for l in run_check().splitlines() if l.startswith("dispatch_check:")][-1].split()
+    line = [l for l in run_check("dispatch_check").stdout.splitlines() if l.startswith("dispatch_check:")][-1].split()
     # the enumeration alone is over a million jobs
     assert int(line[1]) > 1000000 and line[3] == "0", line
 
 
 def test_plan_table_matches_the_recorded_one():
     want = gzip.open(GOLDEN, "rt").read().splitlines()
-    got = run_check("--table").splitlines()
+    got = run_check("dispatch_check", "--table").stdout.splitlines()
     assert len(want) > 3000
     for n, (g, w) in enumerate(zip(got, want), 1):
         assert g == w, f"line {n}:\n got  {g}\n want {w}"

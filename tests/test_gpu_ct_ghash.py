@@ -18,7 +18,8 @@ import sys
 import numpy as np
 import pytest
 
-from test_gpu_parity import AES, dev, gpu_uniform, oracle_seal_records, prepare, stream, sync
+from aead_gpu import gpu_uniform, oracle_seal_records
+from gpu_support import AES, dev, prepare, stream, sync
 
 pytestmark = pytest.mark.gpu
 
@@ -150,7 +151,7 @@ grid = json.load(open(sys.argv[3]))
 o = Oracle()
 n = 0
 for c in grid["cases"]:
-    if c["cipher"] != 0x4302:
+    if c["cipher"] != A.AESGCM:
         continue
     st = A.CipherState.new_by_id(c["cipher"])[1]
     st.init_key(bytes.fromhex(c["key"]))

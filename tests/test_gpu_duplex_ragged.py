@@ -42,14 +42,12 @@ if __name__ == "__main__":  # the child process: what conftest.py does for pytes
     sys.path[:0] = [HERE, ROOT, os.path.join(ROOT, "oracle"), os.path.join(ROOT, "noise-c_amd")]
 
 import edge_records as E
-from test_gpu_edge_values import _filler, check_family, ru
-from test_gpu_parity import AES, CHACHA, dev, prepare, stream, sync
-from test_gpu_seg import REC_DT
+from aead_gpu import _filler, check_family, crafted_ragged
+from gpu_support import AES, CHACHA, INVALID_PARAM, REC_DT, UNKNOWN_ID, _torch, dev, prepare, stream, sync
+from gpu_support import FLAG_CT_GHASH as CT_GHASH, FLAG_FAST as FAST, FLAG_ONE_PASS as ONE_PASS
 
 pytestmark = pytest.mark.gpu
 
-FAST, CT_GHASH, ONE_PASS = 1, 2, 8
-INVALID_PARAM, UNKNOWN_ID = 0x450B, 0x4502  # NOISE_ID('E', 11), NOISE_ID('E', 2)
 TOO_LONG = 65520
 EDGE_LENS = [0, 1, 15, 16, 17, 63, 64, 65, 1400, 16384]
 AD_CHOICES = [0, 0, 0, 5, 32]
@@ -60,11 +58,6 @@ AD_CHOICES = [0, 0, 0, 5, 32]
 # in a child process.
 def default_on(expect, yflags):
     return expect.startswith("chachapoly_seg_duplex") and bool(yflags & ONE_PASS)
-
-
-def _torch():
-    import torch
-    return torch
 
 
 # ------------------------------------------------------------------ the jobs
@@ -478,24 +471,8 @@ def edge_check(aead, oracle, cipher, recs, checked, lanes, flags, expect, partne
     the seal job beside an ordinary open job): each crafted record opens to its
     plaintext, each of the 128 single-bit tag flips and the first and last
     ciphertext bit is rejected."""
-    torch = _torch()
-    n = len(recs)
-    lens = np.array([len(r["pt"]) for r in recs], dtype=np.int64)
-    slots = np.array([ru(max(int(L), 1) + 16, 64) + 64 for L in lens])
-    offs = np.zeros(n, dtype=np.int64)
-    offs[1:] = np.cumsum(slots)[:-1]
-    total = int(offs[-1] + slots[-1]) + 256
-    keys = np.frombuffer(b"".join(r["key"] for r in recs), dtype=np.uint8).reshape(n, 32).copy()
-    ctx, _k = prepare(aead, cipher, keys)
-    d = np.zeros(n, dtype=REC_DT)
-    d["in_off"] = d["out_off"] = offs
-    d["nonce"] = np.array([r["nonce"] for r in recs], dtype=np.uint64)
-    d["ctx_off"] = np.arange(n, dtype=np.uint64) * aead.dev_ctx_bytes(cipher)
-    d["ad_off"] = np.arange(n, dtype=np.uint64) * 64
-    d["len"] = lens
-    d["ad_len"] = [len(r["ad"]) for r in recs]
-    d_recs = dev(d.view(np.uint8))
-    d_ad = dev(E.layout(recs, "ad", [64 * i for i in range(n)], 64 * n + 64))
+    torch, n = _torch(), len(recs)
+    offs, total, (ctx, _k), d_recs, d_ad = crafted_ragged(aead, cipher, recs, True)
     PX, PY = partner
 
     def run(open_, inplace, buf, init):

@@ -24,110 +24,13 @@ import numpy as np
 import pytest
 
 import edge_records as E
+from aead_gpu import FLIPS, _filler, check_family, crafted_ragged, flip_at
 from edge_records import AES, CHACHA
-from test_gpu_parity import (FLAG_CT_GHASH, FLAG_ONE_PASS, FLAG_VERIFY_FIRST, dev, prepare,
-                             rejected_fill, stream, sync)
+from gpu_support import FLAG_CT_GHASH, FLAG_FAST, FLAG_ONE_PASS, FLAG_VERIFY_FIRST, _torch, dev, prepare, ru, stream, sync
 
 pytestmark = pytest.mark.gpu
 
-REC_DT = [("in_off", "<u8"), ("out_off", "<u8"), ("nonce", "<u8"), ("ctx_off", "<u8"),
-          ("ad_off", "<u8"), ("len", "<u4"), ("ad_len", "<u4")]
 AD_STRIDE = 48
-FLAG_FAST = 1
-
-
-def _torch():
-    import torch
-    return torch
-
-
-def ru(x, m):
-    return (x + m - 1) // m * m
-
-
-FLIPS = [("tag", i) for i in range(128)] + [("ct", "first"), ("ct", "last"), ("ct", "partial")]
-
-
-def flip_at(flip, L):
-    """(byte, bit) of one flip of the matrix in a record of L bytes, or None
-    where the record has no such bit: tag bit i; the first ciphertext bit; the
-    last one; bit 0 of the last byte of a partial block."""
-    kind, which = flip
-    if kind == "tag":
-        return L + which // 8, which % 8
-    if L == 0 or (which == "partial" and L % 16 == 0):
-        return None
-    return (0, 0) if which == "first" else (L - 1, 7 if which == "last" else 0)
-
-
-def flip_rounds(lens, odd, checked):
-    """The matrix as rounds of {record: (byte, bit)}: every flip that some
-    checked record has a bit for lands in a record of `odd`, chosen by its
-    length (the ciphertext flips first, they fit fewer records); the records
-    between stay as crafted."""
-    pending = [f for f in reversed(FLIPS) if any(flip_at(f, lens[i]) for i in checked)]
-    assert len(pending) >= 128
-    n_flips, rounds = len(pending), []
-    while pending:
-        flipped = {}
-        for i in odd:
-            f = next((f for f in pending if flip_at(f, lens[i])), None)
-            if f is not None:
-                pending.remove(f)
-                flipped[i] = flip_at(f, lens[i])
-        assert flipped, ("no flipped record has a bit for", pending)
-        rounds.append(flipped)
-    assert sum(len(r) for r in rounds) == n_flips
-    return rounds
-
-
-def check_family(recs, run, ct_offs, pt_offs, ip_offs, sizes, rej, checked=None, what=""):
-    """(a)-(c) of the module docstring over the records `checked` (default:
-    all).  run(open_, inplace, buf, init) -> (out, status): one launch over a
-    host image of the input (records at ct_offs for an open, pt_offs for a
-    seal, ip_offs in place) whose out-of-place output starts filled with init.
-    sizes = (bytes of a CT-side image, of a PT-side one, of an in-place one)."""
-    checked = list(range(len(recs))) if checked is None else checked
-    lens = [len(r["pt"]) for r in recs]
-    ct_total, pt_total, ip_total = sizes
-
-    def opened(out, st, offs, flipped, given, init, inplace):
-        for i in checked:
-            o, L, lab = int(offs[i]), lens[i], (what, i, lens[i], recs[i]["label"], flipped.get(i))
-            if i in flipped:
-                assert st[i] == 1, ("flipped record accepted",) + lab
-                if inplace:
-                    assert bytes(out[o:o + L + 16]) == bytes(given[o:o + L + 16]), ("rejected in place",) + lab
-                else:
-                    assert np.all(out[o:o + L] == init), ("rejected output",) + lab
-            else:
-                assert st[i] == 0, ("crafted record rejected",) + lab
-                assert bytes(out[o:o + L]) == recs[i]["pt"], ("plaintext",) + lab
-
-    def sealed(out, offs):
-        for i in checked:
-            o, L = int(offs[i]), lens[i]
-            assert bytes(out[o:o + L + 16]) == recs[i]["sealed"], (what, "seal", i, L, recs[i]["label"])
-
-    for inplace in (False, True):
-        c_offs, p_offs = (ip_offs, ip_offs) if inplace else (ct_offs, pt_offs)
-        c_total, p_total = (ip_total, ip_total) if inplace else (ct_total, pt_total)
-        fill = rejected_fill(*rej)
-        ct_img = E.layout(recs, "sealed", c_offs, c_total, 0x11)
-        out, st = run(True, inplace, ct_img, 0x5A)                                   # (a)
-        opened(out, st, p_offs if not inplace else c_offs, {}, ct_img, 0x5A, inplace)
-        out, _ = run(False, inplace, E.layout(recs, "pt", c_offs if inplace else p_offs, p_total, 0x22), 0xA5)
-        sealed(out, c_offs)                                                          # (b)
-        if not inplace and len(checked) == len(recs):  # and not a byte outside the records
-            assert np.array_equal(out[:c_total], E.layout(recs, "sealed", c_offs, c_total, 0xA5)), (what, "stray")
-        odd = checked[1::2]                                                          # (c)
-        for flipped in flip_rounds(lens, odd, checked):
-            img = ct_img.copy()
-            for i, (byte, bit) in flipped.items():
-                img[int(c_offs[i]) + byte] ^= 1 << bit
-            init = 0x5A if fill else 0xC3  # a fill of 0 must differ from the buffer's own start
-            out, st = run(True, inplace, img, init)
-            opened(out, st, p_offs if not inplace else c_offs, flipped, img, init if fill else 0, inplace)
 
 
 # ------------------------------------------------------------------ uniform
@@ -307,25 +210,8 @@ def ragged_check(aead, cipher, recs, checked, fast, lanes, flags, what):
     """recs: crafted records (and unchecked filler), each with a context of
     its own, in slots of one buffer: 64-B aligned ones readable to
     roundup64(len) with room for the tag (FAST) or packed at odd offsets."""
-    torch = _torch()
-    n = len(recs)
-    lens = np.array([len(r["pt"]) for r in recs], dtype=np.int64)
-    slots = np.array([ru(max(int(L), 1) + 16, 64) + 64 if fast else int(L) + 16 + 5 for L in lens])
-    offs = np.zeros(n, dtype=np.int64)
-    offs[1:] = np.cumsum(slots)[:-1]
-    assert not fast or not (offs % 64).any()  # FAST: the caller guarantees 16-byte aligned records
-    total = int(offs[-1] + slots[-1]) + 256
-    keys = np.frombuffer(b"".join(r["key"] for r in recs), dtype=np.uint8).reshape(n, 32).copy()
-    ctx, _k = prepare(aead, cipher, keys)
-    d = np.zeros(n, dtype=REC_DT)
-    d["in_off"] = d["out_off"] = offs
-    d["nonce"] = np.array([r["nonce"] for r in recs], dtype=np.uint64)
-    d["ctx_off"] = np.arange(n, dtype=np.uint64) * aead.dev_ctx_bytes(cipher)
-    d["ad_off"] = np.arange(n, dtype=np.uint64) * 64
-    d["len"] = lens
-    d["ad_len"] = [len(r["ad"]) for r in recs]
-    d_recs = dev(d.view(np.uint8))
-    d_ad = dev(E.layout(recs, "ad", [64 * i for i in range(n)], 64 * n + 64))
+    torch, n = _torch(), len(recs)
+    offs, total, (ctx, _k), d_recs, d_ad = crafted_ragged(aead, cipher, recs, fast)
     seal_flags = (FLAG_FAST if fast else 0) | (flags & FLAG_CT_GHASH)
 
     def run(open_, inplace, buf, init):
@@ -354,18 +240,6 @@ def test_ragged_chacha(aead, gpu, oracle, lanes, fast):
     b = E.ragged_shaped(oracle, "chacha")
     for flags in (0, FLAG_ONE_PASS):
         ragged_check(aead, CHACHA, b.records, None, fast, lanes, flags, ("ragged", lanes, fast, flags))
-
-
-def _filler(n, seed):
-    """n records of at most 64 bytes: random plaintext, random CT || tag (an
-    open rejects them; nothing of theirs is checked)."""
-    rng = np.random.default_rng(seed)
-    out = []
-    for L in rng.integers(0, 65, n):
-        blob = rng.integers(0, 256, int(L) + 16 + 32 + 8, dtype=np.uint8).tobytes()
-        out.append(dict(pt=blob[:L], sealed=blob[:L + 16], key=blob[-40:-8], ad=b"",
-                        nonce=int.from_bytes(blob[-8:], "little") >> 1, label=None))
-    return out
 
 
 @pytest.mark.parametrize("flags", [0, FLAG_ONE_PASS])

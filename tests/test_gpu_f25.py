@@ -15,10 +15,10 @@ canonical bytes; every other result is compared as int(out) mod p, since any
 """
 import functools
 
-import numpy as np
 import pytest
 
 import f25_cases as F
+from gpu_support import dev_bytes
 
 pytestmark = pytest.mark.gpu
 
@@ -26,10 +26,6 @@ pytestmark = pytest.mark.gpu
 @functools.lru_cache(maxsize=None)
 def expectations(op):
     return tuple(F.expected(op, a, b) for a, b in F.vectors(op))
-
-
-def to_device(torch, values):
-    return torch.from_numpy(np.frombuffer(F.pack(values), dtype=np.uint8).copy()).cuda()
 
 
 def launch(aead, torch, op, d_a, d_b, n):
@@ -48,8 +44,8 @@ def run(aead, torch, op, vecs):
     """op over the (a, b) of vecs; d_b is NULL for a one-operand operation.
     Checks that the operands read back as they were."""
     binary = F.OPS[op][1] == 2
-    a = to_device(torch, [v[0] for v in vecs])
-    b = to_device(torch, [v[1] for v in vecs]) if binary else None
+    a = dev_bytes(F.pack([v[0] for v in vecs]))
+    b = dev_bytes(F.pack([v[1] for v in vecs])) if binary else None
     before = (a.clone(), b.clone() if binary else None)
     _, got = launch(aead, torch, op, a.data_ptr(), b.data_ptr() if binary else 0, len(vecs))
     assert torch.equal(a, before[0]), "first operands written"
@@ -94,7 +90,7 @@ def test_inverse_times_operand_is_one_on_the_device(aead, gpu):
     units = [a for a in F.E if a % F.P]
     assert len(units) == len(F.E) - 3 and {0, F.P, 2 * F.P} <= set(F.E)
     n = len(units)
-    d_a = to_device(torch, units)
+    d_a = dev_bytes(F.pack(units))
     inv, inv_values = launch(aead, torch, "invert", d_a.data_ptr(), 0, n)
     _, prod = launch(aead, torch, "mul", inv.data_ptr() + 64, d_a.data_ptr(), n)
     for a, i, x in zip(units, inv_values, prod):

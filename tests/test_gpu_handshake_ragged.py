@@ -19,7 +19,8 @@ import pytest
 
 import handshake_model as M
 import handshake_ragged_model as R
-from test_gpu_handshake import CANARY, Buf, Side, _peek, basic_vector, make_sessions, model_pair
+from gpu_support import peek
+from handshake_gpu import CANARY, Buf, Side, basic_vector, make_sessions, model_pair
 
 pytestmark = pytest.mark.gpu
 N = 67
@@ -542,7 +543,7 @@ def test_host_rules_through_the_library(aead, gpu):
     assert out.read() == [48] * n
     assert Rd(ini, **{**good_r, "msg": p + 1024, "msg_len": out.ptr, "payload_len": got.ptr}, stream=sp) == 0
     assert got.read() == [0] * n
-    assert _peek(torch, A.dev_handshake_status(ini), n) == bytes(n) == _peek(torch, A.dev_handshake_status(res), n)
+    assert peek(A.dev_handshake_status(ini), n) == bytes(n) == peek(A.dev_handshake_status(res), n)
     assert A.dev_handshake_get_action(ini) == A.dev_handshake_get_action(res) == A.ACTION_SPLIT
     assert W(ini, **good_w) == STATE and Rd(res, **good_r) == STATE
     h = room.cpu().numpy()
@@ -590,6 +591,6 @@ def test_a_refused_session_never_becomes_a_transport_session(aead, gpu, oracle):
     slots = torch.arange(N, dtype=torch.int32, device="cuda")
     assert A.dev_transport_set_keys(tr, slots=slots.data_ptr(), m=N, k1=ini.k1.data_ptr(), k2=ini.k2.data_ptr(),
                                     status=A.dev_handshake_status(ini.hs), stream=ini.sp) == 0
-    assert list(_peek(torch, A.dev_transport_has_key(tr), N)) == [0 if i == REFUSED else 1 for i in range(N)]
+    assert list(peek(A.dev_transport_has_key(tr), N)) == [0 if i == REFUSED else 1 for i in range(N)]
     assert A.dev_transport_free(tr) == 0
     free(r)

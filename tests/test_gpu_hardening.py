@@ -15,22 +15,9 @@ import os
 import numpy as np
 import pytest
 
+from gpu_support import AES, CHACHA, _torch, peek
+
 pytestmark = pytest.mark.gpu
-
-CHACHA, AES = 0x4301, 0x4302
-
-
-def _torch():
-    import torch
-    return torch
-
-
-def _hip_d2h(ptr, nbytes):
-    """hipMemcpy device -> host through the HIP runtime torch already loaded."""
-    hip = C.CDLL("libamdhip64.so", mode=C.RTLD_GLOBAL)
-    out = (C.c_uint8 * nbytes)()
-    assert hip.hipMemcpy(out, C.c_void_p(ptr), C.c_size_t(nbytes), 2) == 0
-    return bytes(out)
 
 
 @pytest.mark.parametrize("cipher,lanes", [(CHACHA, 4), (CHACHA, 0), (AES, 0), (AES, 4)])
@@ -100,7 +87,7 @@ def test_freed_state_context_is_scrubbed(aead, gpu, cipher, monkeypatch):
     n = C.c_size_t()
     ptr = aead.lib().noise_aead_debug_last_freed_ctx(C.byref(n))
     assert ptr and n.value == aead.dev_ctx_bytes(cipher)
-    assert _hip_d2h(ptr, n.value) == bytes(n.value), "key context not zeroed"
+    assert peek(ptr, n.value) == bytes(n.value), "key context not zeroed"
 
 
 @pytest.mark.parametrize("cipher", [CHACHA, AES])

@@ -25,10 +25,13 @@ import time
 import numpy as np
 import pytest
 
+if __name__ == "__main__":  # the child process: what conftest.py does for pytest
+    ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    sys.path[:0] = [ROOT, os.path.join(ROOT, "oracle"), os.path.join(ROOT, "noise-c_amd")]
+
 import length_classes as C
-from test_gpu_parity import (AES, CHACHA, FLAG_CT_GHASH, FLAG_ONE_PASS, dev, duplex_kernel, oracle_seal_records,
-                             prepare, rejected_fill, stream, sync)
-from test_gpu_seg import REC_DT
+from aead_gpu import duplex_kernel, oracle_seal_records, rejected_fill
+from gpu_support import AES, CHACHA, FLAG_CT_GHASH, FLAG_ONE_PASS, REC_DT, _torch, dev, prepare, ru, stream, sync
 
 pytestmark = pytest.mark.gpu
 
@@ -36,20 +39,11 @@ TF = {False: "false", True: "true"}
 HELPER = os.path.join(os.path.dirname(os.path.abspath(__file__)), "aes_shapes_check.py")
 
 
-def _torch():
-    import torch
-    return torch
-
-
 @pytest.fixture(autouse=True)
 def wall_time(request):
     t = time.perf_counter()
     yield
     print("%s: %.2f s" % (request.node.name, time.perf_counter() - t))
-
-
-def ru(x, m):
-    return (x + m - 1) // m * m
 
 
 def tamper(ct, offs, lens, bad):
@@ -500,8 +494,6 @@ def main(argv):
     goes on to the next case; anything else (a HIP error among them) ends the
     process there, so nothing more starts on the GPU."""
     import json
-    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    sys.path[:0] = [root, os.path.join(root, "oracle"), os.path.join(root, "noise-c_amd")]
     import noise_aead
     import oracle as O
     if not os.path.exists(O.ORACLE_SO):

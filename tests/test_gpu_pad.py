@@ -11,16 +11,11 @@ import os
 import numpy as np
 import pytest
 
+from gpu_support import CHACHA, _torch
 from oracle import RandSnapshot, REF_FULL_SO
 
 pytestmark = pytest.mark.gpu
 ZERO, RANDOM = 0x4701, 0x4702
-CHACHA = 0x4301
-
-
-def _torch():
-    import torch
-    return torch
 
 
 def _snap(seed):
@@ -145,8 +140,8 @@ def test_echo_client_padding_feeds_uniform_seal(aead, gpu, oracle):
     # the RandState: the reference's when present, else a synthetic snapshot
     ref = None
     if os.path.exists(REF_FULL_SO):
-        from test_randstate import _ref_randstate, snapshot_of
-        R, st = _ref_randstate()
+        from randstate_ref import ref_randstate, snapshot_of
+        R, st = ref_randstate()
         snap = snapshot_of(st)
         ref = (R, st)
     else:

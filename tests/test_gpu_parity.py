@@ -10,92 +10,16 @@ one (both verify first) and zeroed by a one-pass ChaChaPoly open
 (scrub_rejected: never unauthenticated plaintext).
 """
 import ctypes as C
-import os
 
 import numpy as np
 import pytest
 
+from aead_gpu import LENS, duplex_cases_check, gpu_uniform, oracle_seal_records, rejected_fill
+from gpu_support import AES, CHACHA, FLAG_ONE_PASS, FLAG_CT_GHASH, FLAG_VERIFY_FIRST, _torch, dev, prepare, stream, sync
+
 pytestmark = pytest.mark.gpu
 
-CHACHA, AES = 0x4301, 0x4302
 NONCE_MAX = 2**64 - 1
-
-
-def _torch():
-    import torch
-    return torch
-
-
-def dev(arr):
-    torch = _torch()
-    return torch.from_numpy(np.ascontiguousarray(arr)).to("cuda")
-
-
-def stream():
-    return _torch().cuda.current_stream().cuda_stream
-
-
-def sync():
-    _torch().cuda.synchronize()
-
-
-# NOISE_AEAD_FLAG_*: verify-first is the default open order (round 6);
-# ONE_PASS opts a ChaChaPoly FAST open into decrypt-while-authenticating
-FLAG_CT_GHASH, FLAG_VERIFY_FIRST, FLAG_ONE_PASS = 2, 4, 8
-
-
-def prepare(aead, cipher, keys):
-    torch = _torch()
-    keys = np.ascontiguousarray(keys, dtype=np.uint8).reshape(-1, 32)
-    d_keys = dev(keys.reshape(-1))
-    ctx = torch.empty(keys.shape[0] * aead.dev_ctx_bytes(cipher), dtype=torch.uint8, device="cuda")
-    assert aead.dev_prepare(cipher, d_keys.data_ptr(), keys.shape[0], ctx.data_ptr(), stream()) == 0
-    return ctx, d_keys
-
-
-def gpu_uniform(aead, open_, cipher, keys, nonce_base, rps, inp, in_stride, length, count,
-                out_stride, lanes=0, ad=None, ad_stride=0, ad_len=0, out_init=0xA5, out=None,
-                flags=0):
-    torch = _torch()
-    ctx, _k = prepare(aead, cipher, keys)
-    d_nb = dev(np.asarray(nonce_base, dtype=np.uint64).view(np.int64))
-    d_in = dev(inp)
-    if out is None:
-        d_out = torch.full((count * out_stride + 64,), out_init, dtype=torch.uint8, device="cuda")
-    else:
-        d_out = out
-    d_st = torch.full((max(1, count),), 7, dtype=torch.uint8, device="cuda")
-    d_ad = dev(ad) if ad is not None else None
-    rc = aead.dev_uniform(open_, cipher, ctx=ctx.data_ptr(), nonce_base=d_nb.data_ptr(),
-                          inp=d_in.data_ptr(), out=d_out.data_ptr(), in_stride=in_stride,
-                          out_stride=out_stride, length=length, n_records=count,
-                          recs_per_state=rps, status=d_st.data_ptr(),
-                          ad=d_ad.data_ptr() if d_ad is not None else 0, ad_stride=ad_stride,
-                          ad_len=ad_len, lanes=lanes, flags=flags, stream=stream())
-    assert rc == 0, hex(rc)
-    sync()
-    return d_out.cpu().numpy(), d_st.cpu().numpy()[:count]
-
-
-def rejected_fill(cipher, out_init, flags=0):
-    """What a rejected record's output holds after an out-of-place open:
-    untouched (its prior fill) when the open verified first — every open by
-    default since round 6 (dispatch.h open_vf; every AES-GCM open always)
-    — and zeroed after a ChaChaPoly open that opted into
-    NOISE_AEAD_FLAG_ONE_PASS (VERIFY_FIRST overrides it)."""
-    return 0 if (cipher == CHACHA and flags & FLAG_ONE_PASS and not flags & FLAG_VERIFY_FIRST) else out_init
-
-
-def oracle_seal_records(oracle, cipher, keys, nonce_base, rps, pt, in_stride, length, count,
-                        out_stride, ad=None, ad_stride=0, ad_len=0):
-    out = np.full(count * out_stride + 64, 0xA5, dtype=np.uint8)
-    for i in range(count):
-        s = i // rps
-        p = bytes(pt[i * in_stride: i * in_stride + length])
-        a = bytes(ad[i * ad_stride: i * ad_stride + ad_len]) if ad_len else b""
-        ct = oracle.encrypt(cipher, bytes(keys[s]), int(nonce_base[s]) + i % rps, p, a)
-        out[i * out_stride: i * out_stride + length + 16] = np.frombuffer(ct, dtype=np.uint8)
-    return out
 
 
 # ------------------------------------------------------------------ KATs
@@ -118,10 +42,6 @@ def test_kat_through_device_api(aead, gpu, golden):
 
 
 # --------------------------------------------------- uniform vs the oracle
-
-LENS = [0, 1, 15, 16, 17, 48, 56, 63, 64, 65, 127, 128, 129, 191, 192, 255, 256, 257,
-        1023, 1400, 1401, 4096, 5000]
-
 
 @pytest.mark.parametrize("cipher,lanes", [(CHACHA, 1), (CHACHA, 2), (CHACHA, 4), (CHACHA, 8),
                                           (CHACHA, 16), (CHACHA, 32), (CHACHA, 64), (AES, 0)])
@@ -259,95 +179,6 @@ DUPLEX_CASES = [((1400, 700, 350), (1400, 300, 100)), ((100, 64, 16), (1401, 513
 # keys) at the bench's 128-B record slots, last workgroup partial
 SLOT_CASES = [((1400, 1024, 512), (1400, 768, 256)), ((1400, 512, 256), (1024, 2048, 1024)),
               ((1, 256, 256), (1400, 300, 256)), ((1400, 1000, 256), (4096, 256, 256))]
-
-
-def duplex_kernel(aead, cipher, lanes, layout, flags, case):
-    """The one-launch kernel that include/noise_aead_hip.h promises the two
-    jobs of a duplex case, None where it promises two launches: an empty job,
-    a layout that is not FAST, AES-GCM without one state per 256 records;
-    ChaChaPoly jobs on different lane counts, on other than 1, 4 or 8 lanes,
-    on 4 or 8 with a verify-first open, or of which only one has a state per
-    wave."""
-    (_La, na, rpsa), (_Lb, nb_, rpsb) = case
-    tf = {False: "false", True: "true"}
-    if not na or not nb_ or layout == "packed":
-        return None
-    if cipher == AES:
-        if rpsa % 256 or rpsb % 256:
-            return None
-        staged = os.environ.get("NOISE_AEAD_GCM_DUPLEX") == "staged"
-        return "gcm_duplex_%s<%s>" % ("staged" if staged else "fused", tf[bool(flags & FLAG_CT_GHASH)])
-    ka, kb = (lanes or aead.dev_duplex_lanes(cipher, n) for n in (na, nb_))
-    vf = bool(flags & FLAG_VERIFY_FIRST) or not flags & FLAG_ONE_PASS
-    if ka != kb or ka not in (1, 4, 8) or (ka != 1 and vf):
-        return None
-    ua, ub = rpsa % (64 // ka) == 0, rpsb % (64 // ka) == 0
-    if ua != ub:
-        return None
-    return "chachapoly_duplex_solo<%s>" % tf[ua] if ka == 1 else "chachapoly_duplex_staged<%d,%s>" % (ka, tf[ua])
-
-
-def duplex_cases_check(aead, oracle, cipher, cases, layout, lanes, flags, rng):
-    """One noise_aead_dev_duplex_uniform call per case, written ((len, records,
-    records per state) of the seal job, the same of the open job), checked
-    against the oracle (test_duplex_vs_oracle; tests/aes_shapes_check.py runs
-    it under the AES-GCM environment switches); the kernel that ran
-    (noise_aead_debug_last_plan) is the one duplex_kernel names.  Returns the
-    last case's device buffers."""
-    torch = _torch()
-    for case in cases:
-        (La, na, rpsa), (Lb, nb_, rpsb) = case
-        def strides(L):
-            if layout == "packed":
-                return L, L + 16
-            if layout == "slot128":
-                return (max(L, 1) + 127) // 128 * 128, (L + 16 + 127) // 128 * 128
-            return (max(L, 1) + 63) // 64 * 64, (L + 16 + 63) // 64 * 64
-        ia, oa = strides(La)
-        ib, ob = strides(Lb)
-        Sa, Sb = (na + rpsa - 1) // rpsa, max(1, (nb_ + rpsb - 1) // rpsb)
-        ka = rng.integers(0, 256, (Sa, 32), dtype=np.uint8)
-        kb = rng.integers(0, 256, (Sb, 32), dtype=np.uint8)
-        nba = rng.integers(0, 2**62, Sa, dtype=np.uint64)
-        nbb = rng.integers(0, 2**62, Sb, dtype=np.uint64)
-        pta = rng.integers(0, 256, na * ia + 64, dtype=np.uint8)
-        ptb = rng.integers(0, 256, max(1, nb_) * ib + 64, dtype=np.uint8)
-        exp_a = oracle_seal_records(oracle, cipher, ka, nba, rpsa, pta, ia, La, na, oa)
-        ctb = oracle_seal_records(oracle, cipher, kb, nbb, rpsb, ptb, ib, Lb, nb_, ob)
-        bad = sorted(set(int(x) for x in rng.integers(0, max(1, nb_), 4))) if nb_ else []
-        for b in bad:
-            ctb[b * ob + int(rng.integers(0, Lb + 16))] ^= 0x10
-        ctxa, _k1 = prepare(aead, cipher, ka)
-        ctxb, _k2 = prepare(aead, cipher, kb)
-        d_nba, d_nbb = dev(nba.view(np.int64)), dev(nbb.view(np.int64))
-        d_pta, d_ctb = dev(pta), dev(ctb)
-        d_outa = torch.full((na * oa + 64,), 0xA5, dtype=torch.uint8, device="cuda")
-        d_outb = torch.full((max(1, nb_) * ib + 64,), 0x5A, dtype=torch.uint8, device="cuda")
-        d_st = torch.full((max(1, nb_),), 7, dtype=torch.uint8, device="cuda")
-        sj = aead.uniform_job(ctx=ctxa.data_ptr(), nonce_base=d_nba.data_ptr(), inp=d_pta.data_ptr(),
-                              out=d_outa.data_ptr(), in_stride=ia, out_stride=oa, length=La,
-                              n_records=na, recs_per_state=rpsa, lanes=lanes,
-                              flags=flags & FLAG_CT_GHASH)
-        oj = aead.uniform_job(ctx=ctxb.data_ptr(), nonce_base=d_nbb.data_ptr(), inp=d_ctb.data_ptr(),
-                              out=d_outb.data_ptr(), in_stride=ob, out_stride=ib, length=Lb,
-                              n_records=nb_, recs_per_state=rpsb, status=d_st.data_ptr(),
-                              lanes=lanes, flags=flags)
-        assert aead.dev_duplex(cipher, sj, oj, stream()) == 0
-        want = duplex_kernel(aead, cipher, lanes, layout, flags, case)
-        ran = aead.last_plan().split()[0]
-        assert ran == want if want else "duplex" not in ran, (case, ran, want)
-        sync()
-        got_a, back, st = d_outa.cpu().numpy(), d_outb.cpu().numpy(), d_st.cpu().numpy()
-        assert np.array_equal(got_a[:na * oa], exp_a[:na * oa]), f"duplex seal len={La}"
-        for i in range(nb_):
-            seg = back[i * ib: i * ib + Lb]
-            if i in bad:
-                fill = rejected_fill(cipher, 0x5A, flags)
-                assert st[i] == 1 and np.all(seg == fill), f"duplex open len={Lb} rec={i}"
-            else:
-                assert st[i] == 0, f"duplex open len={Lb} rec={i}"
-                assert np.array_equal(seg, ptb[i * ib: i * ib + Lb]), f"len={Lb} rec={i}"
-    return ctxa, d_nba, d_pta, d_outa, d_outb, d_st
 
 
 @pytest.mark.parametrize("cipher,lanes,layout,flags", [

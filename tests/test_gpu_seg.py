@@ -14,44 +14,10 @@ one — the default order).
 import numpy as np
 import pytest
 
-from test_gpu_parity import CHACHA, dev, gpu_uniform, oracle_seal_records, prepare, stream, sync
+from aead_gpu import _ragged_batch, gpu_uniform, oracle_seal_records
+from gpu_support import CHACHA, dev, prepare, stream, sync
 
 pytestmark = pytest.mark.gpu
-
-REC_DT = [("in_off", "<u8"), ("out_off", "<u8"), ("nonce", "<u8"), ("ctx_off", "<u8"),
-          ("ad_off", "<u8"), ("len", "<u4"), ("ad_len", "<u4")]
-EDGE_LENS = [0, 1, 15, 16, 17, 63, 64, 65, 127, 128, 129, 1400, 1983, 1984, 1985, 2047, 2048,
-             4095, 4096, 4097, 8191, 8192, 16383, 16384, 16385, 30000, 40000, 65519]
-REFUSED = [65520, 70000]
-
-
-def _fast_slot(L):
-    """a FAST slot: 64-B aligned, readable to roundup64(max(len, 1)), room for the tag"""
-    return ((max(int(L), 1) + 16 + 63) // 64) * 64 + 64
-
-
-def _ragged_batch(rng, count, S):
-    lens = rng.integers(0, 2600, count)
-    big = rng.choice(count, count // 50, replace=False)
-    lens[big] = rng.integers(2600, 16385, len(big))
-    lens[:len(EDGE_LENS)] = EDGE_LENS
-    lens[len(EDGE_LENS):len(EDGE_LENS) + len(REFUSED)] = REFUSED
-    perm = rng.permutation(count)          # descriptors in no particular order
-    lens = lens[perm]
-    adls = np.where(rng.random(count) < 0.1, rng.integers(0, 48, count), 0)
-    slots = np.array([_fast_slot(min(int(L), 65519)) for L in lens], dtype=np.int64)
-    offs = np.zeros(count, dtype=np.int64)
-    offs[1:] = np.cumsum(slots)[:-1]
-    total = int(offs[-1] + slots[-1]) + 256
-    recs = np.zeros(count, dtype=REC_DT)
-    recs["in_off"] = recs["out_off"] = offs
-    recs["nonce"] = rng.integers(0, 2**63, count, dtype=np.int64).astype(np.uint64)
-    key_idx = rng.integers(0, S, count).astype(np.uint32)
-    recs["ctx_off"] = key_idx.astype(np.uint64) * 32
-    recs["ad_off"] = np.arange(count, dtype=np.uint64) * 64
-    recs["len"] = lens
-    recs["ad_len"] = adls
-    return recs, key_idx, offs, lens, total
 
 
 @pytest.mark.parametrize("vf", [False, True])

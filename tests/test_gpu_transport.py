@@ -7,166 +7,14 @@ partial one.  The streams lie in one device buffer at odd, even and 16-byte
 aligned offsets with unequal gaps, between 0xEE canaries that must read back
 untouched; frame counts cycle through 0..5 and lengths through
 {16, 17, 80, 1416, 65535}."""
-import ctypes
-
 import numpy as np
 import pytest
 
 import transport_model as T
+from handshake_gpu import basic_vector, handshake, make_sessions
+from transport_gpu import CIPHERS, LENS, N, Side, Wire, keys_for, plain_streams, total_frames
 
 pytestmark = pytest.mark.gpu
-N = 67
-CANARY = 0xEE
-LENS = (16, 17, 80, 1416, 65535)
-CIPHERS = [T.CHACHAPOLY, T.AESGCM]
-
-
-def _hip():
-    return ctypes.CDLL("libamdhip64.so", mode=ctypes.RTLD_GLOBAL)
-
-
-def peek_u64(torch, ptr, n):
-    """n 64-bit words of device memory the library owns"""
-    host = (ctypes.c_uint64 * n)()
-    torch.cuda.synchronize()
-    assert _hip().hipMemcpy(host, ctypes.c_void_p(ptr), ctypes.c_size_t(8 * n), 2) == 0  # device to host
-    return list(host)
-
-
-def poke_u64(torch, ptr, values):
-    host = (ctypes.c_uint64 * len(values))(*values)
-    torch.cuda.synchronize()
-    assert _hip().hipMemcpy(ctypes.c_void_p(ptr), host, ctypes.c_size_t(8 * len(values)), 1) == 0  # host to device
-
-
-def keys_for(seed, n=N):
-    rng = np.random.default_rng(seed)
-    return [(rng.integers(0, 256, 32, dtype=np.uint8).tobytes(), rng.integers(0, 256, 32, dtype=np.uint8).tobytes())
-            for _ in range(n)]
-
-
-def plain_streams(seed, n=N, big=True):
-    """Seal-ready streams: session i has i % 6 frames, lengths cycling through
-    LENS (65535 kept to every third session so that the batch stays small);
-    every fifth session ends with one byte of a next header."""
-    rng = np.random.default_rng(seed)
-    out = []
-    for i in range(n):
-        lens = [LENS[(i + 2 * k) % 5] for k in range(i % 6)]
-        lens = [L if (L != 65535 or (big and i % 3 == 2)) else 80 for L in lens]
-        s = b"".join(T.frame(rng.integers(0, 256, L - 16, dtype=np.uint8).tobytes() + bytes(16)) for L in lens)
-        out.append(s + (b"\x07" if i % 5 == 3 else b""))
-    return out
-
-
-def offsets(streams):
-    """odd, even and 16-byte aligned offsets in turn, with unequal gaps"""
-    offs, cur = [], 1
-    for i, s in enumerate(streams):
-        cur += (3, 8, 13, 1, 22)[i % 5]
-        if i % 3 == 0:
-            cur |= 1
-        elif i % 3 == 1:
-            cur += (cur & 1) + (2 if (cur + (cur & 1)) % 16 == 0 else 0)
-        else:
-            cur = (cur + 15) & ~15
-        offs.append(cur)
-        cur += len(s)
-    return offs, cur + 9
-
-
-class Wire:
-    """The sessions' streams in one canary-filled device buffer."""
-
-    def __init__(self, torch, streams):
-        self.torch, self.n = torch, len(streams)
-        self.offs, total = offsets(streams)
-        assert {o % 2 for o in self.offs} == {0, 1} and any(o % 16 == 0 for o in self.offs) or self.n < 3
-        self.lens = [len(s) for s in streams]
-        host = np.full(total, CANARY, dtype=np.uint8)
-        for o, s in zip(self.offs, streams):
-            host[o:o + len(s)] = np.frombuffer(s, dtype=np.uint8)
-        self.dev = torch.from_numpy(host).cuda()
-        self.result = torch.full((self.n + 1, 4), 0x55555555, dtype=torch.int32, device="cuda")
-        self.pos = [0] * self.n  # bytes of each stream already consumed (the cap tests)
-
-    def call(self, A, fn, tr):
-        """one call on what is left of every stream; [(frames, consumed, error)]"""
-        torch = self.torch
-        off = torch.tensor([o + p for o, p in zip(self.offs, self.pos)] or [0], dtype=torch.int64, device="cuda")
-        ln = torch.tensor([l - p for l, p in zip(self.lens, self.pos)] or [0], dtype=torch.int32, device="cuda")
-        sp = torch.cuda.current_stream().cuda_stream
-        assert fn(tr, wire=self.dev.data_ptr(), off=off.data_ptr(), length=ln.data_ptr(), result=self.result.data_ptr(),
-                  stream=sp) == 0
-        torch.cuda.synchronize()
-        r = self.result.cpu().numpy()
-        assert (r[self.n] == 0x55555555).all() and (r[:self.n, 3] == 0).all(), "result rows"
-        return [(int(np.uint32(x[0])), int(np.uint32(x[1])), int(x[2])) for x in r[:self.n]]
-
-    def streams(self):
-        """every stream as it is now; checks every byte between and around them"""
-        h = self.dev.cpu().numpy()
-        mask = np.ones(len(h), dtype=bool)
-        out = []
-        for o, l in zip(self.offs, self.lens):
-            out.append(h[o:o + l].tobytes())
-            mask[o:o + l] = False
-        assert (h[mask] == CANARY).all(), "wrote outside a stream"
-        return out
-
-    def rest(self):
-        return [s[p:] for s, p in zip(self.streams(), self.pos)]
-
-
-class Side:
-    """One device transport object beside its model sessions."""
-
-    def __init__(self, A, torch, orc, cipher, initiator, keys, max_frames, k1_ptr=None, k2_ptr=None):
-        self.A, self.torch, self.n = A, torch, len(keys)
-        if k1_ptr is None:
-            self.k1 = torch.tensor(list(b"".join(k[0] for k in keys)), dtype=torch.uint8, device="cuda")
-            self.k2 = torch.tensor(list(b"".join(k[1] for k in keys)), dtype=torch.uint8, device="cuda")
-            k1_ptr, k2_ptr = self.k1.data_ptr(), self.k2.data_ptr()
-        rc, self.tr = A.dev_transport_new(cipher, A.ROLE_INITIATOR if initiator else A.ROLE_RESPONDER, self.n, k1=k1_ptr,
-                                          k2=k2_ptr, max_frames=max_frames, stream=torch.cuda.current_stream().cuda_stream)
-        assert rc == 0 and self.tr, hex(rc)
-        self.max_frames = max_frames
-        self.model = [T.Session.of_role(orc, cipher, initiator, *k) for k in keys]
-
-    def nonces(self, direction):
-        return peek_u64(self.torch, self.A.dev_transport_nonces(self.tr, direction), self.n)
-
-    def set_nonces(self, direction, values):
-        """through the object's own device array, and in the model"""
-        cur = self.nonces(direction)
-        for i, v in values.items():
-            cur[i] = v
-            setattr(self.model[i], "recv" if direction else "send", v)
-        poke_u64(self.torch, self.A.dev_transport_nonces(self.tr, direction), cur)
-
-    def run(self, mode, wire: Wire, exact=True):
-        """One call on the device and in the model.  exact: every byte, result
-        and nonce must equal the model's; else returns both for the caller."""
-        fn = getattr(self.A, f"dev_transport_{mode}_frames")
-        before = wire.rest()
-        want = T.run_batch(self.model, mode, before, self.max_frames)
-        got_results = wire.call(self.A, fn, self.tr)
-        got = wire.rest()
-        assert self.nonces(0) == [m.send for m in self.model], "send nonces"
-        assert self.nonces(1) == [m.recv for m in self.model], "receive nonces"
-        assert got_results == [w[1] for w in want], "results"
-        if exact:
-            for i in range(self.n):
-                assert got[i] == want[i][0], ("stream", i)
-        return got, got_results, want
-
-    def free(self):
-        assert self.A.dev_transport_free(self.tr) == 0
-        self.tr = None
-
-
-def total_frames(streams):
-    return sum(len(T.walk(s, 0)[0]) for s in streams)
 
 
 @pytest.mark.parametrize("initiator", [True, False], ids=["initiator", "responder"])
@@ -380,11 +228,10 @@ def test_handshake_split_feeds_the_transport(aead, gpu, oracle, name):
     object on each side straight from the split's device arrays; traffic both
     ways."""
     import torch
-    import test_gpu_handshake as H
     n = 9
-    v = H.basic_vector(name)
-    sess = H.make_sessions(v, n, 7)
-    r = H.handshake(aead, torch, oracle, v, sess, seed=7)
+    v = basic_vector(name)
+    sess = make_sessions(v, n, 7)
+    r = handshake(aead, torch, oracle, v, sess, seed=7)
     assert r["ini_status"] == [0] * n and r["ini_split"][:2] == r["res_split"][:2]
     k1, k2, _ = r["ini_split"]
     keys = list(zip(k1, k2))

@@ -8,34 +8,32 @@ both nonce arrays and every word of the windows.  A status-5 frame that only an
 earlier frame of the same call made a replay may hold its bytes as given or
 its plaintext; the tests plant those cases and assert that the model names
 exactly them before anything is compared.  The table and wire helpers are those
-of tests/test_gpu_transport_table.py and tests/test_gpu_transport.py."""
+of tests/transport_gpu.py."""
 import numpy as np
 import pytest
 
-import test_gpu_transport as G
-import test_gpu_transport_table as GT
+import transport_gpu
 import transport_model as T
 import transport_datagram_model as D
+from gpu_support import dev_u32, peek_u64, poke_u64
+from transport_gpu import CIPHERS, N, PERM, Wire, keys_for, plain_streams
 
 pytestmark = pytest.mark.gpu
-N = G.N
-CIPHERS = G.CIPHERS
 IDS = ["ChaChaPoly", "AESGCM"]
 TOP = 2 ** 32 - 1
 TOP64 = 2 ** 64 - 1
-PERM = GT.PERM
 PAYLOADS = (0, 1, 15, 16, 17, 63, 64, 65, 1400)
 CANARY = 0xEE
 UNKEYED = 13
 
 
-class Table(GT.Table):
-    """GT.Table with the datagram calls and the windows beside their model"""
+class Table(transport_gpu.Table):
+    """transport_gpu.Table with the datagram calls and the windows beside their model"""
 
     def windows(self):
         ptr, bits = self.A.dev_transport_replay(self.tr)
         assert ptr and bits == D.REPLAY_BITS
-        flat = G.peek_u64(self.torch, ptr, 17 * self.n)
+        flat = peek_u64(ptr, 17 * self.n)
         return [flat[17 * i:17 * i + 17] for i in range(self.n)]
 
     def want_windows(self):
@@ -44,7 +42,7 @@ class Table(GT.Table):
     def set_window(self, i, w):
         """through the object's own device array, and in the model"""
         ptr, _ = self.A.dev_transport_replay(self.tr)
-        G.poke_u64(self.torch, ptr + 136 * i, w.words())
+        poke_u64(ptr + 136 * i, w.words())
         self.model[i].window = w.copy()
 
     def check_state(self):
@@ -56,7 +54,7 @@ class Table(GT.Table):
         equal the model's.  Returns the model's per-entry tuples."""
         A, torch = self.A, self.torch
         m = wire.n
-        d_slots = GT.dev_u32(torch, slots) if slots is not None else None
+        d_slots = dev_u32(slots) if slots is not None else None
         cap = max_frames or self.max_frames
         before = wire.rest()
         want = D.run_datagrams(self.model, mode, before, cap, slots)
@@ -125,7 +123,7 @@ def entries(m):
 
 
 def pair(aead, torch, oracle, cipher, max_frames, seed):
-    keys = G.keys_for(seed)
+    keys = keys_for(seed)
     tabs = [Table(aead, torch, oracle, cipher, ini, max_frames, keys) for ini in (True, False)]
     for t in tabs:
         t.clear_keys([UNKEYED])
@@ -145,7 +143,7 @@ def test_seal_open_reordered_and_replayed(aead, gpu, oracle, cipher, m):
     for sender, receiver, seed in ((a, b, 82), (b, a, 83)):  # both roles seal and open
         plain = payload_streams(seed, m)
         assert m == 1 or {L - D.MIN_L for s in plain for _, L in D.walk(s)[0]} == set(PAYLOADS)
-        wire = G.Wire(torch, plain)
+        wire = Wire(torch, plain)
         want = sender.datagrams("seal", wire, slots)
         assert [w[1][0] for j, w in enumerate(want) if j not in dead] == [1 + j % 8 for j in range(m) if j not in dead]
         sealed = wire.streams()
@@ -159,7 +157,7 @@ def test_seal_open_reordered_and_replayed(aead, gpu, oracle, cipher, m):
             count = len(D.walk(s)[0])
             order = list(range(count)) if j % 3 == 0 or j in dead else list(range(count))[::-1] if j % 3 == 1 else list(rng.permutation(count))
             delivered.append(reorder(s, order))
-        wire = G.Wire(torch, delivered)
+        wire = Wire(torch, delivered)
         want = receiver.datagrams("open", wire, slots)
         opened = wire.streams()
         for j, w in enumerate(want):
@@ -172,7 +170,7 @@ def test_seal_open_reordered_and_replayed(aead, gpu, oracle, cipher, m):
         assert receiver.nonces(1) == [0] * N  # the receive nonces are not in it
         # the same frames again: all replays, no byte and no window bit changes
         windows = receiver.windows()
-        wire = G.Wire(torch, sealed)
+        wire = Wire(torch, sealed)
         want = receiver.datagrams("open", wire, slots)
         for j, w in enumerate(want):
             assert j in dead or (w[2] == [D.REPLAY] * (1 + j % 8) and w[1][3] == 0 and not w[3])
@@ -200,7 +198,7 @@ def test_in_call_cases(aead, gpu, oracle, cipher):
     counter of 2^64 - 1; a jump of 2^40 followed by a frame that is now too
     old; a runt that stops the walk with the frames before it judged"""
     import torch
-    keys = G.keys_for(91)
+    keys = keys_for(91)
     b = Table(aead, torch, oracle, cipher, False, 64, keys)
     rng = np.random.default_rng(91)
 
@@ -217,7 +215,7 @@ def test_in_call_cases(aead, gpu, oracle, cipher):
         b"",
         flip(f(6, 5), 2 + 8 + 4),  # the ciphertext forged
     ]
-    wire = G.Wire(torch, streams)
+    wire = Wire(torch, streams)
     twin = [T.Session.of_role(oracle, cipher, False, *k) for k in keys]
     want = D.run_datagrams(twin, "open", streams, 64)
     at = [[fr[0] for fr in D.walk(s)[0]] for s in streams]
@@ -240,7 +238,7 @@ def test_in_call_cases(aead, gpu, oracle, cipher):
 @pytest.mark.parametrize("cipher", CIPHERS, ids=IDS)
 def test_preset_windows_at_the_edges(aead, gpu, oracle, cipher):
     import torch
-    keys = G.keys_for(101)
+    keys = keys_for(101)
     b = Table(aead, torch, oracle, cipher, True, 64, keys)  # the initiator receives under k2
     rng = np.random.default_rng(101)
 
@@ -284,7 +282,7 @@ def test_preset_windows_at_the_edges(aead, gpu, oracle, cipher):
     # made replays inside the call: a counter the call's own advance of top left behind, or took twice
     assert planted == {(0, 8), (3, 3), (3, 6), (4, 4)}
     assert want[0][2] == [5, 0, 0, 5, 5, 0, 0, 0, 5, 0] and want[2][2] == [5, 5, 5, 5, 0, 0] and want[4][2] == [0, 5, 0, 0, 5, 0]
-    wire = G.Wire(torch, streams)
+    wire = Wire(torch, streams)
     got = b.datagrams("open", wire, slots)
     assert [g[2] for g in got] == [w[2] for w in want]
     b.free()
@@ -295,7 +293,7 @@ def test_preset_windows_at_the_edges(aead, gpu, oracle, cipher):
 @pytest.mark.parametrize("cipher", CIPHERS, ids=IDS)
 def test_caps_cut_before_inside_and_after_entries(aead, gpu, oracle, cipher):
     import torch
-    keys = G.keys_for(111)
+    keys = keys_for(111)
     a, b = pair(aead, torch, oracle, cipher, 40, 111)
     slots = [5, UNKEYED, 20, TOP, 7, N, 66, UNKEYED + 1]
     counts = [3, 0, 3, 0, 3, 0, 3, 3]
@@ -304,7 +302,7 @@ def test_caps_cut_before_inside_and_after_entries(aead, gpu, oracle, cipher):
     for cap in (1, 3, 4, 6, 8, 9, 14, 15, 16, 0):  # before, inside and after entries, dead ones on both sides; the object's own
         for t in (a, b):
             t.set_keys(live, [keys[i] for i in live])  # and every window is new
-        wire = G.Wire(torch, plain)
+        wire = Wire(torch, plain)
         want = a.datagrams("seal", wire, slots, cap)
         lim = cap or 40
         assert sum(w[1][0] for w in want) == min(lim, 15)
@@ -323,11 +321,11 @@ def test_caps_cut_before_inside_and_after_entries(aead, gpu, oracle, cipher):
 @pytest.mark.parametrize("cipher", CIPHERS, ids=IDS)
 def test_keys_reset_the_window_and_the_stream_calls_leave_it(aead, gpu, oracle, cipher):
     import torch
-    keys = G.keys_for(121)
+    keys = keys_for(121)
     a, b = (Table(aead, torch, oracle, cipher, ini, 400, keys) for ini in (True, False))
     b.set_nonces(1, {i: 7 for i in range(N)})
     plain = payload_streams(121, N)
-    wire = G.Wire(torch, plain)
+    wire = Wire(torch, plain)
     a.datagrams("seal", wire)
     b.datagrams("open", wire)
     assert b.nonces(1) == [7] * N and [w[0] for w in b.windows()] == [1 + i % 8 for i in range(N)]
@@ -335,12 +333,12 @@ def test_keys_reset_the_window_and_the_stream_calls_leave_it(aead, gpu, oracle, 
     # a stream tick on the same objects: sends go on from where the datagrams left them, the windows stay
     a.set_nonces(0, {i: 7 for i in range(N)})
     windows = b.windows()
-    stream = G.Wire(torch, G.plain_streams(122, big=False))
+    stream = Wire(torch, plain_streams(122, big=False))
     a.run("seal", stream)
     b.run("open", stream, list(range(N)))  # _open_frames_of
     assert b.windows() == windows and b.nonces(1) == [7 + i % 6 for i in range(N)]
     # re-keying and clearing reset the named slots' windows and no other
-    fresh = G.keys_for(123, 2)
+    fresh = keys_for(123, 2)
     b.set_keys([10, 40], fresh)
     b.clear_keys([3, 20, 99])
     now = b.windows()
@@ -348,7 +346,7 @@ def test_keys_reset_the_window_and_the_stream_calls_leave_it(aead, gpu, oracle, 
     assert all(now[i] == windows[i] for i in range(N) if i not in (10, 40, 3, 20))
     a.set_keys([10, 40], fresh)
     # the re-keyed slots take counter 0 again, the others refuse what they have seen
-    wire = G.Wire(torch, payload_streams(124, N))
+    wire = Wire(torch, payload_streams(124, N))
     for i in (10, 40):
         a.set_nonces(0, {i: 0})
     others = {i: 0 for i in range(N) if i not in (10, 40)}
@@ -374,11 +372,11 @@ def test_seal_stops_where_the_counter_runs_out(aead, gpu, oracle, cipher):
     """send + k == 2^64 - 1 stops the walk with NOISE_ERROR_INVALID_NONCE, as the stream seal; the peer takes
     2^64 - 2 and refuses a frame that claims 2^64 - 1"""
     import torch
-    keys = G.keys_for(131, 4)
+    keys = keys_for(131, 4)
     a, b = (Table(aead, torch, oracle, cipher, ini, 16, keys, n=4) for ini in (True, False))
     a.set_nonces(0, {0: TOP64 - 2, 1: TOP64 - 1, 2: TOP64, 3: 2 ** 63})
     plain = [b"".join(D.seal_ready(bytes([k]) * (17 + k)) for k in range(3))] * 4
-    wire = G.Wire(torch, plain)
+    wire = Wire(torch, plain)
     want = a.datagrams("seal", wire)
     two = D.walk(plain[0], 0, 2)[1]
     assert [w[1] for w in want] == [(2, two, T.ERROR_INVALID_NONCE), (1, D.walk(plain[0], 0, 1)[1], T.ERROR_INVALID_NONCE),
@@ -390,7 +388,7 @@ def test_seal_stops_where_the_counter_runs_out(aead, gpu, oracle, cipher):
     # entry 2's first frame claims 2^64 - 1
     claim = bytearray(sealed[2])
     claim[2:10] = TOP64.to_bytes(8, "little")
-    wire = G.Wire(torch, [sealed[0], sealed[1], bytes(claim), sealed[3]])
+    wire = Wire(torch, [sealed[0], sealed[1], bytes(claim), sealed[3]])
     want = b.datagrams("open", wire)
     assert [w[2] for w in want] == [[0, 0, 5], [0, 5, 5], [5, 1, 1], [0, 0, 0]]
     assert D.window(b.model[0]).top == TOP64 and D.window(b.model[3]).top == 2 ** 63 + 3
@@ -405,10 +403,10 @@ def test_argument_rules_on_a_small_object(aead, gpu, oracle):
     import torch
     A = aead
     BAD = A.ERROR_INVALID_PARAM
-    tab = Table(A, torch, oracle, T.CHACHAPOLY, True, 8, G.keys_for(141, 4), n=4)
+    tab = Table(A, torch, oracle, T.CHACHAPOLY, True, 8, keys_for(141, 4), n=4)
     frames = [D.seal_ready(bytes(20))] * 4
-    wire = G.Wire(torch, frames)
-    slots = GT.dev_u32(torch, [2, 0, 9, 3])
+    wire = Wire(torch, frames)
+    slots = dev_u32([2, 0, 9, 3])
     off = torch.tensor(wire.offs, dtype=torch.int64, device="cuda")
     ln = torch.tensor(wire.lens, dtype=torch.int32, device="cuda")
     res = torch.zeros(4 * 24 + 64, dtype=torch.uint8, device="cuda")

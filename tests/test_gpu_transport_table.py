@@ -7,170 +7,18 @@ call is compared with the model of tests/transport_table_model.py: every byte
 of the wire between canaries, every result, both nonce arrays and the state
 bytes; the key contexts with noise_aead_dev_prepare of the right key into a
 zeroed buffer, byte for byte.  n = 67 slots: one wave plus a partial one.  The
-wire and object helpers are those of tests/test_gpu_transport.py."""
-import ctypes
-
-import numpy as np
+wire and object helpers are those of tests/transport_gpu.py."""
 import pytest
 
-import test_gpu_transport as G
 import transport_model as T
 import transport_table_model as M
+from gpu_support import dev_bytes, dev_u32
+from handshake_gpu import basic_vector, handshake, make_sessions
+from transport_gpu import CIPHERS, N, PERM, Table, Wire, keys_for, plain_streams
 
 pytestmark = pytest.mark.gpu
-N = G.N
-CIPHERS = G.CIPHERS
 IDS = ["ChaChaPoly", "AESGCM"]
 TOP = 2 ** 32 - 1
-PERM = [(29 * j + 5) % N for j in range(N)]  # every slot once, unsorted
-
-
-def peek_u8(torch, ptr, n):
-    """n bytes of device memory the library owns"""
-    host = (ctypes.c_uint8 * n)()
-    torch.cuda.synchronize()
-    assert G._hip().hipMemcpy(host, ctypes.c_void_p(ptr), ctypes.c_size_t(n), 2) == 0  # device to host
-    return np.frombuffer(bytes(host), dtype=np.uint8)
-
-
-def dev_u32(torch, values):
-    return torch.from_numpy(np.array(values, dtype=np.uint32).view(np.int32)).cuda()
-
-
-def dev_bytes(torch, data: bytes):
-    return torch.from_numpy(np.frombuffer(bytes(data), dtype=np.uint8).copy()).cuda()
-
-
-def prepared(A, torch, cipher, keys):
-    """noise_aead_dev_prepare of each key (None: no key) into a zeroed buffer: [len(keys), ctx_bytes]"""
-    cb = A.dev_ctx_bytes(cipher)
-    raw = dev_bytes(torch, b"".join(k or bytes(32) for k in keys))
-    ctx = torch.zeros(len(keys) * cb, dtype=torch.uint8, device="cuda")
-    assert A.dev_prepare(cipher, raw.data_ptr(), len(keys), ctx.data_ptr(), torch.cuda.current_stream().cuda_stream) == 0
-    torch.cuda.synchronize()
-    out = ctx.cpu().numpy().reshape(len(keys), cb).copy()
-    for i, k in enumerate(keys):
-        if k is None:
-            out[i] = 0
-    return out
-
-
-class Table:
-    """One device transport object beside its model: a T.Session per keyed
-    slot, None for an unkeyed one (whose nonces the test tracks itself)."""
-
-    def __init__(self, A, torch, orc, cipher, initiator, max_frames, keys=None, n=N):
-        self.A, self.torch, self.orc, self.cipher, self.initiator, self.n = A, torch, orc, cipher, initiator, n
-        self.max_frames = max_frames
-        self.sp = torch.cuda.current_stream().cuda_stream
-        role = A.ROLE_INITIATOR if initiator else A.ROLE_RESPONDER
-        if keys is None:
-            rc, self.tr = A.dev_transport_new_unkeyed(cipher, role, n, max_frames=max_frames, stream=self.sp)
-            self.model = [None] * n
-        else:
-            k1, k2 = dev_bytes(torch, b"".join(k[0] for k in keys)), dev_bytes(torch, b"".join(k[1] for k in keys))
-            rc, self.tr = A.dev_transport_new(cipher, role, n, k1=k1.data_ptr(), k2=k2.data_ptr(), max_frames=max_frames,
-                                              stream=self.sp)
-            torch.cuda.synchronize()
-            self.model = [T.Session.of_role(orc, cipher, initiator, *k) for k in keys]
-        assert rc == 0 and self.tr, hex(rc)
-        self.loose = [[0] * n, [0] * n]  # the nonces of the unkeyed slots
-
-    # ---- what the device holds
-    def nonces(self, direction):
-        return G.peek_u64(self.torch, self.A.dev_transport_nonces(self.tr, direction), self.n)
-
-    def has_key(self):
-        return list(peek_u8(self.torch, self.A.dev_transport_has_key(self.tr), self.n))
-
-    def ctx(self, direction):
-        ptr, cb = self.A.debug_transport_ctx(self.tr, direction)
-        assert ptr and cb == self.A.dev_ctx_bytes(self.cipher)
-        return peek_u8(self.torch, ptr, self.n * cb).reshape(self.n, cb)
-
-    # ---- what the model says it holds
-    def want_nonces(self, direction):
-        return [(m.recv if direction else m.send) if m else self.loose[direction][i] for i, m in enumerate(self.model)]
-
-    def check_state(self):
-        assert self.has_key() == [1 if m else 0 for m in self.model], "state bytes"
-        assert self.nonces(0) == self.want_nonces(0), "send nonces"
-        assert self.nonces(1) == self.want_nonces(1), "receive nonces"
-
-    def check_contexts(self):
-        """both context arrays, every byte: prepare of the right key, or zero"""
-        for direction, attr in ((0, "send_key"), (1, "recv_key")):
-            want = prepared(self.A, self.torch, self.cipher, [getattr(m, attr) if m else None for m in self.model])
-            got = self.ctx(direction)
-            assert got.shape == want.shape
-            for i in range(self.n):
-                assert (got[i] == want[i]).all(), ("context", direction, i)
-
-    def set_nonces(self, direction, values):
-        cur = self.nonces(direction)
-        for i, v in values.items():
-            cur[i] = v
-            if self.model[i]:
-                setattr(self.model[i], "recv" if direction else "send", v)
-            else:
-                self.loose[direction][i] = v
-        G.poke_u64(self.torch, self.A.dev_transport_nonces(self.tr, direction), cur)
-
-    # ---- the calls
-    def set_keys(self, slots, keys, status=None, ptrs=None):
-        """entry j: slot slots[j], keys[j] = (k1, k2); status: one byte per entry
-        or None.  ptrs = (k1, k2, status) device pointers to use instead of
-        copies of these."""
-        torch = self.torch
-        d_slots = dev_u32(torch, slots)
-        if ptrs is None:
-            k1, k2 = dev_bytes(torch, b"".join(k[0] for k in keys)), dev_bytes(torch, b"".join(k[1] for k in keys))
-            st = dev_bytes(torch, bytes(status)) if status is not None else None
-            ptrs = (k1.data_ptr(), k2.data_ptr(), st.data_ptr() if st is not None else 0)
-        assert self.A.dev_transport_set_keys(self.tr, slots=d_slots.data_ptr(), m=len(slots), k1=ptrs[0], k2=ptrs[1],
-                                             status=ptrs[2], stream=self.sp) == 0
-        torch.cuda.synchronize()
-        for j, i in enumerate(slots):
-            if i < self.n:
-                failed = status is not None and status[j] != 0
-                self.model[i] = None if failed else T.Session.of_role(self.orc, self.cipher, self.initiator, *keys[j])
-                self.loose[0][i] = self.loose[1][i] = 0
-
-    def clear_keys(self, slots):
-        d_slots = dev_u32(self.torch, slots)
-        assert self.A.dev_transport_clear_keys(self.tr, slots=d_slots.data_ptr(), m=len(slots), stream=self.sp) == 0
-        self.torch.cuda.synchronize()
-        for i in slots:
-            if i < self.n:
-                self.model[i] = None
-                self.loose[0][i] = self.loose[1][i] = 0
-
-    def run(self, mode, wire, slots=None, max_frames=0):
-        """One call on the device and in the model: the full call (slots None),
-        or the _of call over `slots` under this call's cap.  Every byte, result,
-        nonce and state byte must equal the model's."""
-        A = self.A
-        if slots is None:
-            fn, cap = getattr(A, f"dev_transport_{mode}_frames"), self.max_frames
-        else:
-            of, d_slots = getattr(A, f"dev_transport_{mode}_frames_of"), dev_u32(self.torch, slots)
-            cap = max_frames or self.max_frames
-
-            def fn(tr, **kw):
-                return of(tr, slots=d_slots.data_ptr(), m=len(slots), max_frames=max_frames, **kw)
-        before = wire.rest()
-        want = M.run_table(self.model, mode, before, cap, slots)
-        results = wire.call(A, fn, self.tr)
-        got = wire.rest()
-        assert results == [w[1] for w in want], "results"
-        for j in range(len(before)):
-            assert got[j] == want[j][0], ("stream", j)
-        self.check_state()
-        return results
-
-    def free(self):
-        assert self.A.dev_transport_free(self.tr) == 0
-        self.tr = None
 
 
 # ---------------------------------------------------------------- 1. contexts
@@ -184,7 +32,7 @@ def test_set_keys_builds_the_contexts_prepare_builds(aead, gpu, oracle, cipher, 
     tab.check_contexts()  # all zero
     slots = PERM[:40]
     slots = slots[:10] + [N] + slots[10:30] + [TOP] + slots[30:]
-    keys = G.keys_for(31, len(slots))
+    keys = keys_for(31, len(slots))
     status = [0] * len(slots)
     for j, v in ((0, 1), (4, 3), (17, 255), (33, 1), (41, 2)):
         status[j] = v
@@ -224,7 +72,7 @@ def _dead(i):
 
 def _pair(aead, torch, oracle, cipher, max_frames, seed):
     """an initiator and a responder table, the slots with _dead(i) unkeyed"""
-    keys = G.keys_for(seed)
+    keys = keys_for(seed)
     live = [i for i in PERM if not _dead(i)]
     pair = []
     for initiator in (True, False):
@@ -241,15 +89,15 @@ def test_unkeyed_slots_in_the_full_calls(aead, gpu, oracle, cipher):
     import torch
     total = sum(i % 6 for i in range(N) if not _dead(i))
     a, b = _pair(aead, torch, oracle, cipher, total, 41)
-    plain = G.plain_streams(41, big=False)
+    plain = plain_streams(41, big=False)
     assert sum(len(T.walk(plain[i], 0)[0]) for i in range(N) if _dead(i)) > 10
-    wire = G.Wire(torch, plain)
+    wire = Wire(torch, plain)
     results = a.run("seal", wire)
     assert [r[2] for r in results] == [M.ERROR_INVALID_STATE if _dead(i) else 0 for i in range(N)]
     assert [r[0] for r in results] == [0 if _dead(i) else i % 6 for i in range(N)]  # nobody was cut
     results = b.run("open", wire)
     assert [r[0] for r in results] == [0 if _dead(i) else i % 6 for i in range(N)]
-    wire = G.Wire(torch, G.plain_streams(42, big=False))
+    wire = Wire(torch, plain_streams(42, big=False))
     a.run("seal", wire)
     results = b.run("echo", wire)
     assert [r[:1] + r[2:] for r in results] == [(0, M.ERROR_INVALID_STATE) if _dead(i) else (i % 6, 0) for i in range(N)]
@@ -265,7 +113,7 @@ def test_unkeyed_slots_on_both_sides_of_a_cut(aead, gpu, oracle, cipher):
     assert not _dead(cutting) and cutting % 6 == 4
     cap = sum(i % 6 for i in range(cutting) if not _dead(i)) + 2
     a, b = _pair(aead, torch, oracle, cipher, cap, 43)
-    wire = G.Wire(torch, G.plain_streams(43, big=False))
+    wire = Wire(torch, plain_streams(43, big=False))
     for tab, mode in ((a, "seal"), (b, "open")):
         results = tab.run(mode, wire)
         assert results[cutting] == (2, results[cutting][1], 0)
@@ -284,15 +132,15 @@ def test_unkeyed_slots_on_both_sides_of_a_cut(aead, gpu, oracle, cipher):
 @pytest.mark.parametrize("cipher", CIPHERS, ids=IDS)
 def test_rekey_and_clear_after_traffic(aead, gpu, oracle, cipher):
     import torch
-    keys = G.keys_for(51)
+    keys = keys_for(51)
     total = sum(i % 6 for i in range(N))
     a, b = (Table(aead, torch, oracle, cipher, ini, total + 5, keys) for ini in (True, False))
     assert a.has_key() == [1] * N  # an object from _new starts with every slot keyed
-    wire = G.Wire(torch, G.plain_streams(51, big=False))
+    wire = Wire(torch, plain_streams(51, big=False))
     a.run("seal", wire)
     b.run("open", wire)
     assert a.nonces(0)[10] == b.nonces(1)[10] == 4
-    fresh = G.keys_for(52, 2)
+    fresh = keys_for(52, 2)
     cleared = [3, 20, 99, 66]
     for tab in (a, b):
         tab.set_keys([10, 40], fresh)
@@ -301,8 +149,8 @@ def test_rekey_and_clear_after_traffic(aead, gpu, oracle, cipher):
         tab.check_contexts()  # the named slots new or all zero, every other slot as it was
         assert [tab.has_key()[i] for i in (3, 20, 66, 10, 40, 11)] == [0, 0, 0, 1, 1, 1]
         assert tab.nonces(0)[10] == tab.nonces(1)[10] == tab.nonces(0)[20] == tab.nonces(1)[20] == 0
-    plain = G.plain_streams(53, big=False)
-    wire = G.Wire(torch, plain)
+    plain = plain_streams(53, big=False)
+    wire = Wire(torch, plain)
     results = a.run("seal", wire)
     for i in (3, 20, 66):
         assert results[i] == (0, 0, M.ERROR_INVALID_STATE)
@@ -337,8 +185,8 @@ def _entries(m):
 @pytest.mark.parametrize("cipher", CIPHERS, ids=IDS)
 def test_subset_calls_equal_the_model_and_a_twin_full_call(aead, gpu, oracle, cipher, m):
     import torch
-    keys = G.keys_for(61)
-    plain = G.plain_streams(61, big=False)
+    keys = keys_for(61)
+    plain = plain_streams(61, big=False)
     plain[S_STOP] = plain[S_STOP] + T.frame(bytes(4))  # an L < 16 stop after its frames
     slots = _entries(m)
     assert len(slots) == m and len(set(slots)) == m and slots != sorted(slots) or m == 1
@@ -357,7 +205,7 @@ def test_subset_calls_equal_the_model_and_a_twin_full_call(aead, gpu, oracle, ci
         return [per_slot[i] if i in slots else b"" for i in range(N)]
 
     # seal: a call whose cap cuts inside a listed session, then max_frames = 0 (the object's own) for the rest
-    wire = G.Wire(torch, entry_streams(plain))
+    wire = Wire(torch, entry_streams(plain))
     cap, cutting = (3, 1) if m > 1 else (2, 0)
     first = a.run("seal", wire, slots, max_frames=cap)
     assert 0 < first[cutting][0] < len(T.walk(plain[slots[cutting]], 0)[0]) and first[cutting][2] == 0
@@ -366,7 +214,7 @@ def test_subset_calls_equal_the_model_and_a_twin_full_call(aead, gpu, oracle, ci
         wire.pos[j] += r[1]
     second = a.run("seal", wire, slots, max_frames=0)
     whole = [(f[0] + s[0], f[1] + s[1], s[2]) for f, s in zip(first, second)]
-    wire2 = G.Wire(torch, twin_streams(plain))
+    wire2 = Wire(torch, twin_streams(plain))
     twin = a2.run("seal", wire2)
     sealed, sealed2 = wire.streams(), wire2.streams()
     for j, i in enumerate(slots):
@@ -386,9 +234,9 @@ def test_subset_calls_equal_the_model_and_a_twin_full_call(aead, gpu, oracle, ci
         at, L = T.walk(sealed2[S_FORGED], 0)[0][-1]
         per_slot[S_FORGED][at + 3] ^= 0x20
     per_slot = [bytes(s) for s in per_slot]
-    wire = G.Wire(torch, entry_streams(per_slot))
+    wire = Wire(torch, entry_streams(per_slot))
     got = b.run("open", wire, slots, max_frames=big)
-    wire2 = G.Wire(torch, twin_streams(per_slot))
+    wire2 = Wire(torch, twin_streams(per_slot))
     twin = b2.run("open", wire2)
     opened, opened2 = wire.streams(), wire2.streams()
     for j, i in enumerate(slots):
@@ -400,9 +248,9 @@ def test_subset_calls_equal_the_model_and_a_twin_full_call(aead, gpu, oracle, ci
     else:  # alone: an unkeyed and an out-of-range entry
         for slot, code in ((S_UNKEYED, M.ERROR_INVALID_STATE), (TOP, M.ERROR_INVALID_PARAM), (N, M.ERROR_INVALID_PARAM)):
             for mode in ("seal", "open", "echo"):
-                assert a.run(mode, G.Wire(torch, [plain[5]]), [slot]) == [(0, 0, code)]
+                assert a.run(mode, Wire(torch, [plain[5]]), [slot]) == [(0, 0, code)]
     # an echo over the list: the server's two directions move together
-    wire = G.Wire(torch, entry_streams(plain))
+    wire = Wire(torch, entry_streams(plain))
     a.run("seal", wire, slots)
     b.run("echo", wire, slots)
     for tab in tabs.values():
@@ -418,9 +266,8 @@ def test_two_handshake_batches_key_one_table(aead, gpu, oracle, name):
     interleaved slots of an initiator and a responder table.  One session's
     messages are spoilt in flight: its slot stays unkeyed on both sides."""
     import torch
-    import test_gpu_handshake as H
     A = aead
-    v = H.basic_vector(name)
+    v = basic_vector(name)
     cipher = T.CHACHAPOLY if "ChaChaPoly" in name else T.AESGCM
     ini_tab, res_tab = (Table(A, torch, oracle, cipher, ini, 64) for ini in (True, False))
     batches = [(5, [1, 3, 5, 7, 9], None), (7, [0, 2, 4, 6, 8, 66, 10], 2)]
@@ -430,8 +277,8 @@ def test_two_handshake_batches_key_one_table(aead, gpu, oracle, name):
             rows = [bytearray(r) for r in rows]
             rows[spoilt][-1] ^= 0x01
             return [bytes(r) for r in rows]
-        sess = H.make_sessions(v, n, 70 + n)
-        r = H.handshake(A, torch, oracle, v, sess, tamper=tamper if spoilt is not None else None, seed=70 + n)
+        sess = make_sessions(v, n, 70 + n)
+        r = handshake(A, torch, oracle, v, sess, tamper=tamper if spoilt is not None else None, seed=70 + n)
         hands.append(r)
         want = [1 if i == spoilt else 0 for i in range(n)]
         assert [min(s, 1) for s in r["ini_status"]] == want and [min(s, 1) for s in r["res_status"]] == want
@@ -446,10 +293,10 @@ def test_two_handshake_batches_key_one_table(aead, gpu, oracle, name):
         assert tab.has_key() == [1 if i in keyed else 0 for i in range(N)]
         tab.check_contexts()
     tick = [4, 66, 1, 0, 9, 10, 2]  # the failed session's slot among those with traffic
-    plain = G.plain_streams(71, N, big=False)
+    plain = plain_streams(71, N, big=False)
     streams = [plain[i + 1] for i in range(len(tick))]
     for w, rd in ((ini_tab, res_tab), (res_tab, ini_tab), (ini_tab, res_tab)):
-        wire = G.Wire(torch, streams)
+        wire = Wire(torch, streams)
         w.run("seal", wire, tick, max_frames=32)
         results = rd.run("open", wire, tick)
         opened = wire.streams()
@@ -478,8 +325,8 @@ def test_small_objects_and_the_rules_that_need_an_object(aead, gpu, oracle):
         assert A.dev_transport_free(tr) == 0
     for cipher in CIPHERS:
         tab = Table(A, torch, oracle, cipher, True, 8, n=4)
-        slots, keys = dev_u32(torch, [2, 0, 9, 3]), dev_bytes(torch, bytes(range(128)) * 2)
-        wire = G.Wire(torch, [T.frame(bytes(20))] * 4)
+        slots, keys = dev_u32([2, 0, 9, 3]), dev_bytes(bytes(range(128)) * 2)
+        wire = Wire(torch, [T.frame(bytes(20))] * 4)
         off = torch.tensor(wire.offs, dtype=torch.int64, device="cuda")
         ln = torch.tensor(wire.lens, dtype=torch.int32, device="cuda")
         ok = dict(slots=slots.data_ptr(), wire=wire.dev.data_ptr(), off=off.data_ptr(), length=ln.data_ptr(),

@@ -17,12 +17,11 @@ instantiation, AES-GCM windows of every launch shape) batches.
 import numpy as np
 import pytest
 
-from test_gpu_parity import AES, CHACHA, dev, oracle_seal_records, prepare, stream, sync
+from aead_gpu import oracle_seal_records
+from gpu_support import AES, CHACHA, REC_DT, dev, prepare, stream, sync
+from gpu_support import FLAG_FAST as FAST, FLAG_VERIFY_FIRST as VF
 
 pytestmark = pytest.mark.gpu
-VF, FAST = 4, 1
-REC_DT = [("in_off", "<u8"), ("out_off", "<u8"), ("nonce", "<u8"), ("ctx_off", "<u8"),
-          ("ad_off", "<u8"), ("len", "<u4"), ("ad_len", "<u4")]
 
 
 # the kernel of each uniform case (noise_aead_debug_last_plan): the 4/8-lane

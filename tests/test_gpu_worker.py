@@ -6,7 +6,7 @@ units whose Poly1305 input is at most 256 blocks run the latency-first path
 (four lanes per ChaCha block, a Poly1305 tree over one block per lane);
 longer ones the multi-pass path (P ChaCha passes, G Poly1305 blocks per lane);
 AES-GCM gcm_wide_record in place in LDS.  The record lengths come from two
-sources: the hand-picked LENS x ADS below, and the cases that
+sources: the hand-picked sample of tests/aead_gpu.py (worker_cases), and the cases that
 tests/length_classes.py derives from the worker's own arithmetic (tree width,
 Horner depth G, ChaCha passes P, the worker_fast_fits border, the transport's
 chunks and raw tail), run by the test_worker_length_classes_* tests.  Every case is checked
@@ -22,31 +22,10 @@ import sys
 
 import pytest
 
+from aead_gpu import worker_cases as _cases
+from gpu_support import AES, CHACHA
+
 pytestmark = pytest.mark.gpu
-
-CHACHA, AES = 0x4301, 0x4302
-
-# hand-picked lengths: one unit, unit boundaries, 63 units (4032 B), the
-# 256-block Poly limit with a 256-byte AD (3824 B), then some of the multi-pass
-# path (worker_chacha_multi) up to the 65519-byte maximum.  They are a sample,
-# not the paths' cases: tests/length_classes.py derives those (wfast, wmulti,
-# wtransport) and test_worker_length_classes_* below run them;
-# tests/test_length_classes_host.py counts what this list reaches of them
-LENS = [0, 1, 15, 16, 17, 63, 64, 65, 100, 127, 128, 129, 1023, 1024, 1025, 1400,
-        2047, 2048, 3823, 3824, 3825, 4031, 4032, 4033, 4096, 8000, 16384, 16385, 20000,
-        40001, 65519]
-ADS = [0, 1, 16, 17, 32, 255, 256]
-
-
-def _cases():
-    rnd = random.Random(0x5EED)
-    out = []
-    for L in LENS:
-        for A in ADS:
-            if rnd.random() < 0.5 and L not in (0, 3824, 4032, 4033, 65519) and A not in (0, 256):
-                continue  # a sample of the grid, the edges always
-            out.append((L, A))
-    return out
 
 
 @pytest.mark.parametrize("cipher", [CHACHA, AES])

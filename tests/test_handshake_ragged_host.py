@@ -15,14 +15,11 @@ the header's list.  It runs here once, as a plain child process."""
 import functools
 import json
 import os
-import subprocess
 
 import handshake_model as M
 import handshake_ragged_model as R
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-LIB = os.path.join(ROOT, "noise-c_amd")
-CHECK = os.path.join(LIB, "asan", "handshake_ragged_check")
+import host_check
+from host_check import ROOT
 FIXTURE = os.path.join(ROOT, "tests", "golden", "handshake_lengths.json")
 LENGTHS = [0, 1, 15, 16, 17, 31, 32, 33, 63, 64, 65, 111, 112, 127, 128, 129, 257]
 
@@ -158,12 +155,7 @@ def test_model_equals_session_on_every_in_scope_vector(oracle):
 
 @functools.lru_cache(maxsize=None)
 def run_check():
-    subprocess.run(["make", "-s", "-C", LIB, "handshake_ragged_check"], check=True)
-    r = subprocess.run([CHECK], capture_output=True, text=True, timeout=300)
-    out = r.stdout[-3000:] + r.stderr[-3000:]
-    assert r.returncode == 0, out
-    assert "AddressSanitizer" not in out and "runtime error" not in out, out
-    return r.stdout.splitlines()
+    return host_check.run_check("handshake_ragged_check", timeout=300).stdout.splitlines()
 
 
 def test_length_function_equals_the_model_rule():

@@ -5,8 +5,8 @@ import numpy as np
 import pytest
 
 import length_classes as C
-from test_gpu_parity import AES, CHACHA, LENS
-from test_gpu_seg import EDGE_LENS
+from aead_gpu import EDGE_LENS, LENS
+from gpu_support import AES, CHACHA
 
 IL_CASES = {4: 89, 8: 185, 16: 377, 32: 761, 64: 1529}      # 24 K - 7
 # the pairs (o, steps) and triples (q, partial, steps) alone take 30 / 38 / 54 / 86 / 150
@@ -172,9 +172,9 @@ def _old_worker_records():
     """the hand-written (len, ad_len) of the worker's older ChaChaPoly tests,
     imported from where they are used"""
     import edge_records as E
-    import test_gpu_worker as W
     import worker_mode_check as M
-    old = set(W._cases())
+    from aead_gpu import worker_cases
+    old = set(worker_cases())
     old |= {(L, A) for L in M.MAIN_LENS for A in M.MAIN_ADS}
     old |= {(L, A) for A in M.HEAD_EDGE_ADS for L in M.head_edge_lens(A)}
     for name, (cipher, _seed, lens, ads) in E.RAGGED_SHAPES.items():

@@ -9,37 +9,19 @@ import os
 import pytest
 
 from oracle import RandSnapshot, REF_FULL_SO
+from randstate_ref import ref_randstate, snapshot_of
 
 ZERO, RANDOM = 0x4701, 0x4702
 
 
 def _ref_randstate():
-    """A reference RandState (OS-seeded) and a snapshot of its generator:
-    struct NoiseRandState_s {size_t size; size_t left; chacha_ctx chacha;}
-    (randstate.c:47-58), chacha input words 4..15 = key, counter, IV."""
+    """randstate_ref.ref_randstate, the reference library built first where it can be"""
     if not os.path.exists(REF_FULL_SO):
         if not os.path.isdir("/root/reference/src"):
             pytest.skip("reference library not built (GPU box without oracle/_ref)")
         import subprocess
         subprocess.run(["make", "-s", "-C", os.path.dirname(REF_FULL_SO) + "/..", "full"], check=True)
-    R = C.CDLL(REF_FULL_SO)
-    R.noise_randstate_new.argtypes = [C.POINTER(C.c_void_p)]
-    R.noise_randstate_pad.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_size_t, C.c_int]
-    R.noise_randstate_free.argtypes = [C.c_void_p]
-    st = C.c_void_p()
-    assert R.noise_randstate_new(C.byref(st)) == 0
-    return R, st
-
-
-def snapshot_of(st):
-    w = (C.c_uint32 * 16).from_address(st.value + 16)
-    s = RandSnapshot()
-    for i in range(8):
-        s.key[i] = w[4 + i]
-    s.counter = w[12] | (w[13] << 32)
-    s.iv = w[14] | (w[15] << 32)
-    s.left = C.c_size_t.from_address(st.value + 8).value
-    return s
+    return ref_randstate()
 
 
 def test_oracle_pad_equals_reference_randstate(oracle):

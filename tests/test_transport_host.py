@@ -9,19 +9,8 @@ the frames one by one, and the argument checks of noise_aead_dev_transport_*
 against a byte-by-byte reading of the header comment.  It runs here as a plain
 child process.  The same argument rules then go through the library itself;
 no launch happens."""
-import os
-import subprocess
-
 import transport_model as T
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-LIB = os.path.join(ROOT, "noise-c_amd")
-CHECK = os.path.join(LIB, "asan", "transport_check")
-
-
-def run_check(feed):
-    subprocess.run(["make", "-s", "-C", LIB, "transport_check"], check=True)
-    return subprocess.run([CHECK], input=feed, capture_output=True, text=True, timeout=120)
+from host_check import run_check
 
 
 def test_model_walk_on_the_cases_spelled_out():
@@ -58,10 +47,7 @@ def test_model_cap_rule():
 
 def test_walk_cap_and_argument_rules_under_sanitizers():
     cases = T.walk_cases()
-    r = run_check("".join(T.walk_case_line(s, n, b) for _, s, n, b in cases))
-    out = r.stdout[-3000:] + r.stderr[-3000:]
-    assert r.returncode == 0, out
-    assert "AddressSanitizer" not in out and "runtime error" not in out, out
+    r = run_check("transport_check", feed="".join(T.walk_case_line(s, n, b) for _, s, n, b in cases))
     last = r.stdout.splitlines()[-1].split()
     assert last[0] == "transport_check:" and last[2] == "walks" and last[-1] == "failures"
     assert int(last[1]) == len(cases) >= 20 and int(last[3]) > 10000 and last[5] == "0", last
@@ -70,11 +56,11 @@ def test_walk_cap_and_argument_rules_under_sanitizers():
     frames, consumed, stop = T.walk(s, n, b)
     for wrong, word in (((len(frames) + 1, consumed, stop), "FAIL walk"), ((len(frames), consumed - 1, stop), "FAIL walk"),
                         ((len(frames), consumed, T.ERROR_INVALID_LENGTH), "FAIL walk")):
-        r = run_check(T.walk_case_line(s, n, b, wrong))
+        r = run_check("transport_check", feed=T.walk_case_line(s, n, b, wrong), checked=False)
         assert r.returncode == 1 and word in r.stderr, r.stdout + r.stderr
         assert "transport_check: 1 walks" in r.stdout and r.stdout.split()[-2] == "1"
     # and a line it cannot read is a failure, not a skipped case
-    r = run_check("zz 0 0 0 0 0\n")
+    r = run_check("transport_check", feed="zz 0 0 0 0 0\n", checked=False)
     assert r.returncode == 1 and "FAIL input" in r.stderr, r.stdout + r.stderr
 
 

@@ -8,17 +8,11 @@ process: the slot of a call's entry on heap lists of exactly their length, and
 the new argument checks against a byte-by-byte reading of the header; then the
 same argument rules through the library itself, on never-dereferenced
 pointers.  No launch happens."""
-import os
-import subprocess
-
 import numpy as np
 
 import transport_model as T
 import transport_table_model as M
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-LIB = os.path.join(ROOT, "noise-c_amd")
-CHECK = os.path.join(LIB, "asan", "transport_table_check")
+from host_check import run_check
 
 
 def _sessions(oracle, cipher, n, dead):
@@ -74,27 +68,20 @@ def test_splice_equals_a_batch_with_empty_streams(oracle):
     assert sum(g[1][0] for g in got) == 7
 
 
-def run_check(*args):
-    subprocess.run(["make", "-s", "-C", LIB, "transport_table_check"], check=True)
-    return subprocess.run([CHECK, *args], capture_output=True, text=True, timeout=120)
-
-
 def test_slots_and_argument_rules_under_sanitizers():
-    r = run_check()
-    out = r.stdout[-3000:] + r.stderr[-3000:]
-    assert r.returncode == 0, out
-    assert "AddressSanitizer" not in out and "runtime error" not in out, out
+    r = run_check("transport_table_check")
     last = r.stdout.splitlines()[-1].split()
     assert last[0] == "transport_table_check:" and last[2] == "checks" and last[4] == "failures"
     assert int(last[1]) > 10000 and last[3] == "0", last
     # an expectation of ours that holds, and wrong ones: the program does compare
-    r = run_check("expect", "67", "66", "1", "expect", "67", "67", "0", "expect", "67", str(2 ** 32 - 1), "0")
+    r = run_check("transport_table_check", "expect", "67", "66", "1", "expect", "67", "67", "0", "expect", "67", str(2 ** 32 - 1), "0",
+                  checked=False)
     assert r.returncode == 0 and r.stdout.split()[-2] == "0", r.stdout + r.stderr
     for wrong in (("67", "67", "1"), ("67", "66", "0"), ("67", str(2 ** 32 - 1), "1")):
-        r = run_check("expect", *wrong)
+        r = run_check("transport_table_check", "expect", *wrong, checked=False)
         assert r.returncode == 1 and "FAIL expect" in r.stderr, r.stdout + r.stderr
         assert r.stdout.split()[-2] == "1"
-    r = run_check("something else")
+    r = run_check("transport_table_check", "something else", checked=False)
     assert r.returncode == 1 and "FAIL argument" in r.stderr
 
 

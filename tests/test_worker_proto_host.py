@@ -12,20 +12,11 @@ heap areas, decodes the way aead_worker does and compares byte for byte.
 -fsanitize=address,undefined -fno-sanitize-recover=all; it runs here as a
 plain child process.
 """
-import os
-import subprocess
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-LIB = os.path.join(ROOT, "noise-c_amd")
+from host_check import run_check
 
 
 def test_worker_protocol_encode_decode_under_sanitizers():
-    subprocess.run(["make", "-s", "-C", LIB, "worker_proto_check"], check=True)
-    r = subprocess.run([os.path.join(LIB, "asan", "worker_proto_check")], capture_output=True, text=True,
-                       timeout=120)
-    out = r.stdout + r.stderr
-    assert r.returncode == 0, out[-4000:]
-    assert "AddressSanitizer" not in out and "runtime error" not in out, out[-4000:]
+    r = run_check("worker_proto_check")
     line = [l for l in r.stdout.splitlines() if l.startswith("worker_proto_check:")][-1].split()
     # 2 placements x 2 directions x 6 AD lengths x 8 reachable totals x 4 numbers
     assert int(line[1]) == 768 and line[-2] == "0", r.stdout[-2000:]

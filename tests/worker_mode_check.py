@@ -302,7 +302,7 @@ def head_edges():
     return 0
 
 
-CHACHA, AES = 0x4301, 0x4302
+CHACHA, AES = aead.CHACHAPOLY, aead.AESGCM
 NONCE0 = (1 << 32) - 3  # both nonce words live: the counter crosses 2^32 inside every run
 
 
