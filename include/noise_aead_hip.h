@@ -941,6 +941,65 @@ int noise_aead_dev_transport_open_datagrams(NoiseAeadDevTransport *tr, const uin
                                             uint8_t *d_frame_status, void *stream);
 uint64_t *noise_aead_dev_transport_replay(const NoiseAeadDevTransport *tr, uint32_t *bits);
 
+/* ------------------------------------------------ 12. rekey on the device
+ * CipherState.Rekey() of the Noise specification (4.2, 11.3): k = REKEY(k),
+ * n untouched, for raw keys and for the slots of a transport object — what a
+ * session that lives as long as its server needs, with nothing passing
+ * through the host.  The reference (noise-c v0.0.1) has no rekey; this is the
+ * specification's, on the reference's nonce layouts.
+ *
+ * REKEY(k) is the first 32 bytes of ENCRYPT(k, 2^64 - 1, "", 32 zero bytes);
+ * no tag is computed:
+ *   ChaChaPoly  bytes 0..31 of the ChaCha20 block under k, block counter 1
+ *               (counter 0 is the Poly1305 key), 64-bit IV 0xFFFFFFFFFFFFFFFF;
+ *   AES-GCM     AES256_k(00000000 || FF x 8 || 00000002) ||
+ *               AES256_k(00000000 || FF x 8 || 00000003): the first two CTR
+ *               blocks under J0 = 0^32 || BE64(2^64 - 1) || 00000001.
+ *
+ * noise_aead_dev_rekey: key i is the 32 bytes at d_keys + 32 i, its successor
+ * goes to d_out + 32 i (the packing of noise_aead_dev_split and _prepare).  No
+ * alignment is needed; d_out == d_keys (in place) is allowed.  Asynchronous on
+ * `stream`, allocates nothing, never synchronises.  Checked on the host before
+ * any launch, in this order:
+ *   1. a cipher other than ChaChaPoly / AESGCM gives NOISE_ERROR_UNKNOWN_ID,
+ *      also with n == 0;
+ *   2. n == 0 gives NOISE_ERROR_NONE, and nothing is launched;
+ *   3. a NULL pointer gives NOISE_ERROR_INVALID_PARAM;
+ *   4. [d_out, + 32 n) meeting [d_keys, + 32 n) other than exactly in place
+ *      gives NOISE_ERROR_INVALID_PARAM.
+ *
+ * noise_aead_dev_transport_rekey: entry j (j < m) is slot d_slots[j], or slot
+ * j when d_slots is NULL, as in section 11.  The directions it rekeys are
+ * directions & (d_which ? d_which[j] : 3): bit 0 is send, bit 1 is receive.
+ * The per-entry byte lets a caller's own device-side policy (a kernel that
+ * looks at the nonces, say) pick the slots without the host reading anything,
+ * as d_status does for _set_keys.  For each chosen direction the slot's key
+ * context becomes, byte for byte, the context noise_aead_dev_prepare builds
+ * from REKEY(k) of the key it was built from.  Nothing else of the object
+ * changes: not the nonce of that direction (the specification's Rekey leaves n
+ * alone; _nonces is writable for a caller that wants otherwise), not the
+ * anti-replay window, not the state byte, not the other direction, no slot
+ * that is not named.  An entry whose slot is out of range or unkeyed is
+ * ignored: nothing is read or written, and an unkeyed slot stays all-zero.
+ * The listed slots must be distinct: the caller's guarantee, as in section 10.
+ * Calls in stream order compose: three calls with no synchronisation between
+ * them leave REKEY(REKEY(REKEY(k))).  Both peers of a session rekey the same
+ * direction at the same counter: the sender its send direction, the receiver
+ * its receive direction.  Asynchronous on
+ * `stream`, allocates nothing, copies nothing to the host and never
+ * synchronises.  Checked on the host before any launch, in this order:
+ *   1. a NULL tr gives NOISE_ERROR_INVALID_PARAM;
+ *   2. m == 0 gives NOISE_ERROR_NONE, and nothing is launched;
+ *   3. m > n gives NOISE_ERROR_INVALID_PARAM;
+ *   4. directions equal to 0 or above 3 gives NOISE_ERROR_INVALID_PARAM.
+ * A refused call leaves the object as it was. */
+int noise_aead_dev_rekey(int cipher_id, const uint8_t *d_keys, uint32_t n, uint8_t *d_out, void *stream);
+
+#define NOISE_AEAD_REKEY_SEND    1u
+#define NOISE_AEAD_REKEY_RECEIVE 2u
+int noise_aead_dev_transport_rekey(NoiseAeadDevTransport *tr, const uint32_t *d_slots /* may be NULL */, uint32_t m,
+                                   uint32_t directions, const uint8_t *d_which /* may be NULL */, void *stream);
+
 /* ------------------------------------------------ error reports
  * include/noise/protocol/errors.h; src/protocol/errors.c:92-127. */
 void noise_perror(const char *s, int err);

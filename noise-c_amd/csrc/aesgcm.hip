@@ -304,8 +304,45 @@ NA_DEV void gf_mul_bytes(const uint8_t x[16], const uint8_t h[16], uint8_t out[1
 }
 
 #ifndef NA_NO_SETUP_KERNELS
+/* Word i (8 <= i < 60) of the AES-256 key schedule (FIPS-197 5.2) from the
+   words before it; sb in LDS.  The callers loop over it: gcm_prepare_one on
+   round keys in LDS, gcm_rekey_keys unrolled on round keys in registers. */
+NA_DEV void aes256_expand_word(uint32_t *rk, const uint32_t *sb, int i, uint32_t &rcon)
+{
+    uint32_t tmp = rk[i - 1];
+    if (i % 8 == 0) {
+        tmp = (tmp << 8) | (tmp >> 24); /* RotWord */
+        tmp = (sb[tmp >> 24] << 24) | (sb[(tmp >> 16) & 255] << 16) |
+              (sb[(tmp >> 8) & 255] << 8) | sb[tmp & 255];
+        tmp ^= rcon << 24;
+        rcon = xtime8(rcon);
+    } else if (i % 8 == 4) {
+        tmp = (sb[tmp >> 24] << 24) | (sb[(tmp >> 16) & 255] << 16) |
+              (sb[(tmp >> 8) & 255] << 8) | sb[tmp & 255];
+    }
+    rk[i] = rk[i - 8] ^ tmp;
+}
+
+/* REKEY(k) of the key whose round keys are rk (header section 12): the two
+   CTR blocks of transport_plan.h tr_rekey_aes_word.  The blocks' big-endian
+   words are the successor's first eight round-key words as they stand. */
+NA_DEV void aes256_rekey(const uint32_t *rk, const uint32_t *te, const uint32_t *sb, uint32_t next[8])
+{
+#pragma unroll
+    for (uint32_t b = 0; b < 2; ++b) {
+        uint32_t s0 = tr_rekey_aes_word(b, 0), s1 = tr_rekey_aes_word(b, 1), s2 = tr_rekey_aes_word(b, 2),
+                 s3 = tr_rekey_aes_word(b, 3);
+        aes256_block(rk, te, sb, s0, s1, s2, s3);
+        next[4 * b] = s0; next[4 * b + 1] = s1; next[4 * b + 2] = s2; next[4 * b + 3] = s3;
+    }
+}
+
 /* One workgroup of 256 threads builds one state from the 32 key bytes at k:
-   round keys, H, and the H^1..H^4 tables. */
+   round keys, H, and the H^1..H^4 tables.  REKEY: the key is REKEY of the key
+   the state at c was built from instead (k is not looked at).  The old round
+   keys are read into LDS before the first barrier and every store to c comes
+   after the last, so no lane overwrites what another still has to read. */
+template <bool REKEY = false>
 __device__ __forceinline__ void gcm_prepare_one(const uint8_t *__restrict__ k, AesCtx *__restrict__ c)
 {
     __shared__ uint32_t te[256], sb[256], rk[60];
@@ -314,26 +351,20 @@ __device__ __forceinline__ void gcm_prepare_one(const uint8_t *__restrict__ k, A
     const int t = threadIdx.x;
     te[t] = g_te0[t];
     sb[t] = g_sbox[t];
+    if (REKEY && t < 60) rk[t] = c->rk[t];
     __syncthreads();
     if (t == 0) {
-        for (int i = 0; i < 8; ++i)
-            rk[i] = ((uint32_t)k[4 * i] << 24) | ((uint32_t)k[4 * i + 1] << 16) |
-                    ((uint32_t)k[4 * i + 2] << 8) | k[4 * i + 3];
-        uint32_t rcon = 1;
-        for (int i = 8; i < 60; ++i) {
-            uint32_t tmp = rk[i - 1];
-            if (i % 8 == 0) {
-                tmp = (tmp << 8) | (tmp >> 24); /* RotWord */
-                tmp = (sb[tmp >> 24] << 24) | (sb[(tmp >> 16) & 255] << 16) |
-                      (sb[(tmp >> 8) & 255] << 8) | sb[tmp & 255];
-                tmp ^= rcon << 24;
-                rcon = xtime8(rcon);
-            } else if (i % 8 == 4) {
-                tmp = (sb[tmp >> 24] << 24) | (sb[(tmp >> 16) & 255] << 16) |
-                      (sb[(tmp >> 8) & 255] << 8) | sb[tmp & 255];
-            }
-            rk[i] = rk[i - 8] ^ tmp;
+        if constexpr (REKEY) {
+            uint32_t next[8];
+            aes256_rekey(rk, te, sb, next);
+            for (int i = 0; i < 8; ++i) rk[i] = next[i];
+        } else {
+            for (int i = 0; i < 8; ++i)
+                rk[i] = ((uint32_t)k[4 * i] << 24) | ((uint32_t)k[4 * i + 1] << 16) |
+                        ((uint32_t)k[4 * i + 2] << 8) | k[4 * i + 3];
         }
+        uint32_t rcon = 1;
+        for (int i = 8; i < 60; ++i) aes256_expand_word(rk, sb, i, rcon);
         uint32_t s0 = 0, s1 = 0, s2 = 0, s3 = 0;
         aes256_block(rk, te, sb, s0, s1, s2, s3);
         const uint32_t hw[4] = {s0, s1, s2, s3};
@@ -403,6 +434,55 @@ __global__ __launch_bounds__(256) void gcm_prepare_slots(const uint32_t *__restr
     if (!tr_slot(slots, j, n, &i) || (status && status[j])) return;
     const uint8_t *keys = (receive != 0) == (initiator != 0) ? k2 : k1;
     gcm_prepare_one(keys + (size_t)j * 32, ctx + ((size_t)receive * n + i));
+}
+
+/* Rekey of a transport object's slots (transport.hip, _rekey; header section
+   12): one workgroup per (entry, direction), 2m in all, laid out as
+   gcm_prepare_slots is.  A workgroup whose direction the call does not choose
+   for its entry (tr_rekey_directions), or whose entry's slot is out of range
+   or unkeyed, returns at once; the others rebuild the context in place from
+   REKEY of its own key. */
+__global__ __launch_bounds__(256) void gcm_rekey_slots(const uint32_t *__restrict__ slots, uint32_t m, uint32_t n,
+                                                       uint32_t directions, const uint8_t *__restrict__ which,
+                                                       const uint8_t *__restrict__ keyed, AesCtx *__restrict__ ctx)
+{
+    const uint32_t j = blockIdx.x >> 1, receive = blockIdx.x & 1;
+    if (j >= m) return;
+    uint32_t i;
+    if (!tr_slot(slots, j, n, &i) || !keyed[i]) return;
+    if (!((tr_rekey_directions(directions, which, j) >> receive) & 1)) return;
+    gcm_prepare_one<true>(nullptr, ctx + ((size_t)receive * n + i));
+}
+
+/* REKEY of raw keys (noise_aead_dev_rekey): one lane per key expands it into
+   registers and runs the two blocks over the workgroup's LDS copy of the
+   tables.  Any alignment; out may be keys (a lane reads its key before it
+   writes). */
+constexpr uint32_t GCM_REKEY_BLOCK = 64;
+
+__global__ __launch_bounds__(GCM_REKEY_BLOCK) void gcm_rekey_keys(const uint8_t *keys, uint8_t *out, uint32_t n)
+{
+    __shared__ uint32_t te[256], sb[256];
+    for (uint32_t e = threadIdx.x; e < 256; e += GCM_REKEY_BLOCK) {
+        te[e] = g_te0[e];
+        sb[e] = g_sbox[e];
+    }
+    __syncthreads();
+    const uint32_t i = blockIdx.x * GCM_REKEY_BLOCK + threadIdx.x;
+    if (i >= n) return;
+    const uint8_t *k = keys + (size_t)i * 32;
+    uint32_t rk[60], next[8];
+#pragma unroll
+    for (int w = 0; w < 8; ++w)
+        rk[w] = ((uint32_t)k[4 * w] << 24) | ((uint32_t)k[4 * w + 1] << 16) | ((uint32_t)k[4 * w + 2] << 8) | k[4 * w + 3];
+    uint32_t rcon = 1;
+#pragma unroll
+    for (int w = 8; w < 60; ++w) aes256_expand_word(rk, sb, w, rcon);
+    aes256_rekey(rk, te, sb, next);
+    uint8_t *o = out + (size_t)i * 32;
+#pragma unroll
+    for (int w = 0; w < 8; ++w)
+        for (int b = 0; b < 4; ++b) o[4 * w + b] = (uint8_t)(next[w] >> (24 - 8 * b));
 }
 #endif
 

@@ -276,6 +276,18 @@ inline int check_dh(int dh_id, const void *priv, uint64_t priv_stride, bool has_
     return NOISE_ERROR_NONE;
 }
 
+/* REKEY of n raw 32-byte keys (noise_aead_dev_rekey, header section 12): the
+   successors may go exactly where the keys are, and nowhere else that meets
+   them.  NOISE_ERROR_NONE with n == 0 means "nothing to do". */
+inline int check_rekey(int cipher_id, const void *keys, uint32_t n, const void *out)
+{
+    if (cipher_id != NOISE_CIPHER_CHACHAPOLY && cipher_id != NOISE_CIPHER_AESGCM) return NOISE_ERROR_UNKNOWN_ID;
+    if (!n) return NOISE_ERROR_NONE;
+    if (!keys || !out) return NOISE_ERROR_INVALID_PARAM;
+    if (out != keys && meet(dh_key_span(out, 32, n), dh_key_span(keys, 32, n))) return NOISE_ERROR_INVALID_PARAM;
+    return NOISE_ERROR_NONE;
+}
+
 /* ------------------------------------------------------ the facts of a job
    FAST layout (chachapoly.hip): 16-B aligned record slots whose input may be
    read up to roundup64(len) — and, for open, holds CT || tag. */

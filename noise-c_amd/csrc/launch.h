@@ -105,5 +105,14 @@ NA_HIDDEN int aes_prepare(const uint8_t *raw_keys, uint32_t n_states, void *ctx,
    status byte (status may be null) are left alone.  Builds the tables first. */
 NA_HIDDEN int aes_prepare_slots(const uint32_t *slots, uint32_t m, uint32_t n, const uint8_t *k1, const uint8_t *k2,
                                 const uint8_t *status, bool initiator, void *ctx, hipStream_t s);
+/* rekey of a transport object's slots (header section 12): entry j < m is slot
+   slots[j] of n (slots may be null: slot j); the contexts of its directions
+   directions & (which ? which[j] : 3) are rebuilt in place from REKEY of their
+   own keys.  Entries out of range or with a zero byte in keyed (per slot) are
+   left alone.  Builds the tables first. */
+NA_HIDDEN int aes_rekey_slots(const uint32_t *slots, uint32_t m, uint32_t n, uint32_t directions, const uint8_t *which,
+                              const uint8_t *keyed, void *ctx, hipStream_t s);
+/* REKEY of n raw keys, 32 bytes apart, to out (which may be keys); builds the tables first */
+NA_HIDDEN int aes_rekey_keys(const uint8_t *keys, uint32_t n, uint8_t *out, hipStream_t s);
 
 } // namespace na

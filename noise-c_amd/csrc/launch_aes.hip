@@ -130,6 +130,24 @@ int aes_prepare_slots(const uint32_t *slots, uint32_t m, uint32_t n, const uint8
     return hip_rc(hipGetLastError());
 }
 
+int aes_rekey_slots(const uint32_t *slots, uint32_t m, uint32_t n, uint32_t directions, const uint8_t *which,
+                    const uint8_t *keyed, void *ctx, hipStream_t s)
+{
+    if (!m) return NOISE_ERROR_NONE;
+    if (m > 0x7fffffffu / 2) return NOISE_ERROR_INVALID_PARAM; /* 2m workgroups in one grid */
+    const int rc = hip_rc(ensure_aes_tables());
+    if (rc) return rc;
+    hipLaunchKernelGGL(gcm_rekey_slots, dim3(2 * m), dim3(256), 0, s, slots, m, n, directions, which, keyed, (AesCtx *)ctx);
+    return hip_rc(hipGetLastError());
+}
+
+int aes_rekey_keys(const uint8_t *keys, uint32_t n, uint8_t *out, hipStream_t s)
+{
+    if (!n) return NOISE_ERROR_NONE;
+    const int rc = hip_rc(ensure_aes_tables());
+    return rc ? rc : launch_items(gcm_rekey_keys, n, GCM_REKEY_BLOCK, s, keys, out, n);
+}
+
 int aes_launch(const Plan &p, const PlanArgs &args, hipStream_t s)
 {
     using UniformFn = void (*)(UniformArgs);

@@ -1,6 +1,6 @@
 /*
  * transport.hip — device-resident transport sessions:
- * noise_aead_dev_transport_* (include/noise_aead_hip.h sections 9 to 11).
+ * noise_aead_dev_transport_* (include/noise_aead_hip.h sections 9 to 12).
  *
  * The object holds, for n sessions, a send and a receive key context and a
  * send and a receive nonce on the device, and what a call needs: descriptors
@@ -63,9 +63,20 @@
  *   tr_commit_datagrams  open: one lane per entry walks its frames in order
  *                with the window evolving: refused before (status 2) or by
  *                now -> 5, tag failed -> 1, else tr_replay_accept -> 0.
+ *
+ * Rekey (section 12): a key, or a slot's key context, becomes its successor
+ * REKEY(k) on the device in stream order; nonces, windows and state bytes are
+ * not touched.
+ *   tr_rekey_keys / tr_rekey_slots  ChaChaPoly: one ChaCha20 block in registers
+ *                (tr_rekey_chacha), a lane per key, or per (entry, direction)
+ *                in place on the object's contexts: the context is the key;
+ *   AES-GCM      gcm_rekey_keys / gcm_rekey_slots (aesgcm.hip), next to the
+ *                tables: the two blocks under the context's own round keys,
+ *                then the context rebuilt by gcm_prepare_one.
  */
 #include "launch.h"
 
+#include "aead_device.h"
 #include "transport_plan.h"
 
 #include <new>
@@ -401,6 +412,60 @@ __global__ __launch_bounds__(TR_WIDE_BLOCK) void tr_clear_wide(TrKeyArgs a)
     for (uint64_t w = threadIdx.x, words = a.ctx_bytes / 16; w < words; w += TR_WIDE_BLOCK) c[w] = make_uint4(0, 0, 0, 0);
 }
 
+/* ---- rekey (section 12) */
+
+/* REKEY(k) of the 32 key bytes at src, any alignment: bytes 0..31 of one
+   ChaCha20 block (transport_plan.h TR_REKEY_CHACHA_*), all in registers;
+   neither a branch nor an address depends on a key byte */
+TR_DEV void tr_rekey_chacha(const uint8_t *src, uint32_t next[8])
+{
+    const uint4 lo = tr_load_key16(src), hi = tr_load_key16(src + 16);
+    const uint32_t key[8] = {lo.x, lo.y, lo.z, lo.w, hi.x, hi.y, hi.z, hi.w};
+    uint32_t x[16];
+    chacha20_block(key, TR_REKEY_CHACHA_COUNTER, 0, TR_REKEY_CHACHA_IV_LO, TR_REKEY_CHACHA_IV_HI, x);
+#pragma unroll
+    for (int w = 0; w < 8; ++w) next[w] = x[w];
+}
+
+/* raw keys: lane i turns the key at keys + 32 i into the one at out + 32 i
+   (out may be keys: a lane reads its key before it writes) */
+__global__ __launch_bounds__(TR_BLOCK) void tr_rekey_keys(const uint8_t *keys, uint8_t *out, uint32_t n)
+{
+    const uint32_t i = blockIdx.x * TR_BLOCK + threadIdx.x;
+    if (i >= n) return;
+    uint32_t next[8];
+    tr_rekey_chacha(keys + (uint64_t)i * 32, next);
+    uint8_t *o = out + (uint64_t)i * 32;
+#pragma unroll
+    for (int w = 0; w < 8; ++w)
+        for (int b = 0; b < 4; ++b) o[4 * w + b] = (uint8_t)(next[w] >> (8 * b));
+}
+
+struct TrRekeyArgs {
+    const uint32_t *slots;       /* may be null: entry j is slot j */
+    const uint8_t *which;        /* may be null: every entry takes the call's directions */
+    const uint8_t *keyed;
+    uint8_t *ctx;                /* n send contexts, then n receive contexts */
+    uint32_t m, n, directions;
+};
+
+/* the slots of an object, in place: one lane per (entry, direction), 2m in all */
+__global__ __launch_bounds__(TR_BLOCK) void tr_rekey_slots(TrRekeyArgs a)
+{
+    const uint64_t t = (uint64_t)blockIdx.x * TR_BLOCK + threadIdx.x;
+    const uint32_t receive = (uint32_t)t & 1;
+    if (t >> 1 >= a.m) return;
+    const uint32_t j = (uint32_t)(t >> 1);
+    uint32_t i;
+    if (!tr_slot(a.slots, j, a.n, &i) || !a.keyed[i]) return;
+    if (!((tr_rekey_directions(a.directions, a.which, j) >> receive) & 1)) return;
+    uint8_t *c = a.ctx + ((uint64_t)receive * a.n + i) * 32;
+    uint32_t next[8];
+    tr_rekey_chacha(c, next);
+    ((uint4 *)c)[0] = make_uint4(next[0], next[1], next[2], next[3]);
+    ((uint4 *)c)[1] = make_uint4(next[4], next[5], next[6], next[7]);
+}
+
 } // namespace
 
 struct NoiseAeadDevTransport {
@@ -648,6 +713,27 @@ int noise_aead_dev_transport_clear_keys(NoiseAeadDevTransport *tr, const uint32_
     const int rc = tr_check_clear_keys(tr, tr ? tr->n : 0, d_slots, m);
     if (rc || !m) return rc;
     return launch_clear(tr, key_args(tr, d_slots, m), (hipStream_t)stream);
+}
+
+int noise_aead_dev_rekey(int cipher_id, const uint8_t *d_keys, uint32_t n, uint8_t *d_out, void *stream)
+{
+    const int rc = check_rekey(cipher_id, d_keys, n, d_out);
+    if (rc || !n) return rc;
+    hipStream_t s = (hipStream_t)stream;
+    if (cipher_id == NOISE_CIPHER_CHACHAPOLY) return launch_items(tr_rekey_keys, n, TR_BLOCK, s, d_keys, d_out, n);
+    return aes_rekey_keys(d_keys, n, d_out, s);
+}
+
+int noise_aead_dev_transport_rekey(NoiseAeadDevTransport *tr, const uint32_t *d_slots, uint32_t m, uint32_t directions,
+                                   const uint8_t *d_which, void *stream)
+{
+    const int rc = tr_check_rekey(tr, tr ? tr->n : 0, m, directions);
+    if (rc || !m) return rc;
+    hipStream_t s = (hipStream_t)stream;
+    if (tr->cipher_id != NOISE_CIPHER_CHACHAPOLY)
+        return aes_rekey_slots(d_slots, m, tr->n, directions, d_which, tr->keyed, tr->ctx, s);
+    const TrRekeyArgs a = {d_slots, d_which, tr->keyed, tr->ctx, m, tr->n, directions};
+    return launch_items(tr_rekey_slots, 2 * (uint64_t)m, TR_BLOCK, s, a);
 }
 
 const uint8_t *noise_aead_dev_transport_has_key(const NoiseAeadDevTransport *tr)

@@ -3,11 +3,13 @@
  * sessions (noise_aead_dev_transport_*, include/noise_aead_hip.h section 9):
  * the frame walk of one session, the cap rule across sessions, the slot of a
  * call's entry (section 10, the session table), the anti-replay window of the
- * datagram calls (section 11), and the argument checks.  One source for both compilers, as fe25519.h is: hipcc's
+ * datagram calls (section 11), the counter blocks and the direction rule of
+ * rekey (section 12), and the argument checks.  One source for both compilers, as fe25519.h is: hipcc's
  * device pass builds the kernels of transport.hip from tr_walk and tr_cap,
- * plain g++ builds asan/transport_check.cpp, asan/transport_table_check.cpp
- * and asan/transport_datagram_check.cpp from them, so the CPU check under
- * ASan/UBSan runs the walk and the window rule the GPU runs.
+ * plain g++ builds asan/transport_check.cpp, asan/transport_table_check.cpp,
+ * asan/transport_datagram_check.cpp and asan/transport_rekey_check.cpp from
+ * them, so the CPU check under ASan/UBSan runs the walk, the window rule and
+ * the direction rule the GPU runs.
  *
  * The wire format is that of csrc/wire.c (echo-common.c:643-688): a 2-byte
  * big-endian length L, then L bytes of CT || tag; in a datagram frame the L
@@ -158,6 +160,29 @@ TR_FN void tr_replay_accept(TrReplay *w, uint64_t c)
     w->seen[(c / 64) % TR_REPLAY_WORDS] |= 1ull << (c % 64);
 }
 
+/* ------------------------------------------------------------------ rekey
+   Section 12.  REKEY(k) is the first 32 bytes of ENCRYPT(k, 2^64 - 1, "", 32
+   zero bytes): key stream alone, no tag. */
+
+/* ChaChaPoly: bytes 0..31 of the block under counter 1 (counter 0 is the
+   Poly1305 key) and the 64-bit IV LE64(2^64 - 1) */
+constexpr uint32_t TR_REKEY_CHACHA_COUNTER = 1;
+constexpr uint32_t TR_REKEY_CHACHA_IV_LO = 0xffffffffu, TR_REKEY_CHACHA_IV_HI = 0xffffffffu;
+
+/* AES-GCM: the CTR blocks 2 and 3 under J0 = 0^32 || BE64(2^64 - 1) || BE32(1);
+   word w of block b (0, 1) as aes256_block takes it, big-endian */
+TR_FN uint32_t tr_rekey_aes_word(uint32_t b, uint32_t w)
+{
+    return w == 0 ? 0u : (w < 3 ? 0xffffffffu : 2u + b);
+}
+
+/* The directions a call rekeys for entry j: `directions` (bit 0 send, bit 1
+   receive) masked by the entry's byte of d_which, all of it without one. */
+TR_FN uint32_t tr_rekey_directions(uint32_t directions, const uint8_t *which, uint32_t j)
+{
+    return directions & (which ? which[j] : 3u);
+}
+
 /* --------------------------------------------------------- argument checks
    Pointers are compared as numbers and never dereferenced. */
 
@@ -208,6 +233,17 @@ inline int tr_check_clear_keys(const void *tr, uint32_t n, const void *d_slots, 
     if (!tr) return NOISE_ERROR_INVALID_PARAM;
     if (!m) return NOISE_ERROR_NONE;
     if (m > n || !d_slots) return NOISE_ERROR_INVALID_PARAM;
+    return NOISE_ERROR_NONE;
+}
+
+/* noise_aead_dev_transport_rekey (section 12) on an object of n slots; d_slots
+   and d_which may be NULL, so no pointer but tr is looked at */
+inline int tr_check_rekey(const void *tr, uint32_t n, uint32_t m, uint32_t directions)
+{
+    if (!tr) return NOISE_ERROR_INVALID_PARAM;
+    if (!m) return NOISE_ERROR_NONE;
+    if (m > n) return NOISE_ERROR_INVALID_PARAM;
+    if (directions == 0 || directions > (NOISE_AEAD_REKEY_SEND | NOISE_AEAD_REKEY_RECEIVE)) return NOISE_ERROR_INVALID_PARAM;
     return NOISE_ERROR_NONE;
 }
 

@@ -203,6 +203,8 @@ def lib() -> C.CDLL:
         "noise_aead_dev_transport_seal_datagrams": (i, [vp, vp, C.c_uint32, C.c_uint32, vp, vp, vp, vp, vp]),
         "noise_aead_dev_transport_open_datagrams": (i, [vp, vp, C.c_uint32, C.c_uint32, vp, vp, vp, vp, vp, vp]),
         "noise_aead_dev_transport_replay": (vp, [vp, P(C.c_uint32)]),
+        "noise_aead_dev_rekey": (i, [i, vp, C.c_uint32, vp, vp]),
+        "noise_aead_dev_transport_rekey": (i, [vp, vp, C.c_uint32, C.c_uint32, vp, vp]),
         "noise_aead_debug_transport_ctx": (vp, [vp, i, P(sz)]),
         "noise_strerror": (i, [i, C.c_char_p, sz]),
         "noise_perror": (None, [C.c_char_p, i]),
@@ -691,6 +693,23 @@ def dev_transport_replay(tr: int):
     """(device pointer of the n windows {uint64 top; uint64 seen[16]}, or 0; the window size in bits)"""
     bits = C.c_uint32(0)
     return lib().noise_aead_dev_transport_replay(tr, C.byref(bits)) or 0, bits.value
+
+
+# ---- rekey on the device (section 12): k = REKEY(k), nonces untouched
+
+REKEY_SEND, REKEY_RECEIVE = 1, 2
+
+
+def dev_rekey(cipher: int, *, keys: int, n: int, out: int, stream: int = 0) -> int:
+    """noise_aead_dev_rekey: the successor of each of n packed 32-byte keys, to
+    `out` (which may be `keys`)."""
+    return lib().noise_aead_dev_rekey(cipher, keys or None, n, out or None, stream or None)
+
+
+def dev_transport_rekey(tr: int, *, slots: int = 0, m: int, directions: int, which: int = 0, stream: int = 0) -> int:
+    """noise_aead_dev_transport_rekey: entry j rekeys the directions
+    `directions` & (its byte of `which`, or 3 without one) of its slot."""
+    return lib().noise_aead_dev_transport_rekey(tr, slots or None, m, directions, which or None, stream or None)
 
 
 def debug_transport_ctx(tr: int, direction: int):
