@@ -1000,6 +1000,102 @@ int noise_aead_dev_rekey(int cipher_id, const uint8_t *d_keys, uint32_t n, uint8
 int noise_aead_dev_transport_rekey(NoiseAeadDevTransport *tr, const uint32_t *d_slots /* may be NULL */, uint32_t m,
                                    uint32_t directions, const uint8_t *d_which /* may be NULL */, void *stream);
 
+/* ------------------------------------------------ 13. packet transport
+ * The datagram calls of section 11 for traffic as a socket delivers it: a
+ * receive batch (recvmmsg, a NIC ring) is a list of packets in arrival order,
+ * each with its session index, the same session many times and interleaved
+ * with others.  Section 11 wants one framed stream per entry and distinct
+ * slots, which costs a server a host sort and a gather per tick.  Here a call
+ * takes a device list of {off, len, slot} in any order with any repetition,
+ * answers with one status byte per packet, and leaves every slot's window and
+ * send counter exactly as if the packets had been processed one by one in
+ * list order.  Nothing of sections 9 to 12 changes: their bytes, results and
+ * memory footprint are what they were, and an object that never reserves is
+ * byte for byte the object it was.
+ *
+ * A packet is a section-11 frame without its 2-byte header (a UDP datagram
+ * knows its own length): the len bytes at d_wire + off are an 8-byte
+ * little-endian counter, then CT || tag; the payload is len - 24 bytes.
+ * Nothing needs alignment.  A packet may point at the body of a frame of a
+ * section-11 wire (off the body, len its L), so the same bytes can be opened
+ * by either call.  The packets' byte ranges are pairwise disjoint: the
+ * caller's guarantee, unchecked, as for the ragged calls.
+ *
+ * _reserve_packets allocates, once per object, what a packet call needs for
+ * up to max_packets packets: sort keys and the order (both double-buffered),
+ * descriptors, AEAD statuses and the sort's scratch — about 65 bytes per
+ * packet, a device allocation of its own, zeroed on `stream`; what _new
+ * allocated is not touched.  _free scrubs and frees it with the rest.  After
+ * it a packet call is asynchronous on `stream`, allocates nothing, copies
+ * nothing to the host and never synchronises.  Checked in this order:
+ *   1. a NULL tr gives NOISE_ERROR_INVALID_PARAM;
+ *   2. max_packets == 0 or above 2^31 gives NOISE_ERROR_INVALID_PARAM;
+ *   3. an object that has reserved gives NOISE_ERROR_INVALID_STATE;
+ *   4. an allocation that fails gives NOISE_ERROR_NO_MEMORY, and the object is
+ *      as it was.
+ *
+ * d_status[p] is the status of packet p; the causes are looked for in this
+ * order:
+ *   6  no session (NOISE_ERROR_INVALID_STATE's number): slot >= n, or the slot
+ *      is unkeyed;
+ *   4  len < 24 or len > 65535 (NOISE_ERROR_INVALID_LENGTH's);
+ *   5  the counter is refused.  Open: by the slot's window.  Seal: the slot's
+ *      send counter has run out, the packet would get 2^64 - 1;
+ *   1  open only: the tag failed;
+ *   0  done.
+ * Of a packet with status 6 or 4 nothing is read or written; it takes no
+ * counter, meets no window and moves no other packet's counter.  On an object
+ * with n == 0 every packet gets 6.
+ *
+ * _open_packets: the statuses and every slot's window after the call are
+ * those of processing the packets one by one in list order with the rule of
+ * section 11: the window refuses the counter -> 5; else the tag is verified
+ * under the receive key with nonce = counter, and a failed tag -> 1; else the
+ * counter is accepted -> 0, the plaintext is in place at off + 8 and the tag
+ * bytes are left as they were.  A forged packet never moves a window and is
+ * byte for byte untouched.  The receive nonce is neither read nor written.  A
+ * packet the window refuses as it stood before the call costs no AEAD work
+ * and is never touched.  The one exception to "as given" is section 11's: a
+ * status-5 packet that only an earlier packet of the same call made a replay
+ * (a duplicate at another offset, or a counter that a jump of top inside the
+ * call left behind) may hold its plaintext if its own tag verified — never
+ * anything else and never unauthenticated plaintext.
+ *
+ * _seal_packets: packet p is 8 bytes of room, len - 24 bytes of plaintext and
+ * 16 bytes of room.  Among the packets of its slot that are sealed, in list
+ * order, the k-th gets the counter send + k written in front and its body
+ * becomes CT || tag under that counter; send advances by the packets sealed.
+ * Where send + k would be 2^64 - 1, that packet and every later packet of the
+ * slot in the call get status 5 and are untouched; send stays at 2^64 - 1.
+ *
+ * Both calls share send and the windows with the calls of section 11 and with
+ * _set_keys, _clear_keys, _rekey, _replay and _nonces; calls of all kinds
+ * compose in stream order.
+ *
+ * Checked on the host before any launch, in this order:
+ *   1. a NULL tr gives NOISE_ERROR_INVALID_PARAM;
+ *   2. count == 0 gives NOISE_ERROR_NONE, and nothing is launched, reserved or
+ *      not;
+ *   3. an object that has not reserved gives NOISE_ERROR_INVALID_STATE;
+ *   4. count > max_packets gives NOISE_ERROR_INVALID_PARAM;
+ *   5. a NULL d_packets, d_wire or d_status gives NOISE_ERROR_INVALID_PARAM;
+ *   6. [d_status, + count) meeting [d_packets, + 16 count) gives
+ *      NOISE_ERROR_INVALID_PARAM.
+ * A refused call leaves the object as it was.  A call whose sort of count
+ * items would need more scratch than was reserved gives NOISE_ERROR_SYSTEM
+ * (nothing is launched). */
+typedef struct NoiseAeadPacket {
+    uint64_t off;   /* the packet's bytes start at d_wire + off; nothing needs alignment */
+    uint32_t len;   /* 8-byte little-endian counter, then CT || tag: 24 .. 65535 */
+    uint32_t slot;  /* its slot of the table; slots repeat and come in any order */
+} NoiseAeadPacket;  /* 16 bytes */
+
+int noise_aead_dev_transport_reserve_packets(NoiseAeadDevTransport *tr, uint32_t max_packets, void *stream);
+int noise_aead_dev_transport_seal_packets(NoiseAeadDevTransport *tr, const NoiseAeadPacket *d_packets, uint32_t count,
+                                          uint8_t *d_wire, uint8_t *d_status, void *stream);
+int noise_aead_dev_transport_open_packets(NoiseAeadDevTransport *tr, const NoiseAeadPacket *d_packets, uint32_t count,
+                                          uint8_t *d_wire, uint8_t *d_status, void *stream);
+
 /* ------------------------------------------------ error reports
  * include/noise/protocol/errors.h; src/protocol/errors.c:92-127. */
 void noise_perror(const char *s, int err);

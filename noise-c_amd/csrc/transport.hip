@@ -1,6 +1,6 @@
 /*
  * transport.hip — device-resident transport sessions:
- * noise_aead_dev_transport_* (include/noise_aead_hip.h sections 9 to 12).
+ * noise_aead_dev_transport_* (include/noise_aead_hip.h sections 9 to 13).
  *
  * The object holds, for n sessions, a send and a receive key context and a
  * send and a receive nonce on the device, and what a call needs: descriptors
@@ -73,6 +73,27 @@
  *   AES-GCM      gcm_rekey_keys / gcm_rekey_slots (aesgcm.hip), next to the
  *                tables: the two blocks under the context's own round keys,
  *                then the context rebuilt by gcm_prepare_one.
+ *
+ * Packet transport (section 13): the datagram calls over a device list of
+ * {off, len, slot} in arrival order, slots repeated and interleaved; one
+ * status byte per packet.  What a call needs (TrPackets) is an allocation of
+ * its own that _reserve_packets makes; descriptor p belongs to packet p, and
+ * the AEAD launch covers exactly the call's count:
+ *   tr_packet_keys    one lane per packet: its class (6, 4 or 0) to d_status,
+ *                its sort key (the slot, or n for a packet that takes no
+ *                part), order[p] = p, and its descriptor: refused_rec(), or,
+ *                for a live packet of an open, what tr_build<TR_DATAGRAM>
+ *                writes for a frame after asking the window as it stands;
+ *   the sort     rocprim's radix sort of (key, order) over the bits of n; it
+ *                is stable, so a slot's packets keep their list order;
+ *   tr_packet_seal    seal: the lane at the head of a slot's run (tr_run_walk)
+ *                hands out send, send + 1, .. in list order (tr_seal_take),
+ *                writes each counter and descriptor, gives 5 from exhaustion
+ *                on and advances send;
+ *   the AEAD     as above, over count records;
+ *   tr_packet_commit  open: the lane at the head of a run judges its packets
+ *                in list order with the window evolving (tr_replay_judge, the
+ *                rule of tr_commit_datagrams).
  */
 #include "launch.h"
 
@@ -80,6 +101,7 @@
 #include "transport_plan.h"
 
 #include <new>
+#include <rocprim/device/device_radix_sort.hpp>
 #include <rocprim/device/device_scan.hpp>
 
 using namespace na;
@@ -179,7 +201,7 @@ struct TrEmit {
     }
 };
 
-constexpr uint8_t TR_FRAME_REPLAY = 5;
+static_assert(TR_STATUS_AEAD_REFUSED == STATUS_BAD_LENGTH, "what the ragged kernels answer to refused_rec()");
 
 /* nothing of a stream is aligned */
 TR_DEV uint64_t tr_load_counter(const uint8_t *p)
@@ -299,15 +321,8 @@ struct TrDatagramJudge {
     TR_DEV void operator()(uint64_t k, uint64_t body, uint32_t) const
     {
         const uint64_t c = tr_load_counter(stream + body);
-        const uint8_t s = status[k];
-        uint8_t out = TR_FRAME_REPLAY;
-        if (s != STATUS_BAD_LENGTH && tr_replay_check(window, c)) {
-            out = s;
-            if (s == 0) {
-                tr_replay_accept(window, c);
-                ++*accepted;
-            }
-        }
+        const uint8_t out = tr_replay_judge(window, c, status[k]);
+        if (out == 0) ++*accepted;
         frame_status[k] = out;
     }
 };
@@ -327,6 +342,86 @@ __global__ __launch_bounds__(TR_BLOCK) void tr_commit_datagrams(TrArgs a)
     }
     const NoiseAeadDatagramResult r = {frames, a.consumed[j], a.stop[j], accepted, base};
     a.datagram_result[j] = r;
+}
+
+/* ---- packet transport (section 13) */
+
+struct TrPacketArgs {
+    const NoiseAeadPacket *packets; /* the caller's list of `count` */
+    uint8_t *wire;
+    uint8_t *status;             /* the caller's, one byte per packet */
+    uint32_t *keys, *order;      /* tr_packet_keys: what the sort reads; after it: what the sort left */
+    RecDesc *recs;               /* descriptor p is packet p's */
+    const uint8_t *aead_status;  /* the open's, per packet */
+    uint64_t *send;
+    TrReplay *replay;
+    const uint8_t *keyed;
+    uint64_t ctx_bytes;
+    uint32_t n, count, open;
+};
+
+__global__ __launch_bounds__(TR_BLOCK) void tr_packet_keys(TrPacketArgs a)
+{
+    const uint32_t p = blockIdx.x * TR_BLOCK + threadIdx.x;
+    if (p >= a.count) return;
+    const NoiseAeadPacket pk = a.packets[p];
+    const uint8_t cls = tr_packet_class(pk.slot, pk.len, a.n, a.keyed);
+    a.keys[p] = tr_packet_key(cls, pk.slot, a.n);
+    a.order[p] = p;
+    a.status[p] = cls;
+    RecDesc d = refused_rec(); /* a seal's live packets get theirs from tr_packet_seal */
+    if (a.open && !cls) {
+        const uint64_t c = tr_load_counter(a.wire + pk.off);
+        if (tr_replay_check(a.replay + pk.slot, c)) /* else: a replay costs no AEAD work */
+            d = tr_rec(pk.off + TR_COUNTER_LEN, c, ((uint64_t)a.n + pk.slot) * a.ctx_bytes, pk.len - TR_DATAGRAM_MIN);
+    }
+    a.recs[p] = d;
+}
+
+/* a packet of a slot's run under the seal: the next counter in front and its descriptor, or 5 */
+struct TrPacketSeal {
+    const TrPacketArgs &a;
+    uint64_t *send;              /* the lane's copy of the slot's */
+    uint64_t ctx_off;
+    TR_DEV void operator()(uint32_t p) const
+    {
+        uint64_t c;
+        if (!tr_seal_take(send, &c)) {
+            a.status[p] = TR_STATUS_REPLAY;
+            return;
+        }
+        const NoiseAeadPacket pk = a.packets[p];
+        for (int b = 0; b < 8; ++b) a.wire[pk.off + b] = (uint8_t)(c >> (8 * b));
+        a.recs[p] = tr_rec(pk.off + TR_COUNTER_LEN, c, ctx_off, pk.len - TR_DATAGRAM_MIN);
+    }
+};
+
+__global__ __launch_bounds__(TR_BLOCK) void tr_packet_seal(TrPacketArgs a)
+{
+    const uint32_t q = blockIdx.x * TR_BLOCK + threadIdx.x;
+    if (q >= a.count || !tr_run_head(a.keys, q, a.n)) return;
+    const uint32_t i = a.keys[q];
+    uint64_t send = a.send[i];
+    tr_run_walk(a.keys, a.order, a.count, q, TrPacketSeal{a, &send, (uint64_t)i * a.ctx_bytes});
+    a.send[i] = send;
+}
+
+/* a packet of a slot's run under the open, against the window as the packets before it left it */
+struct TrPacketJudge {
+    const TrPacketArgs &a;
+    TrReplay *window;
+    TR_DEV void operator()(uint32_t p) const
+    {
+        /* the counter is the descriptor's nonce; a refused descriptor has none, and needs none */
+        a.status[p] = tr_replay_judge(window, a.recs[p].nonce, a.aead_status[p]);
+    }
+};
+
+__global__ __launch_bounds__(TR_BLOCK) void tr_packet_commit(TrPacketArgs a)
+{
+    const uint32_t q = blockIdx.x * TR_BLOCK + threadIdx.x;
+    if (q >= a.count || !tr_run_head(a.keys, q, a.n)) return;
+    tr_run_walk(a.keys, a.order, a.count, q, TrPacketJudge{a, a.replay + a.keys[q]});
 }
 
 /* ---- keying and un-keying slots (section 10) */
@@ -468,6 +563,18 @@ __global__ __launch_bounds__(TR_BLOCK) void tr_rekey_slots(TrRekeyArgs a)
 
 } // namespace
 
+/* What the packet calls need for up to max_packets packets (section 13): a
+   device allocation of its own beside the object's, made by _reserve_packets. */
+struct TrPackets {
+    DevArena dev;
+    uint32_t max_packets;     /* 0: not reserved */
+    uint32_t *keys[2], *order[2]; /* the sort's two buffers of each; a call starts in [0] */
+    RecDesc *recs;
+    uint8_t *status;          /* the AEAD's */
+    void *sort_tmp;
+    size_t sort_bytes;
+};
+
 struct NoiseAeadDevTransport {
     int cipher_id, role;
     uint32_t n, max_frames;
@@ -483,6 +590,7 @@ struct NoiseAeadDevTransport {
     TrReplay *replay;         /* per slot: the datagram calls' anti-replay window */
     void *scan_tmp;
     size_t scan_bytes;
+    TrPackets packets;        /* what _reserve_packets made; all zero until then */
 };
 
 namespace {
@@ -580,6 +688,55 @@ int run_datagrams(Tr *tr, TrMode mode, const uint32_t *d_slots, uint32_t m, uint
     if (rc || !m) return rc;
     return run(tr, TR_DATAGRAM, mode, d_slots, m, max_frames, d_wire, d_off, d_len, d_result, d_datagram_result,
                d_frame_status, stream);
+}
+
+/* The stable sort of the first `count` (key, order) pairs over the low `bits`
+   bits of the keys, from the buffers [0]; *keys and *order: where it leaves
+   them.  tmp == nullptr asks for the size only, and nothing is launched. */
+int sort_packets(const TrPackets &pk, void *tmp, size_t &bytes, uint32_t count, uint32_t bits, uint32_t **keys,
+                 uint32_t **order, hipStream_t s)
+{
+    rocprim::double_buffer<uint32_t> k(pk.keys[0], pk.keys[1]), o(pk.order[0], pk.order[1]);
+    const int rc = hip_rc(rocprim::radix_sort_pairs(tmp, bytes, k, o, (size_t)count, 0u, bits, s));
+    *keys = k.current();
+    *order = o.current();
+    return rc;
+}
+
+/* The calls of section 13: the packets of the list, one status byte each. */
+int run_packets(Tr *tr, bool open, const NoiseAeadPacket *d_packets, uint32_t count, uint8_t *d_wire, uint8_t *d_status,
+                void *stream)
+{
+    int rc = tr_check_packets(tr, tr ? tr->packets.max_packets : 0, d_packets, count, d_wire, d_status);
+    if (rc || !count) return rc;
+    hipStream_t s = (hipStream_t)stream;
+    const TrPackets &pk = tr->packets;
+    const uint32_t bits = tr_packet_key_bits(tr->n);
+    TrPacketArgs a = {};
+    size_t need = 0, bytes = pk.sort_bytes;
+    rc = sort_packets(pk, nullptr, need, count, bits, &a.keys, &a.order, s); /* the size question: nothing is launched */
+    if (rc) return rc;
+    if (need > pk.sort_bytes) return NOISE_ERROR_SYSTEM;
+    a.packets = d_packets; a.wire = d_wire; a.status = d_status;
+    a.keys = pk.keys[0]; a.order = pk.order[0]; /* tr_packet_keys fills what the sort reads */
+    a.recs = pk.recs; a.aead_status = pk.status;
+    a.send = tr->send; a.replay = tr->replay; a.keyed = tr->keyed;
+    a.ctx_bytes = tr->ctx_bytes;
+    a.n = tr->n; a.count = count; a.open = open;
+    rc = launch_items(tr_packet_keys, count, TR_BLOCK, s, a);
+    if (!rc) rc = sort_packets(pk, pk.sort_tmp, bytes, count, bits, &a.keys, &a.order, s);
+    if (!rc && !open) rc = launch_items(tr_packet_seal, count, TR_BLOCK, s, a);
+    if (rc) return rc;
+    NoiseAeadRagged job = {};
+    job.ctx_base = tr->ctx;
+    job.recs = (const NoiseAeadRecord *)pk.recs;
+    job.in = job.out = d_wire;
+    job.ad = d_wire; /* never read: every ad_len is 0 */
+    job.status = pk.status;
+    job.n_records = count;
+    if (!open) return noise_aead_dev_seal_ragged(tr->cipher_id, &job, s);
+    rc = noise_aead_dev_open_ragged(tr->cipher_id, &job, s);
+    return rc ? rc : launch_items(tr_packet_commit, count, TR_BLOCK, s, a);
 }
 
 /* The object and its one device allocation, zeroed on s: every slot unkeyed,
@@ -751,10 +908,57 @@ const uint8_t *noise_aead_debug_transport_ctx(const NoiseAeadDevTransport *tr, i
 int noise_aead_dev_transport_free(NoiseAeadDevTransport *tr)
 {
     if (!tr) return NOISE_ERROR_INVALID_PARAM;
-    const int rc = tr->dev.release();
+    const int rc = tr->dev.release(), rc2 = tr->packets.dev.release();
     memset((void *)tr, 0, sizeof(*tr));
     delete tr;
-    return rc;
+    return rc ? rc : rc2;
+}
+
+int noise_aead_dev_transport_reserve_packets(NoiseAeadDevTransport *tr, uint32_t max_packets, void *stream)
+{
+    int rc = tr_check_reserve_packets(tr, max_packets, tr ? tr->packets.max_packets : 0);
+    if (rc) return rc;
+    hipStream_t s = (hipStream_t)stream;
+    TrPackets pk = {};
+    pk.max_packets = max_packets;
+    /* the sort picks its algorithm by the count, and its scratch is not monotone in it: ask for every power
+       of two up to max_packets and for max_packets itself, keep the most; a call still asks for its own count */
+    for (uint64_t count = 1; count / 2 < max_packets; count *= 2) {
+        uint32_t *unused;
+        size_t need = 0;
+        rc = sort_packets(pk, nullptr, need, count < max_packets ? (uint32_t)count : max_packets, tr_packet_key_bits(tr->n),
+                          &unused, &unused, s);
+        if (rc) return rc;
+        if (need > pk.sort_bytes) pk.sort_bytes = need;
+    }
+    const size_t np = max_packets;
+    DevArena &d = pk.dev;
+    d.align = TR_ALIGN;
+    const size_t o_keys0 = d.carve(np * 4), o_keys1 = d.carve(np * 4), o_order0 = d.carve(np * 4), o_order1 = d.carve(np * 4);
+    const size_t o_recs = d.carve(np * sizeof(RecDesc)), o_status = d.carve(np), o_sort = d.carve(pk.sort_bytes);
+    if (!d.alloc()) return NOISE_ERROR_NO_MEMORY;
+    pk.keys[0] = d.at<uint32_t>(o_keys0); pk.keys[1] = d.at<uint32_t>(o_keys1);
+    pk.order[0] = d.at<uint32_t>(o_order0); pk.order[1] = d.at<uint32_t>(o_order1);
+    pk.recs = d.at<RecDesc>(o_recs); pk.status = d.at(o_status); pk.sort_tmp = d.at(o_sort);
+    rc = d.zero(s);
+    if (rc) {
+        d.release();
+        return rc;
+    }
+    tr->packets = pk;
+    return NOISE_ERROR_NONE;
+}
+
+int noise_aead_dev_transport_seal_packets(NoiseAeadDevTransport *tr, const NoiseAeadPacket *d_packets, uint32_t count,
+                                          uint8_t *d_wire, uint8_t *d_status, void *stream)
+{
+    return run_packets(tr, false, d_packets, count, d_wire, d_status, stream);
+}
+
+int noise_aead_dev_transport_open_packets(NoiseAeadDevTransport *tr, const NoiseAeadPacket *d_packets, uint32_t count,
+                                          uint8_t *d_wire, uint8_t *d_status, void *stream)
+{
+    return run_packets(tr, true, d_packets, count, d_wire, d_status, stream);
 }
 
 uint64_t *noise_aead_dev_transport_nonces(const NoiseAeadDevTransport *tr, int direction)

@@ -4,12 +4,15 @@
  * the frame walk of one session, the cap rule across sessions, the slot of a
  * call's entry (section 10, the session table), the anti-replay window of the
  * datagram calls (section 11), the counter blocks and the direction rule of
- * rekey (section 12), and the argument checks.  One source for both compilers, as fe25519.h is: hipcc's
+ * rekey (section 12), the classification, the sort key, the run walk and the
+ * judging rule of the packet calls (section 13), and the argument checks.  One
+ * source for both compilers, as fe25519.h is: hipcc's
  * device pass builds the kernels of transport.hip from tr_walk and tr_cap,
  * plain g++ builds asan/transport_check.cpp, asan/transport_table_check.cpp,
- * asan/transport_datagram_check.cpp and asan/transport_rekey_check.cpp from
- * them, so the CPU check under ASan/UBSan runs the walk, the window rule and
- * the direction rule the GPU runs.
+ * asan/transport_datagram_check.cpp, asan/transport_rekey_check.cpp and
+ * asan/transport_packet_check.cpp from
+ * them, so the CPU check under ASan/UBSan runs the walk, the window rule, the
+ * direction rule and the run walk the GPU runs.
  *
  * The wire format is that of csrc/wire.c (echo-common.c:643-688): a 2-byte
  * big-endian length L, then L bytes of CT || tag; in a datagram frame the L
@@ -183,6 +186,84 @@ TR_FN uint32_t tr_rekey_directions(uint32_t directions, const uint8_t *which, ui
     return directions & (which ? which[j] : 3u);
 }
 
+/* ------------------------------------------------------ packet transport
+   Section 13.  A call's packets come in list order with their slots repeated
+   and interleaved.  Each packet gets a sort key, a stable sort of (key,
+   position in the list) brings every slot's packets together with their list
+   order kept, and one lane walks a slot's run. */
+
+constexpr uint8_t TR_STATUS_AEAD_REFUSED = 2;  /* the ragged kernels' answer to refused_rec(): nothing was done */
+constexpr uint8_t TR_STATUS_LENGTH = 4;
+constexpr uint8_t TR_STATUS_REPLAY = 5;
+constexpr uint8_t TR_STATUS_NO_SESSION = 6;
+constexpr uint32_t TR_PACKET_MAX_LEN = 65535;
+constexpr uint32_t TR_MAX_PACKETS = 1u << 31;  /* the most packets an object may reserve for */
+
+/* What keeps a packet out of the call, in the order of the header: 6 (no such
+   slot, or unkeyed), 4 (its length), else 0.  Reads only keyed[slot], and that
+   only for a slot of the table. */
+TR_FN uint8_t tr_packet_class(uint32_t slot, uint32_t len, uint32_t n, const uint8_t *keyed)
+{
+    if (slot >= n || !keyed[slot]) return TR_STATUS_NO_SESSION;
+    if (len < TR_DATAGRAM_MIN || len > TR_PACKET_MAX_LEN) return TR_STATUS_LENGTH;
+    return 0;
+}
+
+/* The sort key: the slot, or n, the sentinel of a packet that takes no part;
+   the sentinels sort behind every slot's run. */
+TR_FN uint32_t tr_packet_key(uint8_t cls, uint32_t slot, uint32_t n)
+{
+    return cls ? n : slot;
+}
+
+/* the bits of a key: the fewest that hold n, and at least one */
+TR_FN uint32_t tr_packet_key_bits(uint32_t n)
+{
+    uint32_t bits = 1;
+    while (bits < 32 && (n >> bits)) ++bits;
+    return bits;
+}
+
+/* whether sorted position q is the first of a slot's run */
+TR_FN bool tr_run_head(const uint32_t *keys, uint32_t q, uint32_t n)
+{
+    return keys[q] != n && (q == 0 || keys[q - 1] != keys[q]);
+}
+
+/* The run that starts at sorted position q, in list order (the sort is
+   stable): visit(p) for each of its packets, p the packet's place in the
+   list.  Reads keys[q .. end of the run], one key past it when there is one,
+   and as much of order. */
+template <class Visit>
+TR_FN void tr_run_walk(const uint32_t *keys, const uint32_t *order, uint32_t count, uint32_t q, Visit visit)
+{
+    const uint32_t slot = keys[q];
+    for (; q < count && keys[q] == slot; ++q) visit(order[q]);
+}
+
+/* The open's rule for one packet, frame or counter c against the window as
+   the ones before it left it; s is the AEAD's status of it (2: the window as
+   it stood before the call refused it, nothing was opened).  Refused before or
+   by now -> 5; the tag failed -> 1; else c is accepted -> 0.  Refusal is
+   monotone over a call: what the window refused before the call
+   it refuses at every later point of it, so judging the pre-checked packets
+   in order gives what one-by-one processing gives. */
+TR_FN uint8_t tr_replay_judge(TrReplay *w, uint64_t c, uint8_t s)
+{
+    if (s == TR_STATUS_AEAD_REFUSED || !tr_replay_check(w, c)) return TR_STATUS_REPLAY;
+    if (s == 0) tr_replay_accept(w, c);
+    return s;
+}
+
+/* The seal's counter for the next sealed packet of a slot: *c = send, and send
+   moves on; false, and nothing moves, where that counter would be 2^64 - 1. */
+TR_FN bool tr_seal_take(uint64_t *send, uint64_t *c)
+{
+    if (*send == TR_NONCE_LIMIT) return false;
+    *c = (*send)++;
+    return true;
+}
+
 /* --------------------------------------------------------- argument checks
    Pointers are compared as numbers and never dereferenced. */
 
@@ -305,6 +386,32 @@ inline int tr_check_datagrams(const void *tr, uint32_t n, uint32_t object_max_fr
 {
     return tr_check_frames(TR_FORM_DATAGRAM, tr, n, object_max_frames, d_slots, m, max_frames, d_wire, d_off, d_len,
                            d_result, result_bytes, open, d_frame_status);
+}
+
+/* ---- the packet calls of section 13, in the order of the header.
+   reserved_packets: what the object has reserved for, 0 when it has not. */
+
+/* noise_aead_dev_transport_reserve_packets; the allocation comes after it */
+inline int tr_check_reserve_packets(const void *tr, uint32_t max_packets, uint32_t reserved_packets)
+{
+    if (!tr) return NOISE_ERROR_INVALID_PARAM;
+    if (max_packets == 0 || max_packets > TR_MAX_PACKETS) return NOISE_ERROR_INVALID_PARAM;
+    if (reserved_packets) return NOISE_ERROR_INVALID_STATE;
+    return NOISE_ERROR_NONE;
+}
+
+/* noise_aead_dev_transport_{seal,open}_packets; NOISE_ERROR_NONE with
+   count == 0 means: nothing to launch */
+inline int tr_check_packets(const void *tr, uint32_t reserved_packets, const void *d_packets, uint32_t count,
+                            const void *d_wire, const void *d_status)
+{
+    if (!tr) return NOISE_ERROR_INVALID_PARAM;
+    if (!count) return NOISE_ERROR_NONE;
+    if (!reserved_packets) return NOISE_ERROR_INVALID_STATE;
+    if (count > reserved_packets) return NOISE_ERROR_INVALID_PARAM;
+    if (!d_packets || !d_wire || !d_status) return NOISE_ERROR_INVALID_PARAM;
+    if (tr_ranges_meet(d_status, count, d_packets, (tr_u128)sizeof(NoiseAeadPacket) * count)) return NOISE_ERROR_INVALID_PARAM;
+    return NOISE_ERROR_NONE;
 }
 
 } // namespace na

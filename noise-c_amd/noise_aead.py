@@ -107,6 +107,13 @@ class NoiseAeadTransportResult(C.Structure):
                 ("reserved_", C.c_uint32)]
 
 
+class NoiseAeadPacket(C.Structure):
+    _fields_ = [("off", C.c_uint64), ("len", C.c_uint32), ("slot", C.c_uint32)]
+
+
+# NoiseAeadPacket as a numpy dtype
+PACKET_DT = [("off", "<u8"), ("len", "<u4"), ("slot", "<u4")]
+
 FLAG_FAST = 1
 FLAG_CT_GHASH = 2
 FLAG_VERIFY_FIRST = 4  # the default open order since round 6 (accepted, overrides ONE_PASS)
@@ -205,6 +212,9 @@ def lib() -> C.CDLL:
         "noise_aead_dev_transport_replay": (vp, [vp, P(C.c_uint32)]),
         "noise_aead_dev_rekey": (i, [i, vp, C.c_uint32, vp, vp]),
         "noise_aead_dev_transport_rekey": (i, [vp, vp, C.c_uint32, C.c_uint32, vp, vp]),
+        "noise_aead_dev_transport_reserve_packets": (i, [vp, C.c_uint32, vp]),
+        "noise_aead_dev_transport_seal_packets": (i, [vp, vp, C.c_uint32, vp, vp, vp]),
+        "noise_aead_dev_transport_open_packets": (i, [vp, vp, C.c_uint32, vp, vp, vp]),
         "noise_aead_debug_transport_ctx": (vp, [vp, i, P(sz)]),
         "noise_strerror": (i, [i, C.c_char_p, sz]),
         "noise_perror": (None, [C.c_char_p, i]),
@@ -710,6 +720,27 @@ def dev_transport_rekey(tr: int, *, slots: int = 0, m: int, directions: int, whi
     """noise_aead_dev_transport_rekey: entry j rekeys the directions
     `directions` & (its byte of `which`, or 3 without one) of its slot."""
     return lib().noise_aead_dev_transport_rekey(tr, slots or None, m, directions, which or None, stream or None)
+
+
+# ---- packet transport (section 13): a device list of count NoiseAeadPacket
+# {off, len, slot} in arrival order, slots repeated; one status byte per packet
+# (0 done, 1 the tag failed, 4 the length, 5 the counter refused, 6 no session)
+
+PACKET_OK, PACKET_FORGED, PACKET_LENGTH, PACKET_REPLAY, PACKET_NO_SESSION = 0, 1, 4, 5, 6
+
+
+def dev_transport_reserve_packets(tr: int, max_packets: int, stream: int = 0) -> int:
+    return lib().noise_aead_dev_transport_reserve_packets(tr, max_packets, stream or None)
+
+
+def dev_transport_seal_packets(tr: int, *, packets: int, count: int, wire: int, status: int, stream: int = 0) -> int:
+    return lib().noise_aead_dev_transport_seal_packets(tr, packets or None, count, wire or None, status or None,
+                                                       stream or None)
+
+
+def dev_transport_open_packets(tr: int, *, packets: int, count: int, wire: int, status: int, stream: int = 0) -> int:
+    return lib().noise_aead_dev_transport_open_packets(tr, packets or None, count, wire or None, status or None,
+                                                       stream or None)
 
 
 def debug_transport_ctx(tr: int, direction: int):
