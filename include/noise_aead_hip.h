@@ -1096,6 +1096,68 @@ int noise_aead_dev_transport_seal_packets(NoiseAeadDevTransport *tr, const Noise
 int noise_aead_dev_transport_open_packets(NoiseAeadDevTransport *tr, const NoiseAeadPacket *d_packets, uint32_t count,
                                           uint8_t *d_wire, uint8_t *d_status, void *stream);
 
+/* ------------------------------------------------ 14. packet echo
+ * The third verb of the packet calls, as _echo_frames is of the stream calls:
+ * the reference echo server's tick (echo-server.c: read, decrypt, encrypt,
+ * write) over a receive batch of section 13.  A UDP server that answers what
+ * it accepts otherwise calls _open_packets, needs the list of the accepted
+ * packets (a read of d_status on the host in the middle of its tick, or a
+ * kernel of its own), and calls _seal_packets, which classifies and sorts
+ * again.  Here one call opens the list and seals the replies in place, so that
+ * handshake -> _set_keys -> echo ticks runs with the host reading nothing.
+ *
+ * Definition.  The bytes, the statuses, every slot's window and every slot's
+ * send counter after the call are those of two calls in sequence:
+ *   1. _open_packets over the list;
+ *   2. _seal_packets over the sub-list of the packets that step 1 gave status
+ *      0, in list order, on the same bytes.
+ * d_status[p] is the open's status if that is not 0, else the seal's.  The
+ * causes are therefore looked for in section 13's order:
+ *   6  no session;
+ *   4  len < 24 or len > 65535;
+ *   5  refused by the slot's window;
+ *   1  the tag failed;
+ *   5  the slot's send counter has run out;
+ *   0  echoed.
+ * A packet echoed with status 0 keeps its len and its place: the 8 bytes in
+ * front hold the send counter it got, send + k for the k-th echoed packet of
+ * its slot in list order; the len - 24 bytes behind them are its payload
+ * sealed under the slot's send key and that counter, and the tag follows.  The
+ * counter it arrived with is gone.  Of a packet with status 6 or 4 nothing is
+ * read or written.  A packet with status 1 is byte for byte untouched.  A
+ * packet the window refuses is never read or written, with section 11's one
+ * exception: a packet that only an earlier packet of the same call made a
+ * replay may hold its plaintext.  None of these takes a send counter, and none
+ * moves another packet's.
+ *
+ * Where send + k would be 2^64 - 1, that packet and every later accepted
+ * packet of the slot in the call get status 5.  They were opened: the window
+ * has accepted their counters, and their bytes are what _open_packets leaves
+ * for an accepted packet — the received counter, the plaintext, the tag bytes
+ * as they were.  send stays at 2^64 - 1.
+ *
+ * The receive nonce is neither read nor written.  The call shares send and the
+ * windows with the calls of sections 11 to 13 and with _set_keys, _clear_keys,
+ * _rekey, _replay and _nonces, and composes with them in stream order.  It
+ * uses the reservation of _reserve_packets and nothing more: the reservation
+ * does not grow, and the object's footprint is what it was.  The call is
+ * asynchronous on `stream`, allocates nothing, copies nothing to the host and
+ * never synchronises.  Nothing of sections 9 to 13 changes in bytes, results
+ * or footprint.
+ *
+ * A packet may point at the body of a frame of a section-11 wire, as in
+ * section 13, so framed datagrams are served by this call too; there is no
+ * framed form of it (a framed reply stream with holes where packets were
+ * refused has no counterpart on the sender's side).
+ *
+ * Checked on the host before any launch: the six checks of section 13's
+ * calls, in that order.  A refused call leaves the object as it was;
+ * count == 0 gives NOISE_ERROR_NONE, reserved or not.  A call whose sort would
+ * need more scratch than was reserved gives NOISE_ERROR_SYSTEM (nothing is
+ * launched). */
+int noise_aead_dev_transport_echo_packets(NoiseAeadDevTransport *tr, const NoiseAeadPacket *d_packets, uint32_t count,
+                                          uint8_t *d_wire, uint8_t *d_status, void *stream);
+
 /* ------------------------------------------------ error reports
  * include/noise/protocol/errors.h; src/protocol/errors.c:92-127. */
 void noise_perror(const char *s, int err);

@@ -1,6 +1,6 @@
 /*
  * transport.hip — device-resident transport sessions:
- * noise_aead_dev_transport_* (include/noise_aead_hip.h sections 9 to 13).
+ * noise_aead_dev_transport_* (include/noise_aead_hip.h sections 9 to 14).
  *
  * The object holds, for n sessions, a send and a receive key context and a
  * send and a receive nonce on the device, and what a call needs: descriptors
@@ -94,6 +94,17 @@
  *   tr_packet_commit  open: the lane at the head of a run judges its packets
  *                in list order with the window evolving (tr_replay_judge, the
  *                rule of tr_commit_datagrams).
+ *
+ * Packet echo (section 14): an open of the list and the seal of what it
+ * accepted, in place, in one call: tr_packet_keys as for the open, the sort,
+ * the AEAD's open over count records, then
+ *   tr_packet_echo    in tr_packet_commit's place: the lane at the head of a
+ *                run reads the slot's send once and walks the run once
+ *                (tr_echo_judge): each packet against the evolving window, and
+ *                an accepted one takes the next send counter, gets it written
+ *                in front and its descriptor rewritten in place as the seal's;
+ *                every other packet of the run gets refused_rec();
+ *   the AEAD     the seal over the same count descriptors, no statuses.
  */
 #include "launch.h"
 
@@ -357,7 +368,7 @@ struct TrPacketArgs {
     TrReplay *replay;
     const uint8_t *keyed;
     uint64_t ctx_bytes;
-    uint32_t n, count, open;
+    uint32_t n, count, mode;     /* TR_SEAL, TR_OPEN or TR_ECHO */
 };
 
 __global__ __launch_bounds__(TR_BLOCK) void tr_packet_keys(TrPacketArgs a)
@@ -370,7 +381,7 @@ __global__ __launch_bounds__(TR_BLOCK) void tr_packet_keys(TrPacketArgs a)
     a.order[p] = p;
     a.status[p] = cls;
     RecDesc d = refused_rec(); /* a seal's live packets get theirs from tr_packet_seal */
-    if (a.open && !cls) {
+    if (a.mode != TR_SEAL && !cls) {
         const uint64_t c = tr_load_counter(a.wire + pk.off);
         if (tr_replay_check(a.replay + pk.slot, c)) /* else: a replay costs no AEAD work */
             d = tr_rec(pk.off + TR_COUNTER_LEN, c, ((uint64_t)a.n + pk.slot) * a.ctx_bytes, pk.len - TR_DATAGRAM_MIN);
@@ -422,6 +433,39 @@ __global__ __launch_bounds__(TR_BLOCK) void tr_packet_commit(TrPacketArgs a)
     const uint32_t q = blockIdx.x * TR_BLOCK + threadIdx.x;
     if (q >= a.count || !tr_run_head(a.keys, q, a.n)) return;
     tr_run_walk(a.keys, a.order, a.count, q, TrPacketJudge{a, a.replay + a.keys[q]});
+}
+
+/* a packet of a slot's run under the echo: judged as the open judges it, and an accepted one is made the
+   seal's: the next send counter in front, its descriptor under that counter and the send context */
+struct TrPacketEcho {
+    const TrPacketArgs &a;
+    TrReplay *window;
+    uint64_t *send;              /* the lane's copy of the slot's */
+    uint64_t ctx_off;
+    TR_DEV void operator()(uint32_t p) const
+    {
+        uint64_t c;
+        const uint8_t out = tr_echo_judge(window, send, a.recs[p].nonce, a.aead_status[p], &c);
+        a.status[p] = out;
+        /* a failed tag's descriptor is still the open's, live: nothing but an echoed packet may stay sealable */
+        RecDesc d = refused_rec();
+        if (!out) {
+            const NoiseAeadPacket pk = a.packets[p];
+            for (int b = 0; b < 8; ++b) a.wire[pk.off + b] = (uint8_t)(c >> (8 * b));
+            d = tr_rec(pk.off + TR_COUNTER_LEN, c, ctx_off, pk.len - TR_DATAGRAM_MIN);
+        }
+        a.recs[p] = d;
+    }
+};
+
+__global__ __launch_bounds__(TR_BLOCK) void tr_packet_echo(TrPacketArgs a)
+{
+    const uint32_t q = blockIdx.x * TR_BLOCK + threadIdx.x;
+    if (q >= a.count || !tr_run_head(a.keys, q, a.n)) return;
+    const uint32_t i = a.keys[q];
+    uint64_t send = a.send[i];
+    tr_run_walk(a.keys, a.order, a.count, q, TrPacketEcho{a, a.replay + i, &send, (uint64_t)i * a.ctx_bytes});
+    a.send[i] = send;
 }
 
 /* ---- keying and un-keying slots (section 10) */
@@ -703,8 +747,10 @@ int sort_packets(const TrPackets &pk, void *tmp, size_t &bytes, uint32_t count, 
     return rc;
 }
 
-/* The calls of section 13: the packets of the list, one status byte each. */
-int run_packets(Tr *tr, bool open, const NoiseAeadPacket *d_packets, uint32_t count, uint8_t *d_wire, uint8_t *d_status,
+/* The calls of sections 13 and 14: the packets of the list, one status byte
+   each.  TR_ECHO is the open with tr_packet_echo in the commit's place, then
+   the seal over the same descriptors. */
+int run_packets(Tr *tr, TrMode mode, const NoiseAeadPacket *d_packets, uint32_t count, uint8_t *d_wire, uint8_t *d_status,
                 void *stream)
 {
     int rc = tr_check_packets(tr, tr ? tr->packets.max_packets : 0, d_packets, count, d_wire, d_status);
@@ -722,10 +768,10 @@ int run_packets(Tr *tr, bool open, const NoiseAeadPacket *d_packets, uint32_t co
     a.recs = pk.recs; a.aead_status = pk.status;
     a.send = tr->send; a.replay = tr->replay; a.keyed = tr->keyed;
     a.ctx_bytes = tr->ctx_bytes;
-    a.n = tr->n; a.count = count; a.open = open;
+    a.n = tr->n; a.count = count; a.mode = mode;
     rc = launch_items(tr_packet_keys, count, TR_BLOCK, s, a);
     if (!rc) rc = sort_packets(pk, pk.sort_tmp, bytes, count, bits, &a.keys, &a.order, s);
-    if (!rc && !open) rc = launch_items(tr_packet_seal, count, TR_BLOCK, s, a);
+    if (!rc && mode == TR_SEAL) rc = launch_items(tr_packet_seal, count, TR_BLOCK, s, a);
     if (rc) return rc;
     NoiseAeadRagged job = {};
     job.ctx_base = tr->ctx;
@@ -734,9 +780,12 @@ int run_packets(Tr *tr, bool open, const NoiseAeadPacket *d_packets, uint32_t co
     job.ad = d_wire; /* never read: every ad_len is 0 */
     job.status = pk.status;
     job.n_records = count;
-    if (!open) return noise_aead_dev_seal_ragged(tr->cipher_id, &job, s);
+    if (mode == TR_SEAL) return noise_aead_dev_seal_ragged(tr->cipher_id, &job, s);
     rc = noise_aead_dev_open_ragged(tr->cipher_id, &job, s);
-    return rc ? rc : launch_items(tr_packet_commit, count, TR_BLOCK, s, a);
+    if (!rc) rc = launch_items(mode == TR_ECHO ? tr_packet_echo : tr_packet_commit, count, TR_BLOCK, s, a);
+    if (rc || mode == TR_OPEN) return rc;
+    job.status = nullptr; /* tr_packet_echo has written the caller's statuses */
+    return noise_aead_dev_seal_ragged(tr->cipher_id, &job, s);
 }
 
 /* The object and its one device allocation, zeroed on s: every slot unkeyed,
@@ -952,13 +1001,19 @@ int noise_aead_dev_transport_reserve_packets(NoiseAeadDevTransport *tr, uint32_t
 int noise_aead_dev_transport_seal_packets(NoiseAeadDevTransport *tr, const NoiseAeadPacket *d_packets, uint32_t count,
                                           uint8_t *d_wire, uint8_t *d_status, void *stream)
 {
-    return run_packets(tr, false, d_packets, count, d_wire, d_status, stream);
+    return run_packets(tr, TR_SEAL, d_packets, count, d_wire, d_status, stream);
 }
 
 int noise_aead_dev_transport_open_packets(NoiseAeadDevTransport *tr, const NoiseAeadPacket *d_packets, uint32_t count,
                                           uint8_t *d_wire, uint8_t *d_status, void *stream)
 {
-    return run_packets(tr, true, d_packets, count, d_wire, d_status, stream);
+    return run_packets(tr, TR_OPEN, d_packets, count, d_wire, d_status, stream);
+}
+
+int noise_aead_dev_transport_echo_packets(NoiseAeadDevTransport *tr, const NoiseAeadPacket *d_packets, uint32_t count,
+                                          uint8_t *d_wire, uint8_t *d_status, void *stream)
+{
+    return run_packets(tr, TR_ECHO, d_packets, count, d_wire, d_status, stream);
 }
 
 uint64_t *noise_aead_dev_transport_nonces(const NoiseAeadDevTransport *tr, int direction)

@@ -5,12 +5,13 @@
  * call's entry (section 10, the session table), the anti-replay window of the
  * datagram calls (section 11), the counter blocks and the direction rule of
  * rekey (section 12), the classification, the sort key, the run walk and the
- * judging rule of the packet calls (section 13), and the argument checks.  One
+ * judging rule of the packet calls (section 13), the packet echo's rule for one
+ * packet (section 14), and the argument checks.  One
  * source for both compilers, as fe25519.h is: hipcc's
  * device pass builds the kernels of transport.hip from tr_walk and tr_cap,
  * plain g++ builds asan/transport_check.cpp, asan/transport_table_check.cpp,
- * asan/transport_datagram_check.cpp, asan/transport_rekey_check.cpp and
- * asan/transport_packet_check.cpp from
+ * asan/transport_datagram_check.cpp, asan/transport_rekey_check.cpp,
+ * asan/transport_packet_check.cpp and asan/transport_packet_echo_check.cpp from
  * them, so the CPU check under ASan/UBSan runs the walk, the window rule, the
  * direction rule and the run walk the GPU runs.
  *
@@ -264,6 +265,20 @@ TR_FN bool tr_seal_take(uint64_t *send, uint64_t *c)
     return true;
 }
 
+/* The echo's rule for one packet (section 14): the open's, then the seal's
+   for what the open accepted.  w is the slot's window and *send the lane's
+   copy of its send counter, both as the packets before this one left them; c
+   is the counter the packet came with and s the AEAD's status of its open.
+   What tr_replay_judge refuses keeps that status and takes no counter.  An
+   accepted packet has moved the window; it then takes the next send counter
+   into *taken -> 0, or finds it run out -> 5, with the window still moved. */
+TR_FN uint8_t tr_echo_judge(TrReplay *w, uint64_t *send, uint64_t c, uint8_t s, uint64_t *taken)
+{
+    const uint8_t opened = tr_replay_judge(w, c, s);
+    if (opened) return opened;
+    return tr_seal_take(send, taken) ? 0 : TR_STATUS_REPLAY;
+}
+
 /* --------------------------------------------------------- argument checks
    Pointers are compared as numbers and never dereferenced. */
 
@@ -400,8 +415,8 @@ inline int tr_check_reserve_packets(const void *tr, uint32_t max_packets, uint32
     return NOISE_ERROR_NONE;
 }
 
-/* noise_aead_dev_transport_{seal,open}_packets; NOISE_ERROR_NONE with
-   count == 0 means: nothing to launch */
+/* noise_aead_dev_transport_{seal,open}_packets and _echo_packets (section 14);
+   NOISE_ERROR_NONE with count == 0 means: nothing to launch */
 inline int tr_check_packets(const void *tr, uint32_t reserved_packets, const void *d_packets, uint32_t count,
                             const void *d_wire, const void *d_status)
 {

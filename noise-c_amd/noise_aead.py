@@ -215,6 +215,7 @@ def lib() -> C.CDLL:
         "noise_aead_dev_transport_reserve_packets": (i, [vp, C.c_uint32, vp]),
         "noise_aead_dev_transport_seal_packets": (i, [vp, vp, C.c_uint32, vp, vp, vp]),
         "noise_aead_dev_transport_open_packets": (i, [vp, vp, C.c_uint32, vp, vp, vp]),
+        "noise_aead_dev_transport_echo_packets": (i, [vp, vp, C.c_uint32, vp, vp, vp]),
         "noise_aead_debug_transport_ctx": (vp, [vp, i, P(sz)]),
         "noise_strerror": (i, [i, C.c_char_p, sz]),
         "noise_perror": (None, [C.c_char_p, i]),
@@ -740,6 +741,12 @@ def dev_transport_seal_packets(tr: int, *, packets: int, count: int, wire: int, 
 
 def dev_transport_open_packets(tr: int, *, packets: int, count: int, wire: int, status: int, stream: int = 0) -> int:
     return lib().noise_aead_dev_transport_open_packets(tr, packets or None, count, wire or None, status or None,
+                                                       stream or None)
+
+
+def dev_transport_echo_packets(tr: int, *, packets: int, count: int, wire: int, status: int, stream: int = 0) -> int:
+    """section 14: the open of the list and the seal of what it accepted, in place, in one call"""
+    return lib().noise_aead_dev_transport_echo_packets(tr, packets or None, count, wire or None, status or None,
                                                        stream or None)
 
 

@@ -26,6 +26,20 @@ with every status 0, both opens must give every payload back with every status
 change no byte.  DESIGN.md 4.17 records the figures.
 
     python tools/transport_packet_bench.py --out profiles/transport_packet.jsonl
+
+--echo: what the packet echo (section 14) costs beside the two calls it is
+defined by.  The initiator seals the list; the responder then answers it, in
+the same process, on the same object and lists, in two arms that alternate call
+by call: `echo`, one _echo_packets call, and `pair`, _open_packets followed at
+once by _seal_packets of the whole list — what a server does today if it
+refuses to synchronise in the middle of its tick (every packet is accepted, so
+the whole list is the sub-list of the accepted).  The shapes are 1 024 and
+65 536 packets at 1 and at 16 interleaved packets per slot.  Before the timing
+both arms must leave the same bytes, statuses, windows and send counters, every
+status 0, and the initiator must open every reply to the payload it sent.
+DESIGN.md 4.18 records the figures.
+
+    python tools/transport_packet_bench.py --echo --out profiles/transport_packet_echo.jsonl
 """
 import argparse
 import ctypes
@@ -40,6 +54,7 @@ sys.path[:0] = [ROOT, os.path.join(ROOT, "noise-c_amd")]
 N = 65536
 PLAIN = 1400
 WINDOW_BYTES = 136
+ECHO_SHAPES = {"one1024": (1024, 1), "one65536": (N, 1), "sixteen1024": (64, 16), "sixteen65536": (4096, 16)}
 SHAPES = {"one1024": (1024, 1), "one65536": (N, 1), "sixteen": (4096, 16), "skew1024": (1, 1024), "skew65536": (1, N)}
 
 
@@ -49,14 +64,72 @@ def stat(v):
                 spread=round((max(v) - min(v)) / med, 4))
 
 
+def echo_arms(A, torch, hip, dev, sp, ini, res, pk, pk_seal, reset, windows, timed, wire, plain, rows, pstat):
+    """--echo on one shape: (the line's own fields, whether both arms computed the same and the peer read it)"""
+    count, stride = rows.shape
+    send_ptr, ini_win = A.dev_transport_nonces(res, 0), A.dev_transport_replay(ini)[0]
+
+    def echo():
+        return A.dev_transport_echo_packets(res, **pk)
+
+    def pair():
+        return A.dev_transport_open_packets(res, **pk) or A.dev_transport_seal_packets(res, **pk)
+
+    def rewind():
+        reset()
+        assert hip.hipMemsetAsync(send_ptr, 0, 8 * N, sp) == 0
+
+    def sends():
+        v = torch.empty(N, dtype=torch.int64, device=dev)
+        assert hip.hipMemcpyAsync(v.data_ptr(), send_ptr, 8 * N, 3, sp) == 0
+        return v
+
+    # the receive batch: the list as the initiator seals it
+    wire.copy_(plain)
+    rewind()
+    assert pk_seal() == 0
+    torch.cuda.synchronize(dev)
+    ok = not pstat.any()
+    sealed = wire.clone()
+    left = {}
+    for name, fn in (("echo", echo), ("pair", pair)):
+        wire.copy_(sealed)
+        rewind()
+        assert fn() == 0
+        torch.cuda.synchronize(dev)
+        ok = ok and not pstat.any()
+        left[name] = (wire.clone(), pstat.clone(), windows(), sends())
+    ok = ok and all(torch.equal(x, y) for x, y in zip(left["echo"], left["pair"]))
+    ok = ok and int(left["echo"][3].sum()) == count  # every packet took a send counter
+    # the initiator opens the replies: the payloads it sent
+    wire.copy_(left["echo"][0])
+    assert A.dev_transport_open_packets(ini, **pk) == 0
+    torch.cuda.synchronize(dev)
+    w = wire[:count * stride].view(count, stride)
+    ok = ok and not pstat.any() and torch.equal(w[:, 10:10 + PLAIN], rows[:, 10:10 + PLAIN])
+    assert hip.hipMemsetAsync(ini_win, 0, N * WINDOW_BYTES, sp) == 0
+
+    def before(name):
+        wire.copy_(sealed)
+        rewind()
+    times = timed({"echo": echo, "pair": pair}, before)
+    ok = ok and not pstat.any()
+    med = {a: statistics.median(v) for a, v in times.items()}
+    line = dict(echo=stat(times["echo"]), pair=stat(times["pair"]), echo_over_pair=round(med["echo"] / med["pair"], 4),
+                saved_us=round(med["pair"] - med["echo"], 1))
+    return line, bool(ok)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--ciphers", default="ChaChaPoly,AESGCM")
-    ap.add_argument("--shapes", default=",".join(SHAPES))
+    ap.add_argument("--echo", action="store_true", help="time _echo_packets against _open_packets + _seal_packets")
+    ap.add_argument("--shapes", default=None, help="default: every shape of the mode")
     ap.add_argument("--rounds", type=int, default=9)
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
+    shapes = ECHO_SHAPES if args.echo else SHAPES
 
     import numpy as np
     import torch
@@ -123,8 +196,8 @@ def main():
             else:
                 assert hip.hipMemcpyAsync(win_ptr, saved.data_ptr(), N * WINDOW_BYTES, 3, sp) == 0
 
-        for shape in args.shapes.split(","):
-            E, F = SHAPES[shape]
+        for shape in (args.shapes.split(",") if args.shapes else shapes):
+            E, F = shapes[shape]
             count = E * F
             # E streams of F frames, random but for the headers and the counters' room
             plain = torch.empty(count * stride + 64, dtype=torch.uint8, device=dev)
@@ -168,6 +241,17 @@ def main():
 
             def pk_open():
                 return A.dev_transport_open_packets(res, **pk)
+
+            if args.echo:
+                line, ok = echo_arms(A, torch, hip, dev, sp, ini, res, pk, pk_seal, reset, windows, timed, wire, plain, rows, pstat)
+                bad += not ok
+                lines.append(json.dumps(dict(
+                    shape=shape, cipher=cname, slots=N, active=E, packets_per_slot=F, packets=count, payload=PLAIN,
+                    rounds=args.rounds, warmup=args.warmup, device=device_name, **line, verified=bool(ok))))
+                print(lines[-1], flush=True)
+                del plain, rows, wire
+                torch.cuda.empty_cache()
+                continue
 
             # ---- the arms compute the same bytes
             reset()
