@@ -599,7 +599,8 @@ int noise_aead_dev_dh_public(int dh_id, const uint8_t *d_priv, uint64_t priv_str
  * failed: NOISE_ERROR_MAC_FAILURE), 3 (the received ephemeral was all-zero:
  * NOISE_ERROR_INVALID_PUBLIC_KEY, :1464-1470) or 4 (a length a ragged call
  * refuses: NOISE_ERROR_INVALID_LENGTH); 2 stays reserved as in the
- * ragged calls.  The first failure is sticky.  A failed session writes only
+ * ragged calls; 5 is the fallback's "not in this object" (section 15).  The
+ * first failure is sticky.  A failed session writes only
  * inside its own slots and its later output bytes are unspecified; its opens
  * never write unauthenticated plaintext (the verify-first order) and nothing
  * more is sealed, opened or passed through for it; the split writes zeros for
@@ -1157,6 +1158,100 @@ int noise_aead_dev_transport_open_packets(NoiseAeadDevTransport *tr, const Noise
  * launched). */
 int noise_aead_dev_transport_echo_packets(NoiseAeadDevTransport *tr, const NoiseAeadPacket *d_packets, uint32_t count,
                                           uint8_t *d_wire, uint8_t *d_status, void *stream);
+
+/* ------------------------------------------------ 15. Noise Pipes fallback
+ * What noise_handshakestate_fallback and the noise_handshakestate_start after
+ * it (src/protocol/handshakestate.c:888-1079, :800-885) do for one session,
+ * done for some sessions of a batch of section 8: a responder whose static
+ * key rotated cannot decrypt the IK first message of a client that cached the
+ * old one, and both ends go on with XXfallback, reusing the initiator's
+ * ephemeral, without the host reading a status.  By name XXfallback stays out
+ * of reach (section 8: NOISE_ERROR_NOT_APPLICABLE); it is reached here, as a
+ * call on a running handshake.
+ *
+ * _fallback makes a second object *fb over the same n session indices.  Its
+ * protocol is hs's name with the pattern field replaced by XXfallback, its
+ * role the opposite of hs's, its tokens the reference's (patterns.c:444-471):
+ * pre-message <- e, then -> e, ee, s, se, then <- s, es.  The former responder
+ * is fb's initiator (_get_action: NOISE_ACTION_WRITE_MESSAGE): it keeps the
+ * ephemeral it received and its static key pair, forgets the remote static
+ * key and takes a fresh ephemeral from cfg.  The former initiator is fb's
+ * responder (NOISE_ACTION_READ_MESSAGE): it keeps its ephemeral and its static
+ * key pair and forgets both remote keys.  fb copies the public values it
+ * keeps into device memory of its own, so hs may be freed first; the
+ * private-key pointers (those given to hs's _new, and
+ * cfg->d_local_ephemeral_priv) are the caller's and must stay valid and
+ * unchanged until fb's split.  Start-up is section 8's with the new name (at
+ * most 44 characters), cfg's prologue (the fallback's own: it may differ from
+ * hs's in bytes and length) and cfg's PSK (needed again under NoisePSK: _new
+ * consumed it), then the pre-message: MixHash of the former initiator's
+ * ephemeral public key and, under NoisePSK, MixKey of it (:854-857,
+ * :870-873), which sets a key before the first message.  After that every
+ * call of section 8 works on fb unchanged: the overheads are 96 and 64.
+ *
+ * Which sessions take part is decided on the device, per session, from its
+ * status in hs.  Session i is eligible when that status is 0 or 1 for a
+ * former responder (1: the first message failed; 0: it verified and the
+ * responder falls back anyway, :1001-1005) or 0 for a former initiator; a
+ * session of status 3 or 4 never received or kept a usable e.  It takes part
+ * iff it is eligible, d_select is NULL or d_select[i] != 0, and — with
+ * NOISE_AEAD_FALLBACK_ONLY_FAILED — its status in hs is 1.  A session that
+ * does not take part has the status 5 in fb, "not in this object": it is
+ * inert from the start, as any failed session is (section 8), and fb's split
+ * writes zeros for it.  A session that takes part with status 0 gets status 5
+ * in hs, so that no session is live in both objects; a status-1 session of hs
+ * stays 1.  hs goes on as before for the sessions it keeps.
+ *
+ * Checked on the host before any launch, in this order:
+ *   - hs, cfg or fb NULL: NOISE_ERROR_INVALID_PARAM;
+ *   - hs's pattern is not NK, XK, KK or IK (interactive, the responder's
+ *     static key known beforehand), or hs is itself a fallback:
+ *     NOISE_ERROR_NOT_APPLICABLE;
+ *   - anything but exactly one message done — an initiator waiting to read
+ *     the second, a responder about to write it: NOISE_ERROR_INVALID_STATE;
+ *   - hs was made without a static private key (the NK initiator), or a
+ *     former responder's cfg has no d_local_ephemeral_priv:
+ *     NOISE_ERROR_LOCAL_KEY_REQUIRED;
+ *   - NoisePSK without d_psk: NOISE_ERROR_PSK_REQUIRED;
+ *   - prologue_len without d_prologue, a stride other than 0 below the length
+ *     (prologue) or below 32 (the keys that are read), a flag other than
+ *     NOISE_AEAD_FALLBACK_ONLY_FAILED: NOISE_ERROR_INVALID_PARAM.
+ * A refused call leaves hs as it was and *fb NULL.  n == 0 gives a valid fb
+ * and launches nothing.  The call is asynchronous on `stream`, copies nothing
+ * to the host and never synchronises; a former initiator's cfg needs no key.
+ *
+ * _fallback_merge folds the two objects' splits into one set of keys for
+ * noise_aead_dev_transport_set_keys (section 10), which clears a slot whose
+ * status byte is not 0 and wants every session's keys in one orientation.
+ * d_k1, d_k2 and the optional d_h hold hs's split as it lies, d_fb_k1,
+ * d_fb_k2 and d_fb_h fb's (d_h and d_fb_h: both or neither), d_hs_status is
+ * hs's status array.  For session i, by its status in fb:
+ *   0     d_k1[i] = d_fb_k2[i], d_k2[i] = d_fb_k1[i], d_h[i] = d_fb_h[i],
+ *         d_status[i] = 0: the keys in the original role's orientation, so
+ *         the side that sent under k2 still does;
+ *   5     nothing of the keys or the hash is written, d_status[i] =
+ *         d_hs_status[i];
+ *   else  zeros for both keys and the hash, d_status[i] = fb's status.
+ * Checked on the host before any launch: a NULL pointer (other than d_h and
+ * d_fb_h together) gives NOISE_ERROR_INVALID_PARAM; fb not _COMPLETE
+ * NOISE_ERROR_INVALID_STATE; n == 0 NOISE_ERROR_NONE and no launch; an output
+ * (d_k1, d_k2, d_h, d_status) that meets an array the call reads (d_fb_k1,
+ * d_fb_k2, d_fb_h, d_hs_status, fb's statuses) NOISE_ERROR_INVALID_PARAM.
+ * Asynchronous on `stream`. */
+#define NOISE_AEAD_FALLBACK_ONLY_FAILED 1u
+typedef struct NoiseAeadHandshakeFallbackConfig {
+    const uint8_t *d_prologue;  uint64_t prologue_stride; uint32_t prologue_len; /* the fallback's own */
+    const uint8_t *d_psk;       uint64_t psk_stride;       /* NoisePSK: needed again, _new consumed it */
+    const uint8_t *d_local_ephemeral_priv; uint64_t local_ephemeral_stride; /* the former responder's fresh e */
+    const uint8_t *d_select;    /* n bytes, or NULL: every eligible session */
+    uint32_t flags;
+} NoiseAeadHandshakeFallbackConfig;
+int noise_aead_dev_handshake_fallback(NoiseAeadDevHandshake *hs, const NoiseAeadHandshakeFallbackConfig *cfg,
+                                      NoiseAeadDevHandshake **fb, void *stream);
+int noise_aead_dev_handshake_fallback_merge(const NoiseAeadDevHandshake *fb, const uint8_t *d_hs_status,
+                                            uint8_t *d_k1, uint8_t *d_k2, const uint8_t *d_fb_k1,
+                                            const uint8_t *d_fb_k2, uint8_t *d_h, const uint8_t *d_fb_h,
+                                            uint8_t *d_status, void *stream);
 
 /* ------------------------------------------------ error reports
  * include/noise/protocol/errors.h; src/protocol/errors.c:92-127. */

@@ -36,7 +36,16 @@
  *                 lengths, nonce, i * ctx_bytes, i * hash_len); a failed
  *                 session gets the length the ragged kernels refuse (REFUSED_LEN,
  *                 aead_kernels.h), so nothing more is sealed or opened for it;
- *   hs_split      k1, k2 = HKDF(ck, ""), zeros for a failed session, and h.
+ *   hs_split      k1, k2 = HKDF(ck, ""), zeros for a failed session, and h;
+ *   hs_fallback_take   the Noise Pipes fallback (header section 15): which
+ *                 sessions of a handshake go on in the XXfallback object made of
+ *                 it (hs_fallback_takes, handshake_plan.h) — status 0 there, 5
+ *                 for the others, 5 here for a live session that leaves — and
+ *                 the copy of the public keys the new object keeps;
+ *   hs_fallback_merge  the fallback's split folded into the original's, the
+ *                 keys swapped back into the original role's orientation.
+ * A fallback object is an ordinary object whose pattern is HS_XXFALLBACK: its
+ * start-up ends with the pre-message e, and every call below serves it.
  * DH tokens are the ladder launches of noise_aead_dev_dh_calculate into an
  * arena the object owns; the AEAD steps are noise_aead_dev_seal_ragged /
  * _open_ragged (verify-first) under AD = h; AES-GCM key contexts are prepared
@@ -57,7 +66,6 @@ namespace {
 constexpr uint32_t HS_BLOCK = 64;
 constexpr size_t HS_ALIGN = 64; /* of the parts of the object's device allocation */
 constexpr uint8_t HS_STATUS_MAC = 1, HS_STATUS_NULL_KEY = 3;
-constexpr size_t HS_NAME_MAX = 64; /* the longest name in scope has 36 characters */
 
 struct InitArgs {
     int hash_id;
@@ -260,10 +268,71 @@ __global__ __launch_bounds__(HS_BLOCK) void hs_split(SplitArgs a)
     for (int j = 0; j < 64; ++j) ck[j] = o1[j] = o2[j] = 0;
 }
 
+/* noise_aead_dev_handshake_fallback: which sessions take part
+   (hs_fallback_takes, handshake_plan.h) and the public values the new object
+   keeps.  Session i's status in the new object is 0 or 5; a session that
+   leaves the original with status 0 gets 5 there.  The former initiator's
+   ephemeral public key and the local static public key are copied as they
+   lie, one row when the key is shared. */
+struct FallbackArgs {
+    uint32_t n, flags, was_initiator;
+    const uint8_t *select;
+    uint8_t *hs_status, *fb_status;
+    const uint8_t *e_src; /* the original's re (a former responder) or le_pub */
+    uint8_t *e_dst;       /* the new object's re, or le_pub */
+    uint64_t e_stride;    /* 0: one ephemeral for all, copied by lane 0 */
+    const uint8_t *ls_src; /* NULL: the original never computed it */
+    uint8_t *ls_dst;
+    uint64_t ls_stride;
+};
+
+__global__ __launch_bounds__(HS_BLOCK) void hs_fallback_take(FallbackArgs a)
+{
+    const uint32_t i = blockIdx.x * HS_BLOCK + threadIdx.x;
+    if (i >= a.n) return;
+    const uint8_t st = a.hs_status[i];
+    const bool takes = hs_fallback_takes(st, !a.select || a.select[i], a.flags, a.was_initiator);
+    a.fb_status[i] = takes ? 0 : HS_STATUS_ABSENT;
+    if (takes && !st) a.hs_status[i] = HS_STATUS_ABSENT;
+    if (a.e_stride ? takes : i == 0)
+        for (int j = 0; j < 32; ++j) a.e_dst[(size_t)i * a.e_stride + j] = a.e_src[(size_t)i * a.e_stride + j];
+    if (a.ls_src && (a.ls_stride ? takes : i == 0))
+        for (int j = 0; j < 32; ++j) a.ls_dst[(size_t)i * a.ls_stride + j] = a.ls_src[(size_t)i * a.ls_stride + j];
+}
+
+struct MergeArgs {
+    uint32_t hl, n;
+    const uint8_t *fb_status, *hs_status, *fb_k1, *fb_k2, *fb_h;
+    uint8_t *k1, *k2, *h, *status;
+};
+
+/* noise_aead_dev_handshake_fallback_merge: the fallback's keys swapped into
+   the original role's orientation, over the original's split */
+__global__ __launch_bounds__(HS_BLOCK) void hs_fallback_merge(MergeArgs a)
+{
+    const uint32_t i = blockIdx.x * HS_BLOCK + threadIdx.x;
+    if (i >= a.n) return;
+    const uint8_t st = a.fb_status[i];
+    const HsMerge rule = hs_fallback_merge_rule(st);
+    if (rule == HS_MERGE_KEEP) {
+        a.status[i] = a.hs_status[i];
+        return;
+    }
+    const bool take = rule == HS_MERGE_TAKE;
+    for (int j = 0; j < 32; ++j) {
+        a.k1[(size_t)i * 32 + j] = take ? a.fb_k2[(size_t)i * 32 + j] : 0;
+        a.k2[(size_t)i * 32 + j] = take ? a.fb_k1[(size_t)i * 32 + j] : 0;
+    }
+    if (a.h)
+        for (uint32_t j = 0; j < a.hl; ++j) a.h[(size_t)i * a.hl + j] = take ? a.fb_h[(size_t)i * a.hl + j] : 0;
+    a.status[i] = st;
+}
+
 } // namespace
 
 struct NoiseAeadDevHandshake {
     HsName name;
+    bool fallback; /* the pattern is HS_XXFALLBACK, name.pattern the one it followed */
     int role, action, index;
     uint32_t n, hl;
     bool keyed, ctx_stale;
@@ -282,7 +351,7 @@ namespace {
 
 typedef NoiseAeadDevHandshake Hs;
 
-const HsPattern &pattern_of(const Hs *hs) { return HS_PATTERNS[hs->name.pattern]; }
+const HsPattern &pattern_of(const Hs *hs) { return hs->fallback ? HS_XXFALLBACK : HS_PATTERNS[hs->name.pattern]; }
 
 HsMessage next_message(const Hs *hs) { return hs_message(pattern_of(hs), hs->role, hs->name.psk, hs->index, hs->keyed); }
 
@@ -425,6 +494,83 @@ void advance(Hs *hs, const HsMessage &m)
     ++hs->index;
 }
 
+/* h and ck of the name, MixHash(prologue), the PSK step
+   (symmetricstate.c:97-108, handshakestate.c:822-842) */
+int start_symmetric(Hs *hs, const char *name, const uint8_t *d_prologue, uint64_t prologue_stride, uint32_t prologue_len,
+                    const uint8_t *d_psk, uint64_t psk_stride, hipStream_t s)
+{
+    InitArgs ia = {};
+    ia.hash_id = hs->name.hash_id;
+    ia.hl = hs->hl;
+    ia.n = hs->n;
+    ia.name_len = (uint32_t)strlen(name);
+    ia.h = hs->h;
+    ia.ck = hs->ck;
+    memcpy(ia.name, name, ia.name_len);
+    int rc = launch_items(hs_init, hs->n, HS_BLOCK, s, ia);
+    if (!rc) rc = mix_hash(hs, strided(prologue_len ? d_prologue : hs->arena, prologue_stride), prologue_len, NO_COPY, s);
+    if (!rc && hs->name.psk) rc = mix_key(hs, d_psk, psk_stride, false, true, s);
+    return rc;
+}
+
+/* the device arrays of an object of n > 0 sessions */
+bool carve(Hs *hs)
+{
+    const size_t n = hs->n;
+    DevArena &d = hs->dev;
+    d.align = HS_ALIGN;
+    const size_t o_ck = d.carve(n * hs->hl), o_h = d.carve(n * hs->hl), o_k = d.carve(n * 32);
+    const size_t o_ctx = d.carve(hs->name.cipher_id == NOISE_CIPHER_AESGCM ? n * hs->ctx_bytes : 0);
+    const size_t o_arena = d.carve(n * 32), o_status = d.carve(n), o_step = d.carve(n);
+    const size_t o_ls = d.carve(n * 32), o_le = d.carve(n * 32), o_re = d.carve(n * 32);
+    const size_t o_rs = d.carve(n * 32), o_recs = d.carve(n * sizeof(RecDesc));
+    if (!d.alloc()) return false;
+    hs->ck = d.at(o_ck); hs->h = d.at(o_h); hs->k = d.at(o_k); hs->ctx = d.at(o_ctx); hs->arena = d.at(o_arena);
+    hs->status = d.at(o_status); hs->step = d.at(o_step); hs->ls_pub = d.at(o_ls); hs->le_pub = d.at(o_le);
+    hs->re = d.at(o_re); hs->rs = d.at(o_rs); hs->recs = d.at<RecDesc>(o_recs);
+    return true;
+}
+
+/* everything _fallback launches, after the allocation: who takes part and
+   what fb keeps, a former responder's fresh ephemeral, the start-up with the
+   new name, then the pre-message e (handshakestate.c:848-857, :864-873) */
+int start_fallback(Hs *fb, Hs *hs, const NoiseAeadHandshakeFallbackConfig *cfg, const char *name, hipStream_t s)
+{
+    const bool init = hs_is_initiator(fb->role); /* the former responder */
+    int rc = fb->dev.zero(s);
+    if (rc) return rc;
+    FallbackArgs a = {};
+    a.n = hs->n;
+    a.flags = cfg->flags;
+    a.was_initiator = !init;
+    a.select = cfg->d_select;
+    a.hs_status = hs->status;
+    a.fb_status = fb->status;
+    a.e_src = init ? hs->re : hs->le_pub;
+    a.e_dst = init ? fb->re : fb->le_pub;
+    a.e_stride = init ? HS_DH_LEN : hs->le_pub_stride;
+    /* a static key the original pattern had no use for has no public key yet */
+    const bool have_ls_pub = hs_needs(pattern_of(hs), hs->role).local_static;
+    a.ls_src = have_ls_pub ? hs->ls_pub : nullptr;
+    a.ls_dst = fb->ls_pub;
+    a.ls_stride = hs->ls_pub_stride;
+    rc = launch_items(hs_fallback_take, hs->n, HS_BLOCK, s, a);
+    if (!rc && !have_ls_pub)
+        rc = noise_aead_dev_dh_public(NOISE_DH_CURVE25519, fb->ls_priv, fb->ls_stride, fb->ls_stride ? fb->n : 1,
+                                      fb->ls_pub, s);
+    if (!rc && init)
+        rc = noise_aead_dev_dh_public(NOISE_DH_CURVE25519, fb->le_priv, fb->le_stride, fb->le_stride ? fb->n : 1,
+                                      fb->le_pub, s);
+    if (!rc)
+        rc = start_symmetric(fb, name, cfg->d_prologue, cfg->prologue_stride, cfg->prologue_len, cfg->d_psk,
+                             cfg->psk_stride, s);
+    const uint8_t *e = init ? fb->re : fb->le_pub;
+    const uint64_t e_stride = init ? HS_DH_LEN : fb->le_pub_stride;
+    if (!rc) rc = mix_hash(fb, strided(e, e_stride), HS_DH_LEN, NO_COPY, s);
+    if (!rc && fb->name.psk) rc = mix_key(fb, e, e_stride, false, false, s);
+    return rc;
+}
+
 /* everything _new launches, after the allocation */
 int start(Hs *hs, const NoiseAeadHandshakeConfig *cfg, hipStream_t s)
 {
@@ -441,21 +587,10 @@ int start(Hs *hs, const NoiseAeadHandshakeConfig *cfg, hipStream_t s)
     if (!rc && need.remote_static)
         rc = launch_items(hs_copy32, hs->n, HS_BLOCK, s, cfg->d_remote_static_pub, cfg->remote_static_stride, hs->rs,
                           hs->n);
-    if (rc) return rc;
-    InitArgs ia = {};
-    ia.hash_id = hs->name.hash_id;
-    ia.hl = hs->hl;
-    ia.n = hs->n;
-    ia.name_len = (uint32_t)strlen(cfg->protocol_name);
-    ia.h = hs->h;
-    ia.ck = hs->ck;
-    memcpy(ia.name, cfg->protocol_name, ia.name_len);
-    rc = launch_items(hs_init, hs->n, HS_BLOCK, s, ia);
-    /* handshakestate.c:822-877 */
     if (!rc)
-        rc = mix_hash(hs, strided(cfg->prologue_len ? cfg->d_prologue : hs->arena, cfg->prologue_stride),
-                      cfg->prologue_len, NO_COPY, s);
-    if (!rc && hs->name.psk) rc = mix_key(hs, cfg->d_psk, cfg->psk_stride, false, true, s);
+        rc = start_symmetric(hs, cfg->protocol_name, cfg->d_prologue, cfg->prologue_stride, cfg->prologue_len, cfg->d_psk,
+                             cfg->psk_stride, s);
+    /* :844-877 */
     const bool init = hs_is_initiator(hs->role);
     const HsSpan ls_pub = strided(hs->ls_pub, hs->ls_pub_stride), rs = strided(hs->rs, HS_DH_LEN);
     if (!rc && p.pre_i_s) rc = mix_hash(hs, init ? ls_pub : rs, HS_DH_LEN, NO_COPY, s);
@@ -490,21 +625,10 @@ int noise_aead_dev_handshake_new(NoiseAeadDevHandshake **out, const NoiseAeadHan
     hs->ls_pub_stride = hs->ls_stride ? HS_DH_LEN : 0;
     hs->le_pub_stride = hs->le_stride ? HS_DH_LEN : 0;
     if (hs->n) {
-        const size_t n = hs->n;
-        DevArena &d = hs->dev;
-        d.align = HS_ALIGN;
-        const size_t o_ck = d.carve(n * hs->hl), o_h = d.carve(n * hs->hl), o_k = d.carve(n * 32);
-        const size_t o_ctx = d.carve(name.cipher_id == NOISE_CIPHER_AESGCM ? n * hs->ctx_bytes : 0);
-        const size_t o_arena = d.carve(n * 32), o_status = d.carve(n), o_step = d.carve(n);
-        const size_t o_ls = d.carve(n * 32), o_le = d.carve(n * 32), o_re = d.carve(n * 32);
-        const size_t o_rs = d.carve(n * 32), o_recs = d.carve(n * sizeof(RecDesc));
-        if (!d.alloc()) {
+        if (!carve(hs)) {
             delete hs;
             return NOISE_ERROR_NO_MEMORY;
         }
-        hs->ck = d.at(o_ck); hs->h = d.at(o_h); hs->k = d.at(o_k); hs->ctx = d.at(o_ctx); hs->arena = d.at(o_arena);
-        hs->status = d.at(o_status); hs->step = d.at(o_step); hs->ls_pub = d.at(o_ls); hs->le_pub = d.at(o_le);
-        hs->re = d.at(o_re); hs->rs = d.at(o_rs); hs->recs = d.at<RecDesc>(o_recs);
         rc = start(hs, cfg, (hipStream_t)stream);
         if (rc) {
             noise_aead_dev_handshake_free(hs);
@@ -613,6 +737,62 @@ int noise_aead_dev_handshake_split(NoiseAeadDevHandshake *hs, uint8_t *d_k1, uin
     }
     hs->action = NOISE_ACTION_COMPLETE;
     return rc;
+}
+
+int noise_aead_dev_handshake_fallback(NoiseAeadDevHandshake *hs, const NoiseAeadHandshakeFallbackConfig *cfg,
+                                      NoiseAeadDevHandshake **out, void *stream)
+{
+    if (out) *out = nullptr;
+    HsFallbackFrom from = {};
+    if (hs) from = {&pattern_of(hs), hs->name.psk, hs->role, hs->action, hs->index, hs->ls_priv != nullptr};
+    int rc = hs_check_fallback(from, cfg, out);
+    if (rc) return rc;
+    char name[HS_NAME_MAX];
+    if (!hs_fallback_name(hs->name, name, sizeof(name))) return NOISE_ERROR_INVALID_LENGTH;
+    Hs *fb = new (std::nothrow) Hs();
+    if (!fb) return NOISE_ERROR_NO_MEMORY;
+    const bool init = !hs_is_initiator(hs->role); /* the roles swap (handshakestate.c:1035-1046) */
+    fb->name = hs->name;
+    fb->fallback = true;
+    fb->role = init ? NOISE_ROLE_INITIATOR : NOISE_ROLE_RESPONDER;
+    fb->action = hs_first_action(fb->role);
+    fb->n = hs->n;
+    fb->hl = hs->hl;
+    fb->ctx_bytes = hs->ctx_bytes;
+    fb->ls_priv = hs->ls_priv;
+    fb->ls_stride = hs->ls_stride;
+    fb->ls_pub_stride = hs->ls_pub_stride;
+    fb->le_priv = init ? cfg->d_local_ephemeral_priv : hs->le_priv;
+    fb->le_stride = init ? cfg->local_ephemeral_stride : hs->le_stride;
+    fb->le_pub_stride = fb->le_stride ? HS_DH_LEN : 0;
+    if (fb->n) {
+        if (!carve(fb)) {
+            delete fb;
+            return NOISE_ERROR_NO_MEMORY;
+        }
+        rc = start_fallback(fb, hs, cfg, name, (hipStream_t)stream);
+        if (rc) {
+            noise_aead_dev_handshake_free(fb);
+            return rc;
+        }
+    } else {
+        fb->keyed = hs_keyed_before(HS_XXFALLBACK, fb->name.psk, 0);
+    }
+    *out = fb;
+    return NOISE_ERROR_NONE;
+}
+
+int noise_aead_dev_handshake_fallback_merge(const NoiseAeadDevHandshake *fb, const uint8_t *d_hs_status,
+                                            uint8_t *d_k1, uint8_t *d_k2, const uint8_t *d_fb_k1,
+                                            const uint8_t *d_fb_k2, uint8_t *d_h, const uint8_t *d_fb_h,
+                                            uint8_t *d_status, void *stream)
+{
+    const int rc = hs_check_fallback_merge(fb, fb ? fb->action : NOISE_ACTION_NONE, fb ? fb->n : 0, fb ? fb->hl : 0,
+                                           fb ? fb->status : nullptr, d_hs_status, d_k1, d_k2, d_fb_k1, d_fb_k2, d_h,
+                                           d_fb_h, d_status);
+    if (rc || !fb->n) return rc;
+    const MergeArgs a = {fb->hl, fb->n, fb->status, d_hs_status, d_fb_k1, d_fb_k2, d_fb_h, d_k1, d_k2, d_h, d_status};
+    return launch_items(hs_fallback_merge, fb->n, HS_BLOCK, (hipStream_t)stream, a);
 }
 
 const uint8_t *noise_aead_dev_handshake_status(const NoiseAeadDevHandshake *hs) { return hs ? hs->status : nullptr; }

@@ -4,7 +4,11 @@
  * table of the fifteen one-way and interactive patterns, the ordered steps and
  * the overhead of every message for (pattern, role, prefix, message index),
  * the argument checks of the entry points, and the length rule of one session
- * of a ragged call (hs_session_len, which the kernels run too).
+ * of a ragged call (hs_session_len, which the kernels run too), and the Noise
+ * Pipes fallback (header section 15): XXfallback as a pattern of its own, its
+ * name, who takes part (hs_fallback_takes, which the kernel runs too), the
+ * merge rule and the argument checks of the two calls
+ * (asan/handshake_fallback_check.cpp, tests/test_handshake_fallback_host.py).
  *
  * No HIP header is included and no device pointer is dereferenced, so all of
  * it compiles with a host compiler alone and runs under ASan/UBSan
@@ -36,6 +40,7 @@ struct HsPattern {
     uint8_t n_msgs;
     uint8_t n_toks[HS_MAX_MSGS];
     HsTok toks[HS_MAX_MSGS][HS_MAX_TOKS];
+    bool pre_r_e; /* the responder's ephemeral key is a pre-message (HS_XXFALLBACK alone) */
 };
 
 /* initiator pre-message | responder pre-message | messages (-> <- -> ...) */
@@ -57,6 +62,14 @@ constexpr HsPattern HS_PATTERNS[] = {
     {"IX", false, false, 2, {2, 5}, {{HT_E, HT_S}, {HT_E, HT_EE, HT_SE, HT_S, HT_ES}}},
 };
 constexpr int HS_N_PATTERNS = (int)(sizeof(HS_PATTERNS) / sizeof(HS_PATTERNS[0]));
+
+/* XXfallback as the reference has it (patterns.c:444-471), the roles swapped
+   against the handshake it follows: pre-message <- e, then -> e, ee, s, se and
+   <- s, es.  Not a row of HS_PATTERNS: no name reaches it (hs_parse_name walks
+   that table and refuses "XXfallback"); noise_aead_dev_handshake_fallback
+   makes it of a running handshake (the end of this file). */
+constexpr HsPattern HS_XXFALLBACK = {"XXfallback", false, false, 2, {4, 2}, {{HT_E, HT_EE, HT_S, HT_SE}, {HT_S, HT_ES}},
+                                     true};
 
 /* ------------------------------------------------------------ name parser */
 
@@ -184,9 +197,11 @@ inline bool hs_is_initiator(int role) { return role == NOISE_ROLE_INITIATOR; }
 
 /* whether a key is set when message `index` starts: a DH token, or an `e`
    under NoisePSK, of an earlier message set it (the PSK start-up step itself
-   sets none) */
+   sets none); a pre-message `e` under NoisePSK set it before message 0
+   (handshakestate.c:854-857, :870-873) */
 inline bool hs_keyed_before(const HsPattern &p, bool psk, int index)
 {
+    if (psk && p.pre_r_e) return true;
     for (int m = 0; m < index && m < p.n_msgs; ++m)
         for (int t = 0; t < p.n_toks[m]; ++t)
             if (p.toks[m][t] >= HT_EE || (psk && p.toks[m][t] == HT_E)) return true;
@@ -242,15 +257,17 @@ inline int hs_first_action(int role)
 
 /* What a role must bring: its static key pair when it has a pre-message `s`
    or sends an `s` token, its ephemeral private key when it sends an `e`, the
-   remote static public key when the other side's `s` is a pre-message. */
+   remote static public key when the other side's `s` is a pre-message.  A
+   pre-message `e` of the responder is an ephemeral key pair the responder
+   brings and a remote ephemeral public key the initiator brings. */
 struct HsNeeds {
-    bool local_static, local_ephemeral, remote_static;
+    bool local_static, local_ephemeral, remote_static, remote_ephemeral;
 };
 
 inline HsNeeds hs_needs(const HsPattern &p, int role)
 {
     const bool init = hs_is_initiator(role);
-    HsNeeds r = {init ? p.pre_i_s : p.pre_r_s, false, init ? p.pre_r_s : p.pre_i_s};
+    HsNeeds r = {init ? p.pre_i_s : p.pre_r_s, p.pre_r_e && !init, init ? p.pre_r_s : p.pre_i_s, p.pre_r_e && init};
     for (int m = init ? 0 : 1; m < p.n_msgs; m += 2)
         for (int t = 0; t < p.n_toks[m]; ++t) {
             if (p.toks[m][t] == HT_S) r.local_static = true;
@@ -429,6 +446,113 @@ inline int hs_check_split(int action, uint32_t n, uint32_t hash_len, const void 
     if (hs_spans_meet(d_k1, 0, kb, d_k2, 0, kb, 1)) return NOISE_ERROR_INVALID_PARAM;
     if (d_hh && (hs_spans_meet(d_k1, 0, kb, d_hh, 0, hb, 1) || hs_spans_meet(d_k2, 0, kb, d_hh, 0, hb, 1)))
         return NOISE_ERROR_INVALID_PARAM;
+    return NOISE_ERROR_NONE;
+}
+
+/* ------------------------------------------------- the Noise Pipes fallback
+   noise_aead_dev_handshake_fallback / _fallback_merge (header section 15):
+   the new name, the patterns it may follow, which sessions take part — one
+   statement for both compilers, run by the hs_fallback_take kernel of
+   handshake.hip and by asan/handshake_fallback_check.cpp — and the argument
+   checks of the two calls. */
+
+constexpr uint8_t HS_STATUS_ABSENT = 5; /* "not in this object" */
+constexpr size_t HS_NAME_MAX = 64;      /* the longest name, a NoisePSK XXfallback one, has 44 characters */
+
+/* the name of `name`'s handshake with the pattern field replaced by
+   XXfallback; the length, 0 when it does not fit in cap bytes with its NUL */
+inline size_t hs_fallback_name(const HsName &name, char *out, size_t cap)
+{
+    const char *hash = name.hash_id == NOISE_HASH_BLAKE2s   ? "BLAKE2s"
+                       : name.hash_id == NOISE_HASH_BLAKE2b ? "BLAKE2b"
+                       : name.hash_id == NOISE_HASH_SHA256  ? "SHA256"
+                                                            : "SHA512";
+    const char *parts[] = {name.psk ? "NoisePSK" : "Noise", "_", HS_XXFALLBACK.name, "_25519_",
+                           name.cipher_id == NOISE_CIPHER_AESGCM ? "AESGCM" : "ChaChaPoly", "_", hash};
+    size_t len = 0;
+    for (const char *p : parts) {
+        const size_t n = strlen(p);
+        if (len + n >= cap) return 0;
+        memcpy(out + len, p, n);
+        len += n;
+    }
+    out[len] = 0;
+    return len;
+}
+
+/* NOISE_REQ_FALLBACK_POSSIBLE: interactive, the responder's static key known
+   beforehand */
+inline bool hs_fallback_possible(const HsPattern &p) { return p.n_msgs >= 2 && p.pre_r_s; }
+
+/* A former responder falls back after a first message that failed (1) or that
+   verified (0: "it decides to always fall back anyway",
+   handshakestate.c:1001-1005), a former initiator after writing it (0).  A
+   session of status 3 or 4 never received or kept a usable e. */
+HS_FN bool hs_fallback_eligible(uint8_t status, bool was_initiator)
+{
+    return status == 0 || (status == 1 && !was_initiator);
+}
+
+/* whether a session of that status in the original handshake takes part in
+   the fallback; selected: d_select is NULL or the session's byte is not 0 */
+HS_FN bool hs_fallback_takes(uint8_t status, bool selected, uint32_t flags, bool was_initiator)
+{
+    if (!hs_fallback_eligible(status, was_initiator) || !selected) return false;
+    return (flags & NOISE_AEAD_FALLBACK_ONLY_FAILED) ? status == 1 : true;
+}
+
+/* what _fallback_merge does with a session by its status in the fallback */
+enum HsMerge : uint8_t { HS_MERGE_TAKE, HS_MERGE_KEEP, HS_MERGE_ZERO };
+
+HS_FN HsMerge hs_fallback_merge_rule(uint8_t fb_status)
+{
+    return fb_status == 0 ? HS_MERGE_TAKE : (fb_status == HS_STATUS_ABSENT ? HS_MERGE_KEEP : HS_MERGE_ZERO);
+}
+
+/* the handshake a fallback is asked of, as the host object knows it */
+struct HsFallbackFrom {
+    const HsPattern *pattern; /* NULL: no object */
+    bool psk;
+    int role, action, index;  /* index: messages done */
+    bool has_static;          /* a static private key was given to _new */
+};
+
+/* noise_aead_dev_handshake_fallback, in the order of the header */
+inline int hs_check_fallback(const HsFallbackFrom &from, const NoiseAeadHandshakeFallbackConfig *cfg, const void *fb)
+{
+    if (!from.pattern || !cfg || !fb) return NOISE_ERROR_INVALID_PARAM;
+    if (from.pattern->pre_r_e || !hs_fallback_possible(*from.pattern)) return NOISE_ERROR_NOT_APPLICABLE;
+    const bool init = hs_is_initiator(from.role);
+    if (from.index != 1 || from.action != (init ? NOISE_ACTION_READ_MESSAGE : NOISE_ACTION_WRITE_MESSAGE))
+        return NOISE_ERROR_INVALID_STATE;
+    if (!from.has_static || (!init && !cfg->d_local_ephemeral_priv)) return NOISE_ERROR_LOCAL_KEY_REQUIRED;
+    if (from.psk && !cfg->d_psk) return NOISE_ERROR_PSK_REQUIRED;
+    if (cfg->prologue_len && !cfg->d_prologue) return NOISE_ERROR_INVALID_PARAM;
+    if (cfg->prologue_len && cfg->prologue_stride && cfg->prologue_stride < cfg->prologue_len)
+        return NOISE_ERROR_INVALID_PARAM;
+    if ((from.psk && !hs_key_stride_ok(cfg->psk_stride)) || (!init && !hs_key_stride_ok(cfg->local_ephemeral_stride)))
+        return NOISE_ERROR_INVALID_PARAM;
+    if (cfg->flags & ~NOISE_AEAD_FALLBACK_ONLY_FAILED) return NOISE_ERROR_INVALID_PARAM;
+    return NOISE_ERROR_NONE;
+}
+
+/* noise_aead_dev_handshake_fallback_merge: the outputs (32n, 32n, hash_len * n
+   and n bytes) against every array the call reads (d_fb_status: the
+   fallback's own statuses) */
+inline int hs_check_fallback_merge(const void *fb, int action, uint32_t n, uint32_t hash_len, const void *d_fb_status,
+                                   const void *d_hs_status, const void *d_k1, const void *d_k2, const void *d_fb_k1,
+                                   const void *d_fb_k2, const void *d_h, const void *d_fb_h, const void *d_status)
+{
+    if (!fb || !d_hs_status || !d_k1 || !d_k2 || !d_fb_k1 || !d_fb_k2 || !d_status || (!d_h != !d_fb_h))
+        return NOISE_ERROR_INVALID_PARAM;
+    if (action != NOISE_ACTION_COMPLETE) return NOISE_ERROR_INVALID_STATE;
+    if (!n) return NOISE_ERROR_NONE;
+    const hs_u128 kb = (hs_u128)32 * n, hb = (hs_u128)hash_len * n;
+    const void *outs[] = {d_k1, d_k2, d_h, d_status}, *ins[] = {d_fb_k1, d_fb_k2, d_fb_h, d_hs_status, d_fb_status};
+    const hs_u128 out_bytes[] = {kb, kb, d_h ? hb : 0, n}, in_bytes[] = {kb, kb, d_fb_h ? hb : 0, n, d_fb_status ? n : 0};
+    for (int o = 0; o < 4; ++o)
+        for (int i = 0; i < 5; ++i)
+            if (hs_ranges_meet(outs[o], out_bytes[o], ins[i], in_bytes[i])) return NOISE_ERROR_INVALID_PARAM;
     return NOISE_ERROR_NONE;
 }
 

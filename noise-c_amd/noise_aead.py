@@ -102,6 +102,16 @@ class NoiseAeadHandshakeConfig(C.Structure):
                 ("d_remote_static_pub", C.c_void_p), ("remote_static_stride", C.c_uint64)]
 
 
+class NoiseAeadHandshakeFallbackConfig(C.Structure):
+    _fields_ = [("d_prologue", C.c_void_p), ("prologue_stride", C.c_uint64), ("prologue_len", C.c_uint32),
+                ("d_psk", C.c_void_p), ("psk_stride", C.c_uint64),
+                ("d_local_ephemeral_priv", C.c_void_p), ("local_ephemeral_stride", C.c_uint64),
+                ("d_select", C.c_void_p), ("flags", C.c_uint32)]
+
+
+FALLBACK_ONLY_FAILED = 1
+
+
 class NoiseAeadTransportResult(C.Structure):
     _fields_ = [("frames", C.c_uint32), ("consumed", C.c_uint32), ("error", C.c_int32),
                 ("reserved_", C.c_uint32)]
@@ -194,6 +204,8 @@ def lib() -> C.CDLL:
         "noise_aead_dev_handshake_split": (i, [vp, vp, vp, vp, vp]),
         "noise_aead_dev_handshake_status": (vp, [vp]),
         "noise_aead_dev_handshake_remote_static": (vp, [vp]),
+        "noise_aead_dev_handshake_fallback": (i, [vp, P(NoiseAeadHandshakeFallbackConfig), P(vp), vp]),
+        "noise_aead_dev_handshake_fallback_merge": (i, [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]),
         "noise_aead_dev_transport_new": (i, [P(vp), i, i, C.c_uint32, vp, vp, C.c_uint32, vp]),
         "noise_aead_dev_transport_free": (i, [vp]),
         "noise_aead_dev_transport_nonces": (vp, [vp, i]),
@@ -598,6 +610,31 @@ def dev_handshake_status(hs: int) -> int:
 def dev_handshake_remote_static(hs: int) -> int:
     """device pointer of the n x 32 remote static public keys"""
     return lib().noise_aead_dev_handshake_remote_static(hs) or 0
+
+
+# ---- the Noise Pipes fallback (include/noise_aead_hip.h section 15)
+
+def dev_handshake_fallback(hs: int, *, prologue: int = 0, prologue_stride: int = 0, prologue_len: int = 0,
+                           psk: int = 0, psk_stride: int = 32, local_ephemeral: int = 0,
+                           local_ephemeral_stride: int = 32, select: int = 0, flags: int = 0, stream: int = 0,
+                           no_cfg: bool = False, no_out: bool = False):
+    """noise_aead_dev_handshake_fallback: (rc, fb); fb is None unless rc == 0.
+    no_cfg / no_out: a NULL cfg / a NULL fb pointer, for the argument tests."""
+    cfg = NoiseAeadHandshakeFallbackConfig(prologue or None, prologue_stride, prologue_len, psk or None, psk_stride,
+                                           local_ephemeral or None, local_ephemeral_stride, select or None, flags)
+    fb = C.c_void_p()
+    rc = lib().noise_aead_dev_handshake_fallback(hs, None if no_cfg else C.byref(cfg), None if no_out else C.byref(fb),
+                                                 stream or None)
+    return rc, fb.value
+
+
+def dev_handshake_fallback_merge(fb: int, *, hs_status: int, k1: int, k2: int, fb_k1: int, fb_k2: int, h: int = 0,
+                                 fb_h: int = 0, status: int, stream: int = 0) -> int:
+    """noise_aead_dev_handshake_fallback_merge: fb's split folded into hs's
+    (k1, k2, h as they lie) and the n status bytes for _set_keys."""
+    return lib().noise_aead_dev_handshake_fallback_merge(fb, hs_status or None, k1 or None, k2 or None, fb_k1 or None,
+                                                         fb_k2 or None, h or None, fb_h or None, status or None,
+                                                         stream or None)
 
 
 # ---- device-resident transport sessions (include/noise_aead_hip.h section 9);
