@@ -1253,6 +1253,111 @@ int noise_aead_dev_handshake_fallback_merge(const NoiseAeadDevHandshake *fb, con
                                             const uint8_t *d_fb_k2, uint8_t *d_h, const uint8_t *d_fb_h,
                                             uint8_t *d_status, void *stream);
 
+/* ------------------------------------------------ 16. sessions that change their object
+ *
+ * An object of section 8 runs its n sessions in lockstep: the action, the
+ * message index, "is a key set" and the nonce are host values of the whole
+ * object, and every message call advances them for the batch.  That fits a
+ * two-message pattern.  The third message of XX, XK and XN, and the second of
+ * an XXfallback object (section 15), comes back from each client in its own
+ * time.  Lockstep stays; what these calls add is that a session can change its
+ * object.  A lane of status 5, "not in this object" (section 15), is inert in
+ * every call: that is an empty lane.
+ *
+ * _new_like makes an empty object of `capacity` lanes at the position of
+ * `like`: its protocol name, fallback flag, role, action, message index, "is
+ * a key set", nonce, hash length and cipher context size.  Every lane has the
+ * status 5 and every other device byte the object owns is zero.  Each of
+ * like's two private keys (static, ephemeral) on its own: a key like holds per
+ * session (stride != 0) gets capacity x 32 bytes the object owns, read at
+ * stride 32 from then on; a key like holds once for all (stride 0) is read
+ * through like's pointer, which stays the caller's and must stay valid, and
+ * its one public-key row is copied now; a key like never had stays absent.
+ * After that the object is an ordinary one: every call of sections 8 and 15
+ * but _fallback serves it, over all `capacity` lanes, and _free scrubs the
+ * owned rows with the rest.  Checked on the host, in this order: a NULL out or
+ * like gives NOISE_ERROR_INVALID_PARAM; like at NOISE_ACTION_COMPLETE or
+ * _NONE gives NOISE_ERROR_INVALID_STATE.  capacity == 0 gives a valid object
+ * that allocates and launches nothing.  *out is NULL after a refused call.
+ *
+ * _move: entry j (j < m) moves the session in lane d_src_lanes[j] of src into
+ * lane d_dst_lanes[j] of dst.  Either list may be NULL and then means
+ * 0 .. m-1.  d_result may be NULL; otherwise byte j receives the outcome,
+ * the causes tested in this order:
+ *   NOISE_AEAD_MOVE_RANGE  3  a lane number >= n of its object; nothing is
+ *                             read or written for the entry;
+ *   NOISE_AEAD_MOVE_EMPTY  1  the source lane has the status 5;
+ *   NOISE_AEAD_MOVE_TAKEN  2  the destination lane has another status than 5;
+ *   NOISE_AEAD_MOVED       0  otherwise.
+ * A failed session (status 1, 3 or 4) moves with its status, so that the
+ * status array of the object it ends in still clears its slot in _set_keys
+ * (section 10).  A moved entry copies ck, h, k, the status, the remote
+ * ephemeral and static keys, the public-key rows held per session and the
+ * private-key rows held per session — read from src's pointer and stride, the
+ * caller's memory or owned rows, no alignment assumed — into dst's owned rows.
+ * Then the source lane is scrubbed: every one of those rows that src owns is
+ * zeroed, with the lane's AES-GCM context, and its status set to 5.  The
+ * caller's own key memory is never written.  AES-GCM contexts are not copied:
+ * a dst with a key set prepares them from k before its next AEAD step, as
+ * after a MixKey.  The lanes of one call must be distinct per object; they
+ * live in device memory, so that is the caller's guarantee, unchecked as for
+ * _set_keys.
+ *
+ * Checked on the host before any launch, in this order; a refused call leaves
+ * both objects as they were:
+ *   1. a NULL object gives NOISE_ERROR_INVALID_PARAM;
+ *   2. src == dst gives NOISE_ERROR_INVALID_PARAM;
+ *   3. the two objects must be at the same position — name, fallback flag,
+ *      role, action, message index, "is a key set" and nonce all equal — and
+ *      the action NOISE_ACTION_WRITE_MESSAGE, _READ_MESSAGE or _SPLIT:
+ *      otherwise NOISE_ERROR_INVALID_STATE;
+ *   4. for each private key, both objects hold it per session and dst in rows
+ *      it owns (dst came from _new_like), or both hold it once for all through
+ *      the same pointer, or neither holds it: otherwise
+ *      NOISE_ERROR_INVALID_PARAM;
+ *   5. m == 0 gives NOISE_ERROR_NONE, and nothing is launched;
+ *   6. a NULL list with m above that object's n gives
+ *      NOISE_ERROR_INVALID_PARAM;
+ *   7. [d_result, + m) meeting [d_dst_lanes, + 4 m) or [d_src_lanes, + 4 m)
+ *      gives NOISE_ERROR_INVALID_PARAM.
+ *
+ * _drop is the scrub half alone, for sessions that timed out: the rows of the
+ * named lanes are zeroed and their status set to 5.  A lane >= n is ignored.
+ * An object from _new may drop as well (its caller's key memory is not
+ * written).  Checked as _clear_keys (section 10): a NULL hs gives
+ * NOISE_ERROR_INVALID_PARAM; m == 0 NOISE_ERROR_NONE and no launch; m > n or a
+ * NULL d_lanes NOISE_ERROR_INVALID_PARAM.  The lanes must be distinct.
+ *
+ * All three are asynchronous on `stream`, copy nothing to the host and never
+ * synchronise; _move and _drop allocate nothing.
+ *
+ * What stays out.  _fallback from an object made by _new_like gives
+ * NOISE_ERROR_NOT_APPLICABLE: the fallback would read ephemeral rows owned by
+ * an object that may be freed first.  _fallback_merge pairs the lanes of two
+ * objects by index and knows nothing of moves: a cohort taken out of a
+ * fallback object does not merge, it hands its own split to _set_keys with
+ * the two key pointers exchanged (d_k1 = the split's k2, d_k2 = its k1), which
+ * is the orientation of the original role.  There is no compaction by a
+ * device-side predicate, no move between positions and no growing of an
+ * object.
+ *
+ * The flow: cohorts of first messages are read and answered in objects of
+ * their own; each cohort is moved whole into one long-lived pool object made
+ * by _new_like; each tick the host lists the pool lanes whose last message
+ * arrived, as it lists the transport's slots, makes _new_like(pool, m), moves
+ * those lanes into it, reads, splits, calls _set_keys with the slot list and
+ * the cohort's status array, and frees the cohort. */
+#define NOISE_AEAD_MOVED      0
+#define NOISE_AEAD_MOVE_EMPTY 1
+#define NOISE_AEAD_MOVE_TAKEN 2
+#define NOISE_AEAD_MOVE_RANGE 3
+int noise_aead_dev_handshake_new_like(NoiseAeadDevHandshake **out, const NoiseAeadDevHandshake *like,
+                                      uint32_t capacity, void *stream);
+int noise_aead_dev_handshake_move(NoiseAeadDevHandshake *dst, const uint32_t *d_dst_lanes /* may be NULL */,
+                                  NoiseAeadDevHandshake *src, const uint32_t *d_src_lanes /* may be NULL */,
+                                  uint32_t m, uint8_t *d_result /* may be NULL */, void *stream);
+int noise_aead_dev_handshake_drop(NoiseAeadDevHandshake *hs, const uint32_t *d_lanes, uint32_t m, void *stream);
+
 /* ------------------------------------------------ error reports
  * include/noise/protocol/errors.h; src/protocol/errors.c:92-127. */
 void noise_perror(const char *s, int err);

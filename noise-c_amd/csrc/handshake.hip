@@ -43,7 +43,13 @@
  *                 for the others, 5 here for a live session that leaves — and
  *                 the copy of the public keys the new object keeps;
  *   hs_fallback_merge  the fallback's split folded into the original's, the
- *                 keys swapped back into the original role's orientation.
+ *                 keys swapped back into the original role's orientation;
+ *   hs_move       sessions that change their object (header section 16): entry
+ *                 j of a lane list by hs_move_rule (handshake_plan.h) — a moved
+ *                 session's ck, h, k, status, keys received and per-session key
+ *                 rows go through registers into the other object's lane, then
+ *                 the lane it left is scrubbed;
+ *   hs_drop       that scrub alone: the lane's rows zeroed, its status 5.
  * A fallback object is an ordinary object whose pattern is HS_XXFALLBACK: its
  * start-up ends with the pre-message e, and every call below serves it.
  * DH tokens are the ladder launches of noise_aead_dev_dh_calculate into an
@@ -328,6 +334,102 @@ __global__ __launch_bounds__(HS_BLOCK) void hs_fallback_merge(MergeArgs a)
     a.status[i] = st;
 }
 
+/* ---- sessions that change their object (header section 16).  What hs_move
+   and hs_drop need of one object: its per-session rows.  A public-key row is
+   per session at stride 32 (stride 0: one row for all, never moved or
+   scrubbed); ls_priv / le_priv are read at their stride from wherever they
+   lie, ls_own / le_own are the rows the object owns (NULL: none, the key is
+   the caller's, shared or absent). */
+struct LaneRows {
+    uint32_t n;
+    const uint32_t *lanes; /* NULL: entry j is lane j */
+    uint8_t *ck, *h, *k, *ctx, *status, *re, *rs, *ls_pub, *le_pub;
+    uint64_t ls_pub_stride, le_pub_stride;
+    const uint8_t *ls_priv, *le_priv;
+    uint64_t ls_stride, le_stride;
+    uint8_t *ls_own, *le_own;
+    __device__ __forceinline__ uint32_t lane(uint32_t j) const { return lanes ? lanes[j] : j; }
+};
+
+/* `bytes` (a multiple of 16) from one 16-byte aligned row of an arena to another, through registers */
+__device__ __forceinline__ void move_row(uint8_t *dst, const uint8_t *src, uint32_t bytes)
+{
+    for (uint32_t j = 0; j < bytes; j += 16) *(uint4 *)(dst + j) = *(const uint4 *)(src + j);
+}
+
+__device__ __forceinline__ void zero_row(uint8_t *row, uint32_t bytes)
+{
+    for (uint32_t j = 0; j < bytes; j += 16) *(uint4 *)(row + j) = make_uint4(0, 0, 0, 0);
+}
+
+/* a private key from any address into an owned row: eight words in registers */
+__device__ __forceinline__ void take_priv(uint8_t *own, const uint8_t *priv)
+{
+    uint32_t w[8];
+#pragma unroll
+    for (int j = 0; j < 8; ++j)
+        w[j] = (uint32_t)priv[4 * j] | (uint32_t)priv[4 * j + 1] << 8 | (uint32_t)priv[4 * j + 2] << 16 |
+               (uint32_t)priv[4 * j + 3] << 24;
+    *(uint4 *)own = make_uint4(w[0], w[1], w[2], w[3]);
+    *(uint4 *)(own + 16) = make_uint4(w[4], w[5], w[6], w[7]);
+}
+
+/* every row of lane i that the object owns zeroed, the status 5 */
+__device__ __forceinline__ void scrub_lane(const LaneRows &o, uint32_t i, uint32_t hl, uint32_t ctx_bytes)
+{
+    zero_row(o.ck + (size_t)i * hl, hl);
+    zero_row(o.h + (size_t)i * hl, hl);
+    zero_row(o.k + (size_t)i * 32, 32);
+    zero_row(o.re + (size_t)i * 32, 32);
+    zero_row(o.rs + (size_t)i * 32, 32);
+    if (o.ls_pub_stride) zero_row(o.ls_pub + (size_t)i * 32, 32);
+    if (o.le_pub_stride) zero_row(o.le_pub + (size_t)i * 32, 32);
+    if (o.ls_own) zero_row(o.ls_own + (size_t)i * 32, 32);
+    if (o.le_own) zero_row(o.le_own + (size_t)i * 32, 32);
+    uint32_t *ctx = (uint32_t *)(o.ctx + (size_t)i * ctx_bytes);
+    for (uint32_t j = 0; j < ctx_bytes / 4; ++j) ctx[j] = 0; /* 0 bytes under ChaChaPoly: its context is k */
+    o.status[i] = HS_STATUS_ABSENT;
+}
+
+struct MoveArgs {
+    LaneRows src, dst;
+    uint32_t m, hl, ctx_bytes; /* ctx_bytes: of src's AES-GCM contexts, 0 under ChaChaPoly */
+    uint8_t *result;
+};
+
+/* noise_aead_dev_handshake_move: entry j by hs_move_rule (handshake_plan.h) */
+__global__ __launch_bounds__(HS_BLOCK) void hs_move(MoveArgs a)
+{
+    const uint32_t j = blockIdx.x * HS_BLOCK + threadIdx.x;
+    if (j >= a.m) return;
+    const uint32_t s = a.src.lane(j), d = a.dst.lane(j);
+    const bool in_range = s < a.src.n && d < a.dst.n;
+    const uint8_t st = in_range ? a.src.status[s] : 0;
+    const uint8_t r = hs_move_rule(s < a.src.n, d < a.dst.n, st, in_range ? a.dst.status[d] : 0);
+    if (a.result) a.result[j] = r;
+    if (r != NOISE_AEAD_MOVED) return;
+    move_row(a.dst.ck + (size_t)d * a.hl, a.src.ck + (size_t)s * a.hl, a.hl);
+    move_row(a.dst.h + (size_t)d * a.hl, a.src.h + (size_t)s * a.hl, a.hl);
+    move_row(a.dst.k + (size_t)d * 32, a.src.k + (size_t)s * 32, 32);
+    move_row(a.dst.re + (size_t)d * 32, a.src.re + (size_t)s * 32, 32);
+    move_row(a.dst.rs + (size_t)d * 32, a.src.rs + (size_t)s * 32, 32);
+    if (a.src.ls_pub_stride) move_row(a.dst.ls_pub + (size_t)d * 32, a.src.ls_pub + (size_t)s * 32, 32);
+    if (a.src.le_pub_stride) move_row(a.dst.le_pub + (size_t)d * 32, a.src.le_pub + (size_t)s * 32, 32);
+    if (a.dst.ls_own) take_priv(a.dst.ls_own + (size_t)d * 32, a.src.ls_priv + (uint64_t)s * a.src.ls_stride);
+    if (a.dst.le_own) take_priv(a.dst.le_own + (size_t)d * 32, a.src.le_priv + (uint64_t)s * a.src.le_stride);
+    scrub_lane(a.src, s, a.hl, a.ctx_bytes);
+    a.dst.status[d] = st;
+}
+
+/* noise_aead_dev_handshake_drop */
+__global__ __launch_bounds__(HS_BLOCK) void hs_drop(LaneRows o, uint32_t m, uint32_t hl, uint32_t ctx_bytes)
+{
+    const uint32_t j = blockIdx.x * HS_BLOCK + threadIdx.x;
+    if (j >= m) return;
+    const uint32_t i = o.lanes[j];
+    if (i < o.n) scrub_lane(o, i, hl, ctx_bytes);
+}
+
 } // namespace
 
 struct NoiseAeadDevHandshake {
@@ -338,9 +440,13 @@ struct NoiseAeadDevHandshake {
     bool keyed, ctx_stale;
     uint64_t nonce;
     size_t ctx_bytes;
-    /* the caller's private keys (read by the DH steps) */
+    /* the private keys (read by the DH steps): the caller's, or — per-session
+       keys of an object from _new_like — the owned rows ls_own / le_own */
     const uint8_t *ls_priv, *le_priv;
     uint64_t ls_stride, le_stride;
+    HsHold ls_hold, le_hold;
+    bool made_like;
+    uint8_t *ls_own, *le_own; /* parts of dev, or NULL */
     DevArena dev; /* the one device allocation; the pointers below are its parts */
     uint8_t *ck, *h, *k, *ctx, *arena, *status, *step, *ls_pub, *le_pub, *re, *rs;
     RecDesc *recs;
@@ -513,8 +619,9 @@ int start_symmetric(Hs *hs, const char *name, const uint8_t *d_prologue, uint64_
     return rc;
 }
 
-/* the device arrays of an object of n > 0 sessions */
-bool carve(Hs *hs)
+/* the device arrays of an object of n > 0 sessions; own_ls, own_le: rows of
+   its own for the private keys as well (_new_like) */
+bool carve(Hs *hs, bool own_ls = false, bool own_le = false)
 {
     const size_t n = hs->n;
     DevArena &d = hs->dev;
@@ -524,7 +631,10 @@ bool carve(Hs *hs)
     const size_t o_arena = d.carve(n * 32), o_status = d.carve(n), o_step = d.carve(n);
     const size_t o_ls = d.carve(n * 32), o_le = d.carve(n * 32), o_re = d.carve(n * 32);
     const size_t o_rs = d.carve(n * 32), o_recs = d.carve(n * sizeof(RecDesc));
+    const size_t o_ls_own = d.carve(own_ls ? n * 32 : 0), o_le_own = d.carve(own_le ? n * 32 : 0);
     if (!d.alloc()) return false;
+    hs->ls_own = own_ls ? d.at(o_ls_own) : nullptr;
+    hs->le_own = own_le ? d.at(o_le_own) : nullptr;
     hs->ck = d.at(o_ck); hs->h = d.at(o_h); hs->k = d.at(o_k); hs->ctx = d.at(o_ctx); hs->arena = d.at(o_arena);
     hs->status = d.at(o_status); hs->step = d.at(o_step); hs->ls_pub = d.at(o_ls); hs->le_pub = d.at(o_le);
     hs->re = d.at(o_re); hs->rs = d.at(o_rs); hs->recs = d.at<RecDesc>(o_recs);
@@ -624,6 +734,8 @@ int noise_aead_dev_handshake_new(NoiseAeadDevHandshake **out, const NoiseAeadHan
     hs->le_stride = cfg->local_ephemeral_stride;
     hs->ls_pub_stride = hs->ls_stride ? HS_DH_LEN : 0;
     hs->le_pub_stride = hs->le_stride ? HS_DH_LEN : 0;
+    hs->ls_hold = hs_hold_of(hs->ls_priv, hs->ls_stride);
+    hs->le_hold = hs_hold_of(hs->le_priv, hs->le_stride);
     if (hs->n) {
         if (!carve(hs)) {
             delete hs;
@@ -744,7 +856,7 @@ int noise_aead_dev_handshake_fallback(NoiseAeadDevHandshake *hs, const NoiseAead
 {
     if (out) *out = nullptr;
     HsFallbackFrom from = {};
-    if (hs) from = {&pattern_of(hs), hs->name.psk, hs->role, hs->action, hs->index, hs->ls_priv != nullptr};
+    if (hs) from = {&pattern_of(hs), hs->name.psk, hs->role, hs->action, hs->index, hs->ls_hold != HS_HOLD_NONE, hs->made_like};
     int rc = hs_check_fallback(from, cfg, out);
     if (rc) return rc;
     char name[HS_NAME_MAX];
@@ -765,6 +877,8 @@ int noise_aead_dev_handshake_fallback(NoiseAeadDevHandshake *hs, const NoiseAead
     fb->le_priv = init ? cfg->d_local_ephemeral_priv : hs->le_priv;
     fb->le_stride = init ? cfg->local_ephemeral_stride : hs->le_stride;
     fb->le_pub_stride = fb->le_stride ? HS_DH_LEN : 0;
+    fb->ls_hold = hs_hold_of(fb->ls_priv, fb->ls_stride);
+    fb->le_hold = hs_hold_of(fb->le_priv, fb->le_stride);
     if (fb->n) {
         if (!carve(fb)) {
             delete fb;
@@ -793,6 +907,98 @@ int noise_aead_dev_handshake_fallback_merge(const NoiseAeadDevHandshake *fb, con
     if (rc || !fb->n) return rc;
     const MergeArgs a = {fb->hl, fb->n, fb->status, d_hs_status, d_fb_k1, d_fb_k2, d_fb_h, d_k1, d_k2, d_h, d_status};
     return launch_items(hs_fallback_merge, fb->n, HS_BLOCK, (hipStream_t)stream, a);
+}
+
+int noise_aead_dev_handshake_new_like(NoiseAeadDevHandshake **out, const NoiseAeadDevHandshake *like,
+                                      uint32_t capacity, void *stream)
+{
+    if (out) *out = nullptr;
+    int rc = hs_check_new_like(out, like, like ? like->action : NOISE_ACTION_NONE);
+    if (rc) return rc;
+    Hs *hs = new (std::nothrow) Hs();
+    if (!hs) return NOISE_ERROR_NO_MEMORY;
+    hs->name = like->name;
+    hs->fallback = like->fallback;
+    hs->role = like->role;
+    hs->action = like->action;
+    hs->index = like->index;
+    hs->n = capacity;
+    hs->hl = like->hl;
+    hs->keyed = like->keyed;
+    hs->ctx_stale = like->keyed;
+    hs->nonce = like->nonce;
+    hs->ctx_bytes = like->ctx_bytes;
+    hs->made_like = true;
+    hs->ls_hold = like->ls_hold;
+    hs->le_hold = like->le_hold;
+    hs->ls_pub_stride = like->ls_pub_stride;
+    hs->le_pub_stride = like->le_pub_stride;
+    const bool own_ls = hs->ls_hold == HS_HOLD_EACH, own_le = hs->le_hold == HS_HOLD_EACH;
+    if (hs->n && !carve(hs, own_ls, own_le)) {
+        delete hs;
+        return NOISE_ERROR_NO_MEMORY;
+    }
+    /* per session: the owned rows (NULL with no lanes); once for all: like's pointer */
+    hs->ls_priv = own_ls ? hs->ls_own : like->ls_priv;
+    hs->ls_stride = own_ls ? HS_DH_LEN : like->ls_stride;
+    hs->le_priv = own_le ? hs->le_own : like->le_priv;
+    hs->le_stride = own_le ? HS_DH_LEN : like->le_stride;
+    if (hs->n) {
+        hipStream_t s = (hipStream_t)stream;
+        rc = hs->dev.zero(s);
+        if (!rc) rc = hip_rc(hipMemsetAsync(hs->status, HS_STATUS_ABSENT, hs->n, s));
+        /* the one public-key row of a shared key (an object of no lanes has none to copy) */
+        if (!rc && like->n && hs->ls_hold == HS_HOLD_SHARED)
+            rc = launch_items(hs_copy32, 1, HS_BLOCK, s, (const uint8_t *)like->ls_pub, (uint64_t)0, hs->ls_pub, 1u);
+        if (!rc && like->n && hs->le_hold == HS_HOLD_SHARED)
+            rc = launch_items(hs_copy32, 1, HS_BLOCK, s, (const uint8_t *)like->le_pub, (uint64_t)0, hs->le_pub, 1u);
+        if (rc) {
+            noise_aead_dev_handshake_free(hs);
+            return rc;
+        }
+    }
+    *out = hs;
+    return NOISE_ERROR_NONE;
+}
+
+namespace {
+
+LaneRows lane_rows(const Hs *hs, const uint32_t *d_lanes)
+{
+    return {hs->n, d_lanes, hs->ck, hs->h, hs->k, hs->ctx, hs->status, hs->re, hs->rs, hs->ls_pub, hs->le_pub,
+            hs->ls_pub_stride, hs->le_pub_stride, hs->ls_priv, hs->le_priv, hs->ls_stride, hs->le_stride,
+            hs->ls_own, hs->le_own};
+}
+
+HsMoveSide move_side(const Hs *hs, const uint32_t *d_lanes)
+{
+    if (!hs) return {};
+    return {hs,
+            {hs->name, hs->fallback, hs->role, hs->action, hs->index, hs->keyed, hs->nonce},
+            {{hs->ls_hold, hs->ls_priv, hs->made_like}, {hs->le_hold, hs->le_priv, hs->made_like}},
+            hs->n,
+            d_lanes};
+}
+
+uint32_t aes_ctx_bytes(const Hs *hs) { return hs->name.cipher_id == NOISE_CIPHER_AESGCM ? (uint32_t)hs->ctx_bytes : 0; }
+
+} // namespace
+
+int noise_aead_dev_handshake_move(NoiseAeadDevHandshake *dst, const uint32_t *d_dst_lanes, NoiseAeadDevHandshake *src,
+                                  const uint32_t *d_src_lanes, uint32_t m, uint8_t *d_result, void *stream)
+{
+    const int rc = hs_check_move(move_side(dst, d_dst_lanes), move_side(src, d_src_lanes), m, d_result);
+    if (rc || !m) return rc;
+    if (dst->keyed) dst->ctx_stale = true; /* the contexts are not moved: prepared from k, as after a MixKey */
+    const MoveArgs a = {lane_rows(src, d_src_lanes), lane_rows(dst, d_dst_lanes), m, src->hl, aes_ctx_bytes(src), d_result};
+    return launch_items(hs_move, m, HS_BLOCK, (hipStream_t)stream, a);
+}
+
+int noise_aead_dev_handshake_drop(NoiseAeadDevHandshake *hs, const uint32_t *d_lanes, uint32_t m, void *stream)
+{
+    const int rc = hs_check_drop(hs, hs ? hs->n : 0, d_lanes, m);
+    if (rc || !m) return rc;
+    return launch_items(hs_drop, m, HS_BLOCK, (hipStream_t)stream, lane_rows(hs, d_lanes), m, hs->hl, aes_ctx_bytes(hs));
 }
 
 const uint8_t *noise_aead_dev_handshake_status(const NoiseAeadDevHandshake *hs) { return hs ? hs->status : nullptr; }

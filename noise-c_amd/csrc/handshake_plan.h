@@ -8,7 +8,11 @@
  * Pipes fallback (header section 15): XXfallback as a pattern of its own, its
  * name, who takes part (hs_fallback_takes, which the kernel runs too), the
  * merge rule and the argument checks of the two calls
- * (asan/handshake_fallback_check.cpp, tests/test_handshake_fallback_host.py).
+ * (asan/handshake_fallback_check.cpp, tests/test_handshake_fallback_host.py),
+ * and the sessions that change their object (header section 16): the rule of
+ * one entry of a move (hs_move_rule, which the kernel runs too), the position
+ * two objects must share and the argument checks of _new_like, _move and _drop
+ * (asan/handshake_move_check.cpp, tests/test_handshake_move_host.py).
  *
  * No HIP header is included and no device pointer is dereferenced, so all of
  * it compiles with a host compiler alone and runs under ASan/UBSan
@@ -515,13 +519,14 @@ struct HsFallbackFrom {
     bool psk;
     int role, action, index;  /* index: messages done */
     bool has_static;          /* a static private key was given to _new */
+    bool made_like = false;   /* the object came from _new_like (section 16): it owns its private-key rows */
 };
 
 /* noise_aead_dev_handshake_fallback, in the order of the header */
 inline int hs_check_fallback(const HsFallbackFrom &from, const NoiseAeadHandshakeFallbackConfig *cfg, const void *fb)
 {
     if (!from.pattern || !cfg || !fb) return NOISE_ERROR_INVALID_PARAM;
-    if (from.pattern->pre_r_e || !hs_fallback_possible(*from.pattern)) return NOISE_ERROR_NOT_APPLICABLE;
+    if (from.pattern->pre_r_e || !hs_fallback_possible(*from.pattern) || from.made_like) return NOISE_ERROR_NOT_APPLICABLE;
     const bool init = hs_is_initiator(from.role);
     if (from.index != 1 || from.action != (init ? NOISE_ACTION_READ_MESSAGE : NOISE_ACTION_WRITE_MESSAGE))
         return NOISE_ERROR_INVALID_STATE;
@@ -553,6 +558,105 @@ inline int hs_check_fallback_merge(const void *fb, int action, uint32_t n, uint3
     for (int o = 0; o < 4; ++o)
         for (int i = 0; i < 5; ++i)
             if (hs_ranges_meet(outs[o], out_bytes[o], ins[i], in_bytes[i])) return NOISE_ERROR_INVALID_PARAM;
+    return NOISE_ERROR_NONE;
+}
+
+/* ------------------------------------------ sessions that change their object
+   noise_aead_dev_handshake_new_like / _move / _drop (header section 16): the
+   rule of one entry of a move — one statement for both compilers, run by the
+   hs_move kernel of handshake.hip and by asan/handshake_move_check.cpp — what
+   "the same position" means, and the argument checks of the three calls. */
+
+/* The outcome of entry j, the byte _move writes to d_result[j].  The causes
+   are tested in this order; the statuses are not looked at (and the kernel
+   reads none) unless both lane numbers are in range. */
+HS_FN uint8_t hs_move_rule(bool src_in_range, bool dst_in_range, uint8_t src_status, uint8_t dst_status)
+{
+    if (!src_in_range || !dst_in_range) return NOISE_AEAD_MOVE_RANGE;
+    if (src_status == HS_STATUS_ABSENT) return NOISE_AEAD_MOVE_EMPTY;
+    if (dst_status != HS_STATUS_ABSENT) return NOISE_AEAD_MOVE_TAKEN;
+    return NOISE_AEAD_MOVED;
+}
+
+/* everything of an object that is the same for all its sessions and lives on
+   the host: where it stands in which handshake */
+struct HsPosition {
+    HsName name;
+    bool fallback;
+    int role, action, index;
+    bool keyed;
+    uint64_t nonce;
+};
+
+inline bool hs_same_position(const HsPosition &a, const HsPosition &b)
+{
+    return a.name.pattern == b.name.pattern && a.name.cipher_id == b.name.cipher_id && a.name.hash_id == b.name.hash_id &&
+           a.name.psk == b.name.psk && a.fallback == b.fallback && a.role == b.role && a.action == b.action &&
+           a.index == b.index && a.keyed == b.keyed && a.nonce == b.nonce;
+}
+
+/* how an object holds one of its two private keys */
+enum HsHold : uint8_t {
+    HS_HOLD_NONE,   /* it never had it */
+    HS_HOLD_SHARED, /* once for all: stride 0, the caller's memory */
+    HS_HOLD_EACH,   /* per session: the caller's rows, or rows the object owns (_new_like) */
+};
+
+struct HsKey {
+    HsHold hold;
+    const void *ptr; /* compared for HS_HOLD_SHARED alone */
+    bool owned;      /* HS_HOLD_EACH: the rows are the object's own */
+};
+
+inline HsHold hs_hold_of(const void *priv, uint64_t stride) { return !priv ? HS_HOLD_NONE : (stride ? HS_HOLD_EACH : HS_HOLD_SHARED); }
+
+/* noise_aead_dev_handshake_new_like */
+inline int hs_check_new_like(const void *out, const void *like, int action)
+{
+    if (!out || !like) return NOISE_ERROR_INVALID_PARAM;
+    if (action != NOISE_ACTION_WRITE_MESSAGE && action != NOISE_ACTION_READ_MESSAGE && action != NOISE_ACTION_SPLIT)
+        return NOISE_ERROR_INVALID_STATE;
+    return NOISE_ERROR_NONE;
+}
+
+/* one object of a move, as the host knows it; pos and keys are not looked at when obj is NULL */
+struct HsMoveSide {
+    const void *obj;
+    HsPosition pos;
+    HsKey keys[2]; /* static, ephemeral */
+    uint32_t n;
+    const void *d_lanes;
+};
+
+/* noise_aead_dev_handshake_move, in the order of the header */
+inline int hs_check_move(const HsMoveSide &dst, const HsMoveSide &src, uint32_t m, const void *d_result)
+{
+    if (!dst.obj || !src.obj) return NOISE_ERROR_INVALID_PARAM;
+    if (dst.obj == src.obj) return NOISE_ERROR_INVALID_PARAM;
+    const int action = src.pos.action;
+    if (!hs_same_position(dst.pos, src.pos) ||
+        (action != NOISE_ACTION_WRITE_MESSAGE && action != NOISE_ACTION_READ_MESSAGE && action != NOISE_ACTION_SPLIT))
+        return NOISE_ERROR_INVALID_STATE;
+    for (int k = 0; k < 2; ++k) {
+        const HsKey &d = dst.keys[k], &s = src.keys[k];
+        if (d.hold != s.hold) return NOISE_ERROR_INVALID_PARAM;
+        if (d.hold == HS_HOLD_SHARED && d.ptr != s.ptr) return NOISE_ERROR_INVALID_PARAM;
+        if (d.hold == HS_HOLD_EACH && !d.owned) return NOISE_ERROR_INVALID_PARAM; /* the caller's memory is never written */
+    }
+    if (!m) return NOISE_ERROR_NONE;
+    if ((!dst.d_lanes && m > dst.n) || (!src.d_lanes && m > src.n)) return NOISE_ERROR_INVALID_PARAM;
+    if (hs_ranges_meet(d_result, d_result ? m : 0, dst.d_lanes, dst.d_lanes ? (hs_u128)4 * m : 0) ||
+        hs_ranges_meet(d_result, d_result ? m : 0, src.d_lanes, src.d_lanes ? (hs_u128)4 * m : 0))
+        return NOISE_ERROR_INVALID_PARAM;
+    return NOISE_ERROR_NONE;
+}
+
+/* noise_aead_dev_handshake_drop: as noise_aead_dev_transport_clear_keys (section 10) */
+inline int hs_check_drop(const void *hs, uint32_t n, const void *d_lanes, uint32_t m)
+{
+    if (!hs) return NOISE_ERROR_INVALID_PARAM;
+    if (!m) return NOISE_ERROR_NONE;
+    if (m > n || !d_lanes) return NOISE_ERROR_INVALID_PARAM;
     return NOISE_ERROR_NONE;
 }
 

@@ -206,6 +206,9 @@ def lib() -> C.CDLL:
         "noise_aead_dev_handshake_remote_static": (vp, [vp]),
         "noise_aead_dev_handshake_fallback": (i, [vp, P(NoiseAeadHandshakeFallbackConfig), P(vp), vp]),
         "noise_aead_dev_handshake_fallback_merge": (i, [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]),
+        "noise_aead_dev_handshake_new_like": (i, [P(vp), vp, C.c_uint32, vp]),
+        "noise_aead_dev_handshake_move": (i, [vp, vp, vp, vp, C.c_uint32, vp, vp]),
+        "noise_aead_dev_handshake_drop": (i, [vp, vp, C.c_uint32, vp]),
         "noise_aead_dev_transport_new": (i, [P(vp), i, i, C.c_uint32, vp, vp, C.c_uint32, vp]),
         "noise_aead_dev_transport_free": (i, [vp]),
         "noise_aead_dev_transport_nonces": (vp, [vp, i]),
@@ -635,6 +638,31 @@ def dev_handshake_fallback_merge(fb: int, *, hs_status: int, k1: int, k2: int, f
     return lib().noise_aead_dev_handshake_fallback_merge(fb, hs_status or None, k1 or None, k2 or None, fb_k1 or None,
                                                          fb_k2 or None, h or None, fb_h or None, status or None,
                                                          stream or None)
+
+
+# ---- sessions that change their object (include/noise_aead_hip.h section 16)
+
+MOVED, MOVE_EMPTY, MOVE_TAKEN, MOVE_RANGE = 0, 1, 2, 3
+
+
+def dev_handshake_new_like(like: int, capacity: int, *, stream: int = 0, no_out: bool = False):
+    """noise_aead_dev_handshake_new_like: (rc, hs); hs is None unless rc == 0.
+    no_out: a NULL out pointer, for the argument tests."""
+    hs = C.c_void_p()
+    rc = lib().noise_aead_dev_handshake_new_like(None if no_out else C.byref(hs), like or None, capacity, stream or None)
+    return rc, hs.value
+
+
+def dev_handshake_move(dst: int, src: int, m: int, *, dst_lanes: int = 0, src_lanes: int = 0, result: int = 0,
+                       stream: int = 0) -> int:
+    """noise_aead_dev_handshake_move: dst_lanes / src_lanes: m uint32 on the
+    device, or 0 for 0 .. m-1; result: m bytes the call writes, or 0."""
+    return lib().noise_aead_dev_handshake_move(dst or None, dst_lanes or None, src or None, src_lanes or None, m,
+                                               result or None, stream or None)
+
+
+def dev_handshake_drop(hs: int, *, lanes: int, m: int, stream: int = 0) -> int:
+    return lib().noise_aead_dev_handshake_drop(hs or None, lanes or None, m, stream or None)
 
 
 # ---- device-resident transport sessions (include/noise_aead_hip.h section 9);
