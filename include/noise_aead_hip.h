@@ -87,6 +87,8 @@ typedef struct {
 #define NOISE_ERROR_LOCAL_KEY_REQUIRED NOISE_ID('E', 8)
 #define NOISE_ERROR_PSK_REQUIRED NOISE_ID('E', 9)
 #define NOISE_ERROR_INVALID_PUBLIC_KEY NOISE_ID('E', 15)
+#define NOISE_SIGN_ED25519 NOISE_ID('S', 1) /* constants.h:108, 148 */
+#define NOISE_ERROR_INVALID_SIGNATURE NOISE_ID('E', 17)
 #endif
 
 /* ------------------------------------------------ 1. CipherState API
@@ -599,7 +601,10 @@ int noise_aead_dev_dh_public(int dh_id, const uint8_t *d_priv, uint64_t priv_str
  * failed: NOISE_ERROR_MAC_FAILURE), 3 (the received ephemeral was all-zero:
  * NOISE_ERROR_INVALID_PUBLIC_KEY, :1464-1470) or 4 (a length a ragged call
  * refuses: NOISE_ERROR_INVALID_LENGTH); 2 stays reserved as in the
- * ragged calls; 5 is the fallback's "not in this object" (section 15).  The
+ * ragged calls; 5 is the fallback's "not in this object" (section 15); 6 is
+ * never written by a handshake call: it is section 17's "signature refused:
+ * NOISE_ERROR_INVALID_SIGNATURE", which noise_aead_dev_sign_verify merges into
+ * a copy of these bytes or into the bytes themselves.  The
  * first failure is sticky.  A failed session writes only
  * inside its own slots and its later output bytes are unspecified; its opens
  * never write unauthenticated plaintext (the verify-first order) and nothing
@@ -1357,6 +1362,96 @@ int noise_aead_dev_handshake_move(NoiseAeadDevHandshake *dst, const uint32_t *d_
                                   NoiseAeadDevHandshake *src, const uint32_t *d_src_lanes /* may be NULL */,
                                   uint32_t m, uint8_t *d_result /* may be NULL */, void *stream);
 int noise_aead_dev_handshake_drop(NoiseAeadDevHandshake *hs, const uint32_t *d_lanes, uint32_t m, void *stream);
+
+/* ------------------------------------------------ 17. batched Ed25519
+ *
+ * n calls of noise_signstate_verify, or of noise_signstate_sign, for Ed25519
+ * (src/protocol/signstate.c:544-597 over src/backend/ref/sign-ed25519.c and
+ * src/crypto/ed25519/ed25519.c:45-116) in one launch, so that a responder
+ * that learns a client's static key in a handshake message can decide whether
+ * a certificate authorises it, and hand the verdict to
+ * noise_aead_dev_transport_set_keys (section 10), without a host round trip.
+ * The three calls are stateless, as section 7's are: there is no object, the
+ * keys are the caller's arrays.  Entry i takes the 32-byte key at ptr +
+ * i*stride; a key stride of 0 is one key for all n entries (one certificate
+ * authority verifying n certificates), any other key stride must be at least
+ * 32.  Message i is the d_msg_len[i] bytes at d_msg + d_msg_off[i]: ragged, as
+ * the _ragged calls of section 8 take their messages, in any order, and two
+ * entries may share a message.  No pointer, stride or offset needs any
+ * alignment.
+ *
+ * noise_aead_dev_sign_verify.  Entry i is exactly ed25519_sign_open
+ * (ed25519.c:93-116) on message i, the public key at d_pub + i*pub_stride and
+ * the 64-byte signature R || S at d_sig + i*sig_stride (a stride of at least
+ * 64; 0 only with n == 1), the reference's leniencies included:
+ *   - a signature with any of the top three bits of S set (sig[63] & 0xE0) is
+ *     refused; S is otherwise reduced mod L, not range-checked, so S + L is
+ *     accepted where S is (a caller who needs strict signatures checks S < L);
+ *   - the public key is decoded as ge25519_unpack_negative_vartime decodes it
+ *     (ed25519-donna-impl-base.h:192-239): y is the low 255 bits whatever
+ *     their value (2^255 - 19 + k stands for k), the sign bit is not looked
+ *     at when x = 0, and a y for which x^2 has no root is refused;
+ *   - the check is the comparison of the 32 bytes encode([S]B - [h]A),
+ *     h = SHA-512(R || A || M) mod L, with the 32 bytes of R.  R is never
+ *     decoded, so a non-canonical R is refused; nothing is multiplied by the
+ *     cofactor, so keys of small order verify what the equation says they do.
+ * d_status[i] is 0 where the reference returns NOISE_ERROR_NONE and 6 where it
+ * returns NOISE_ERROR_INVALID_SIGNATURE (section 8's status space).  With
+ * d_status_in (typically noise_aead_dev_handshake_status(hs)), an entry whose
+ * input status is non-zero does no work and reads nothing of its own — not its
+ * offset, its length, its key nor its signature — and d_status[i] =
+ * d_status_in[i]; the output array is then directly the d_status of
+ * noise_aead_dev_transport_set_keys.  d_status == d_status_in is allowed: the
+ * merge happens in place.  Everything verify reads is public, and its running
+ * time depends on it.
+ *
+ * noise_aead_dev_sign_public is ed25519_publickey (ed25519.c:45-55) of the
+ * 32-byte seed at d_priv + i*priv_stride: the private key of a NoiseSignState
+ * is that seed.  Public key i goes to d_pub_out + 32*i.
+ * noise_aead_dev_sign is ed25519_sign (ed25519.c:58-91) of message i with
+ * seed i and the public key at d_pub + i*pub_stride, which is taken as given
+ * and never re-derived, as noise_signstate_sign signs with the stored key.
+ * Signature i goes to d_sig_out + 64*i.  Signing is deterministic: the bytes
+ * are the reference's.  There is no key generation: a seed is 32 bytes of the
+ * caller's entropy, as an ephemeral private key is.
+ *
+ * Constant time, for _sign_public and _sign: [k]B is 253 doublings with an
+ * addition at every step whose operand is the identity or B by mask; the
+ * scalars mod L are reduced without a branch; no branch, address, table index
+ * or loop bound depends on a bit of the seed, of the secret scalar, of the
+ * prefix, of r or of an intermediate value.  The seed's hash and the r hash
+ * run through the byte buffer of the device's SHA-512, indexed by position
+ * only, as the handshake kernels' keys are; the curve arithmetic of all three
+ * calls keeps its points in registers.  The message lengths are public.
+ *
+ * Checked on the host before any launch, in this order: sign_id other than
+ * NOISE_SIGN_ED25519 gives NOISE_ERROR_UNKNOWN_ID; n == 0 gives
+ * NOISE_ERROR_NONE and touches nothing; otherwise NOISE_ERROR_INVALID_PARAM
+ * for a NULL pointer (d_status_in alone may be NULL), for a key stride in
+ * 1..31, for a signature stride in 1..63 or of 0 with n > 1, and for an output
+ * range ([d_status, + n), [d_pub_out, + 32 n), [d_sig_out, + 64 n)) that meets
+ * an input key span ([ptr, + (n - 1)*stride + 32)), the signature span
+ * ([d_sig, + (n - 1)*sig_stride + 64)), the offset array [d_msg_off, + 8 n),
+ * the length array [d_msg_len, + 4 n) or [d_status_in, + n) — the one
+ * exception being d_status == d_status_in exactly.  The message spans are the
+ * caller's guarantee, as for every ragged call.  A refused call writes
+ * nothing.  Device pointers, asynchronous on `stream`; nothing is allocated
+ * and nothing synchronises.
+ *
+ * What stays out: the batch equation (ed25519_sign_open_batch), a host
+ * NoiseSignState object, keypair generation, and any parsing of a
+ * certificate: the caller says where the signed bytes and the signature lie. */
+int noise_aead_dev_sign_verify(int sign_id, const uint8_t *d_pub, uint64_t pub_stride,
+                               const uint8_t *d_sig, uint64_t sig_stride,
+                               const uint8_t *d_msg, const uint64_t *d_msg_off, const uint32_t *d_msg_len,
+                               uint32_t n, const uint8_t *d_status_in /* may be NULL */, uint8_t *d_status,
+                               void *stream);
+int noise_aead_dev_sign_public(int sign_id, const uint8_t *d_priv, uint64_t priv_stride, uint32_t n,
+                               uint8_t *d_pub_out, void *stream);
+int noise_aead_dev_sign(int sign_id, const uint8_t *d_priv, uint64_t priv_stride,
+                        const uint8_t *d_pub, uint64_t pub_stride,
+                        const uint8_t *d_msg, const uint64_t *d_msg_off, const uint32_t *d_msg_len,
+                        uint32_t n, uint8_t *d_sig_out, void *stream);
 
 /* ------------------------------------------------ error reports
  * include/noise/protocol/errors.h; src/protocol/errors.c:92-127. */

@@ -254,11 +254,13 @@ inline int check_duplex_ragged(const NoiseAeadRagged *sj, const NoiseAeadRagged 
 
 /* Batched X25519 (noise_aead_dev_dh_calculate / _dh_public; launch_dh.hip).
    The span of n 32-byte keys a stride apart; stride 0 is one key for all. */
-inline Span dh_key_span(const void *p, uint64_t stride, uint32_t n)
+inline Span item_span(const void *p, uint64_t stride, uint32_t n, uint32_t item)
 {
     const u128 lo = (uintptr_t)p;
-    return {lo, lo + (u128)(n - 1) * stride + 32};
+    return {lo, lo + (u128)(n - 1) * stride + item};
 }
+
+inline Span dh_key_span(const void *p, uint64_t stride, uint32_t n) { return item_span(p, stride, n, 32); }
 
 /* pub == nullptr with has_pub false: the base point (noise_aead_dev_dh_public).
    NOISE_ERROR_NONE with n == 0 means "nothing to do". */
@@ -285,6 +287,60 @@ inline int check_rekey(int cipher_id, const void *keys, uint32_t n, const void *
     if (!n) return NOISE_ERROR_NONE;
     if (!keys || !out) return NOISE_ERROR_INVALID_PARAM;
     if (out != keys && meet(dh_key_span(out, 32, n), dh_key_span(keys, 32, n))) return NOISE_ERROR_INVALID_PARAM;
+    return NOISE_ERROR_NONE;
+}
+
+/* Batched Ed25519 (noise_aead_dev_sign_verify / _sign_public / _sign, header
+   section 17; launch_sign.hip).  The rules in the header's order: the id,
+   n == 0, the pointers, the strides, then every output range against every
+   input the host can see (the message spans are the caller's guarantee). */
+
+inline bool sign_key_stride_bad(uint64_t stride) { return stride && stride < 32; }
+
+/* the offset and length arrays of a ragged message list against an output */
+inline bool sign_lists_meet(Span o, const void *off, const void *len, uint32_t n)
+{
+    return meet(o, item_span(off, 8, n, 8)) || meet(o, item_span(len, 4, n, 4));
+}
+
+inline int check_sign_verify(int sign_id, const void *pub, uint64_t pub_stride, const void *sig, uint64_t sig_stride,
+                             const void *msg, const void *msg_off, const void *msg_len, uint32_t n,
+                             const void *status_in, const void *status)
+{
+    if (sign_id != NOISE_SIGN_ED25519) return NOISE_ERROR_UNKNOWN_ID;
+    if (!n) return NOISE_ERROR_NONE;
+    if (!pub || !sig || !msg || !msg_off || !msg_len || !status) return NOISE_ERROR_INVALID_PARAM;
+    if (sign_key_stride_bad(pub_stride) || (sig_stride ? sig_stride < 64 : n > 1)) return NOISE_ERROR_INVALID_PARAM;
+    const Span o = item_span(status, 1, n, 1);
+    if (meet(o, item_span(pub, pub_stride, n, 32)) || meet(o, item_span(sig, sig_stride, n, 64)) ||
+        sign_lists_meet(o, msg_off, msg_len, n))
+        return NOISE_ERROR_INVALID_PARAM;
+    /* in place is the one overlap allowed */
+    if (status_in && status_in != status && meet(o, item_span(status_in, 1, n, 1))) return NOISE_ERROR_INVALID_PARAM;
+    return NOISE_ERROR_NONE;
+}
+
+inline int check_sign_public(int sign_id, const void *priv, uint64_t priv_stride, uint32_t n, const void *pub_out)
+{
+    if (sign_id != NOISE_SIGN_ED25519) return NOISE_ERROR_UNKNOWN_ID;
+    if (!n) return NOISE_ERROR_NONE;
+    if (!priv || !pub_out) return NOISE_ERROR_INVALID_PARAM;
+    if (sign_key_stride_bad(priv_stride)) return NOISE_ERROR_INVALID_PARAM;
+    if (meet(item_span(pub_out, 32, n, 32), item_span(priv, priv_stride, n, 32))) return NOISE_ERROR_INVALID_PARAM;
+    return NOISE_ERROR_NONE;
+}
+
+inline int check_sign(int sign_id, const void *priv, uint64_t priv_stride, const void *pub, uint64_t pub_stride,
+                      const void *msg, const void *msg_off, const void *msg_len, uint32_t n, const void *sig_out)
+{
+    if (sign_id != NOISE_SIGN_ED25519) return NOISE_ERROR_UNKNOWN_ID;
+    if (!n) return NOISE_ERROR_NONE;
+    if (!priv || !pub || !msg || !msg_off || !msg_len || !sig_out) return NOISE_ERROR_INVALID_PARAM;
+    if (sign_key_stride_bad(priv_stride) || sign_key_stride_bad(pub_stride)) return NOISE_ERROR_INVALID_PARAM;
+    const Span o = item_span(sig_out, 64, n, 64);
+    if (meet(o, item_span(priv, priv_stride, n, 32)) || meet(o, item_span(pub, pub_stride, n, 32)) ||
+        sign_lists_meet(o, msg_off, msg_len, n))
+        return NOISE_ERROR_INVALID_PARAM;
     return NOISE_ERROR_NONE;
 }
 

@@ -42,6 +42,7 @@ ERROR_INVALID_PARAM = NOISE_ID("E", 11)
 ERROR_INVALID_STATE = NOISE_ID("E", 12)
 ERROR_INVALID_NONCE = NOISE_ID("E", 13)
 ERROR_INVALID_PUBLIC_KEY = NOISE_ID("E", 15)
+ERROR_INVALID_SIGNATURE = NOISE_ID("E", 17)
 ROLE_INITIATOR = NOISE_ID("R", 1)  # constants.h:111-112
 ROLE_RESPONDER = NOISE_ID("R", 2)
 ACTION_NONE = 0  # constants.h:115-120
@@ -55,6 +56,8 @@ HASH_BLAKE2b = NOISE_ID("H", 2)
 HASH_SHA256 = NOISE_ID("H", 3)
 HASH_SHA512 = NOISE_ID("H", 4)
 DH_CURVE25519 = NOISE_ID("D", 1)  # constants.h:51
+SIGN_ED25519 = NOISE_ID("S", 1)  # constants.h:108
+STATUS_SIGNATURE_REFUSED = 6  # section 8's status space, written by dev_sign_verify
 HASH_LEN = {HASH_BLAKE2s: 32, HASH_BLAKE2b: 64, HASH_SHA256: 32, HASH_SHA512: 64}
 
 
@@ -193,6 +196,9 @@ def lib() -> C.CDLL:
         "noise_aead_dev_pad": (i, [vp, vp, C.c_uint64, vp, C.c_uint32, C.c_uint32, i, vp, vp]),
         "noise_aead_dev_dh_calculate": (i, [i, vp, C.c_uint64, vp, C.c_uint64, C.c_uint32, vp, vp]),
         "noise_aead_dev_dh_public": (i, [i, vp, C.c_uint64, C.c_uint32, vp, vp]),
+        "noise_aead_dev_sign_verify": (i, [i, vp, C.c_uint64, vp, C.c_uint64, vp, vp, vp, C.c_uint32, vp, vp, vp]),
+        "noise_aead_dev_sign_public": (i, [i, vp, C.c_uint64, C.c_uint32, vp, vp]),
+        "noise_aead_dev_sign": (i, [i, vp, C.c_uint64, vp, C.c_uint64, vp, vp, vp, C.c_uint32, vp, vp]),
         "noise_aead_dev_handshake_new": (i, [P(vp), P(NoiseAeadHandshakeConfig), vp]),
         "noise_aead_dev_handshake_free": (i, [vp]),
         "noise_aead_dev_handshake_get_action": (i, [vp]),
@@ -537,6 +543,34 @@ def dev_dh_public(dh_id: int, *, priv: int, priv_stride: int = 32, n: int, pub_o
     """noise_aead_dev_dh_public: the public key of each of n private keys."""
     return lib().noise_aead_dev_dh_public(dh_id, priv or None, priv_stride, n, pub_out or None,
                                           stream or None)
+
+
+def dev_sign_verify(sign_id: int, *, pub: int, pub_stride: int = 32, sig: int, sig_stride: int = 64,
+                    msg: int, msg_off: int, msg_len: int, n: int, status_in: int = 0, status: int,
+                    stream: int = 0) -> int:
+    """noise_aead_dev_sign_verify: n Ed25519 verdicts as status bytes (0, or 6:
+    refused); message i is msg_len[i] bytes at msg + msg_off[i] (device arrays
+    of u64 / u32).  A pub_stride of 0 is one signer for all; an entry whose
+    status_in byte is non-zero keeps that byte and reads nothing."""
+    return lib().noise_aead_dev_sign_verify(sign_id, pub or None, pub_stride, sig or None, sig_stride,
+                                            msg or None, msg_off or None, msg_len or None, n,
+                                            status_in or None, status or None, stream or None)
+
+
+def dev_sign_public(sign_id: int, *, priv: int, priv_stride: int = 32, n: int, pub_out: int,
+                    stream: int = 0) -> int:
+    """noise_aead_dev_sign_public: the Ed25519 public key of each of n 32-byte seeds."""
+    return lib().noise_aead_dev_sign_public(sign_id, priv or None, priv_stride, n, pub_out or None,
+                                            stream or None)
+
+
+def dev_sign(sign_id: int, *, priv: int, priv_stride: int = 32, pub: int, pub_stride: int = 32,
+             msg: int, msg_off: int, msg_len: int, n: int, sig_out: int, stream: int = 0) -> int:
+    """noise_aead_dev_sign: n signatures R || S, packed 64 bytes apart at
+    sig_out; the public keys are taken as given."""
+    return lib().noise_aead_dev_sign(sign_id, priv or None, priv_stride, pub or None, pub_stride,
+                                     msg or None, msg_off or None, msg_len or None, n, sig_out or None,
+                                     stream or None)
 
 
 # ---- batched handshakes (include/noise_aead_hip.h section 8); `hs` is the
